@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- reads/s of the MI355X Poisson-binomial read filter on BASELINE.json's configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both launch shapes work for every N: started WITHOUT torchrun and with --gpus N > 1, this script
@@ -18,9 +18,11 @@ Workload (config.workload):
           scaling (N = 2, 4 are the partial node with the same per-GPU shard).
 A "step" = one pass of the whole hot path over the resident batch: prepass -> scan -> scatter ->
 DP -> overflow pass, producing ee / Ns / pass for every read.  The wall-clock region carries no
-per-kernel events; the per-kernel HIP-event timing behind `roofline` is taken in a separate pass
-right after it.  Without --steps the timed region is sized to last >= 1 s (1.25 s of steps at the
-warm-up rate).
+per-kernel events; with --full, the per-kernel HIP-event timing behind `roofline` is taken in a separate
+pass right after it.  Without --steps the timed region is sized to last >= 1 s (1.25 s of steps at the
+warm-up rate).  `--dump-outputs DIR` writes what the last timed step computed (ee, Ns and pass of a fixed,
+seeded sample of 2^20 reads, with their read ids) as DIR/<name>.npy in float64: two builds run with the same
+arguments on the same inputs can be compared output for output.
 
 Collectives (N > 1): the data path has none.  Barriers, the rank-uniform step count and the max over ranks go over a
 gloo group (CPU tensors: nothing that can hang on a GPU communicator brackets the timed region beyond
@@ -35,10 +37,12 @@ Weak-scaling anchor: N > 1 times 125 M reads per GPU (configs[3]); the plain N =
 metric's own configuration).  The single-GPU point of the SAME per-GPU workload is `extras.config4_shard` of the N = 1
 line, or `python bench.py --gpus 1 --reads 125000000`.
 
-Output (rank 0): the headline as ONE JSON line as soon as the timed region, the event pass and cpu_baseline are done -- before
-anything optional runs -- and, at N = 1, the same line again with the live counters (`pmc_live`, roofline.traffic: rocprofv3 --pmc
-passes in fresh child processes over tools/pmc_probe.py) and with `extras` (tools/bench_extras.py) as the LAST line: a run that is
-killed inside an extra still leaves a complete headline on stdout.  Extra objects of the headline:
+Output (rank 0): a plain run sets up, warms up, times the steps and prints the headline as ONE JSON line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration and per-rank rates) -- nothing else.  Everything else runs
+only with --full: there the line is printed as soon as the timed region, the event pass and cpu_baseline are done -- before anything
+optional runs -- and, at N = 1, again with the live counters (`pmc_live`, roofline.traffic: rocprofv3 --pmc passes in fresh child
+processes over tools/pmc_probe.py) and with `extras` (tools/bench_extras.py) as the LAST line: a run that is killed inside an extra
+still leaves a complete headline on stdout.  Objects that --full adds to the line:
   roofline     dominant kernel (k_dp): algorithmic bytes (L + 13 per read) per launch
                / its mean duration measured with HIP events on the library's stream.
   cpu_baseline the real reference extension (oracle/_ref, kind "reference") called per read from
@@ -61,7 +65,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 # launch shapes, collectives, the step plan (tools/bench_launch.py) and the extras (tools/bench_extras.py: imported lazily --
 # nothing in it runs before the headline is on stdout)
 from bench_launch import (HBM_PEAK_GBS, FP64_VALU_PEAK, CONFIG2_READS, CONFIG4_SHARD, Collectives, StubEngine,  # noqa: E402,F401
-                          ClockSampler, pci_bus_id_of, plan_steps, self_launch, threads_main, visible_gpus, _decode_rank)
+                          ClockSampler, dump_outputs, pci_bus_id_of, plan_steps, self_launch, threads_main, visible_gpus,
+                          _decode_rank)
 
 
 def usable_cpus():
@@ -218,10 +223,17 @@ def main():
     ap.add_argument("--length", type=int, default=300)
     ap.add_argument("--seed", type=int, default=2)
     ap.add_argument("--fast-fma", action="store_true", help="non-bit-exact FMA mode (not the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else this script measures: the per-kernel event pass, roofline / FP64 "
+                         "figures, pass / fail totals, row-budget histogram, CPU baseline, live counter passes and extras "
+                         "(without it: set-up, warm-up, the timed steps and the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (ee, Ns, pass of a fixed, seeded sample of "
+                         "2^20 reads, and their read ids; rank 0's shard at N > 1) as DIR/<name>.npy in float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--stride", type=int, default=0, help="row stride in bytes (default: length rounded up to 64; experiments)")
-    ap.add_argument("--no-extras", action="store_true", help="the headline only: no extras, no live counter passes (profiling)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="keep the committed profiles/ counters (no rocprofv3 child passes)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: no extras, no live counter passes (profiling)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: keep the committed profiles/ counters (no rocprofv3 child passes)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank dry run on a 1-GPU box: every rank uses device 0 and the (tiny) "
                          "collectives go over gloo; exercises the N>1 code path, not a scaling number")
@@ -242,6 +254,8 @@ def main():
     ap.add_argument("--_stub-extras", type=float, default=0.0, help=argparse.SUPPRESS)      # tests (CPU rehearsal, N = 1): after the headline, "extras" that sleep this many seconds each
     args = ap.parse_args()
     rehearsal = args.rehearse_on_one_gpu or args.rehearse_on_cpu
+    if args.dump_outputs and args.rehearse_on_cpu:
+        raise SystemExit("--dump-outputs needs the GPU path: --rehearse-on-cpu computes nothing")
 
     if args.launch == "threads" and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return threads_main(args)
@@ -314,8 +328,8 @@ def main():
     device_sync()
     if rank == args._die_rank:
         os._exit(3)                                      # tests: a rank that dies must fail the whole job, promptly
-    # ---- the timed region: no events, no host round trips (a host thread reads the device's clock from sysfs meanwhile) ----
-    clock = ClockSampler(pci_bus_id_of(local_rank) if use_gpu else None).start()
+    # ---- the timed region: no events, no host round trips (with --full a host thread reads the device's clock from sysfs) ----
+    clock = ClockSampler(pci_bus_id_of(local_rank) if use_gpu else None).start() if args.full else None
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -324,10 +338,14 @@ def main():
     dt_rank = time.perf_counter() - t0                   # this rank's own time, before it waits for the others
     barrier()
     dt = coll.allmax(time.perf_counter() - t0)
-    held_clock = clock.stop()
+    held_clock = clock.stop() if clock else None
     per_rank = [n * steps / t for t in coll.gather_floats(dt_rank)]
-    counts = step(counts=True)
-    n_pass, n_fail, n_ovf = coll.sum_totals((counts.n_pass, counts.n_fail, counts.n_overflow))
+    if args.dump_outputs and rank == 0:                  # what the last timed step left in d_ee / d_ns / d_pass
+        dump_outputs(args.dump_outputs, d_ee, d_ns, d_pass, n)
+    # everything below that is not the headline (args are the same on every rank: the collectives stay paired) runs with --full
+    if args.full:
+        counts = step(counts=True)
+        n_pass, n_fail, n_ovf = coll.sum_totals((counts.n_pass, counts.n_fail, counts.n_overflow))
 
     if not use_gpu:
         if rank == 0:
@@ -340,9 +358,11 @@ def main():
                                "collective_backend": "gloo (rehearsal)" if not args._try_rccl else
                                "gloo (RCCL not used: %s)" % coll.rccl_error},
                     "t_step_rank_uniform_s": t_step, "timed_region_s": dt, "reads_per_s_per_rank": per_rank,
-                    "devices": devices, "outcome": {"pass": n_pass, "fail": n_fail, "overflow_reruns": n_ovf}}
+                    "devices": devices}
+            if args.full:
+                line["outcome"] = {"pass": n_pass, "fail": n_fail, "overflow_reruns": n_ovf}
             emit(line)
-            if args._stub_extras > 0 and world == 1:
+            if args.full and args._stub_extras > 0 and world == 1:
                 # tests: the order of a real N = 1 run -- the headline is out, the extras follow, the full line closes
                 line["extras"] = {}
                 for k in range(3):
@@ -353,43 +373,32 @@ def main():
         coll.close()
         return
 
-    # ---- per-kernel HIP events on the library's stream, in a pass of their own ----
-    ev_steps = min(steps, 20)
-    eng.timing(True)
-    eng.timing_reset()
-    for _ in range(ev_steps):
-        step()
-    eng.synchronize()
-    times = eng.kernel_times()
-    eng.timing(False)
-    # every rank's own kernel times and held clock, so that a throttled GPU shows in the line (fixed-width text, nothing pickled)
-    mine = {"k": {k: round(v[0] / max(v[1], 1), 4) for k, v in times.items() if v[1]},
-            "mhz": [round(held_clock[x]) for x in ("mean_mhz", "min_mhz", "max_mhz")] if held_clock else None}
-    per_rank_text = coll.gather_text(json.dumps(mine, separators=(",", ":")), width=480)
-    # row budgets and algorithmic cells: one untimed pass through the sorted pipeline (what the headline batch takes by itself;
-    # forced, because the histogram describes the sorted pipeline's classes) that also sums the algorithmic DP cells on the device
-    prm_cells = eng.params(alpha=0.005, uncert=0.01, ambigs="treat_as_errors", fast_fma=args.fast_fma, count_cells=True, no_narrow=True)
-    eng.filter_device(d_q, n, stride, fixed_len=L, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass, params=prm_cells, want_counts=False)
-    hist = eng.class_histogram()
-    alg_cells = eng.algorithmic_cells()
+    if args.full:
+        # ---- per-kernel HIP events on the library's stream, in a pass of their own ----
+        ev_steps = min(steps, 20)
+        eng.timing(True)
+        eng.timing_reset()
+        for _ in range(ev_steps):
+            step()
+        eng.synchronize()
+        times = eng.kernel_times()
+        eng.timing(False)
+        # every rank's own kernel times and held clock, so that a throttled GPU shows in the line (fixed-width text, nothing pickled)
+        mine = {"k": {k: round(v[0] / max(v[1], 1), 4) for k, v in times.items() if v[1]},
+                "mhz": [round(held_clock[x]) for x in ("mean_mhz", "min_mhz", "max_mhz")] if held_clock else None}
+        per_rank_text = coll.gather_text(json.dumps(mine, separators=(",", ":")), width=480)
+        # row budgets and algorithmic cells: one untimed pass through the sorted pipeline (what the headline batch takes by itself;
+        # forced, because the histogram describes the sorted pipeline's classes) that also sums the algorithmic DP cells on the device
+        prm_cells = eng.params(alpha=0.005, uncert=0.01, ambigs="treat_as_errors", fast_fma=args.fast_fma, count_cells=True, no_narrow=True)
+        eng.filter_device(d_q, n, stride, fixed_len=L, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass, params=prm_cells, want_counts=False)
+        hist = eng.class_histogram()
+        alg_cells = eng.algorithmic_cells()
 
     line = None
     if rank == 0:
         total_reads = n * world * steps
         value = total_reads / dt
-        dp_ms, dp_n = times["dp"]
-        dp_avg_s = dp_ms / max(dp_n, 1) / 1e3
-        alg_bytes = (L + 13) * n
-        achieved = alg_bytes / dp_avg_s / 1e9 if dp_n else None
-        cells = sum(cap * cnt for cap, cnt in hist.items()) * L        # DP cells one launch evaluates
-        opc = 2 if args.fast_fma else 3
-        # FP64 lane-operations actually issued: row 0 of a one-lane-per-read class (budget <= 16) is a single
-        # multiply (there is no row -1), every other cell costs `opc`
-        issued = sum((opc * cap - (opc - 1 if cap <= 16 else 0)) * cnt for cap, cnt in hist.items()) * L
-        traffic, valu_pmc, pmc_source = (None, None, None) if args.fast_fma else committed_traffic(n, L, args.seed)
         step_s = dt / steps
-        fp64_floor_ms = cells * opc / FP64_VALU_PEAK * 1e3
-        hbm40_ms = alg_bytes / (0.40 * HBM_PEAK_GBS * 1e9) * 1e3
         if world == 1:
             wl = ("BASELINE configs[1]: %d synthetic single-end %d bp reads, poisson_binomial filter, alpha 0.005, "
                   "uncert 0.01, resident in HBM (uint8 %d x %d, seed %d)" % (n, L, n, stride, args.seed))
@@ -427,6 +436,21 @@ def main():
             "t_step_rank_uniform_s": t_step,
             "reads_per_s_per_rank": per_rank,
             "launch": "processes" if world > 1 else "single process",
+        }
+    if rank == 0 and args.full:
+        dp_ms, dp_n = times["dp"]
+        dp_avg_s = dp_ms / max(dp_n, 1) / 1e3
+        alg_bytes = (L + 13) * n
+        achieved = alg_bytes / dp_avg_s / 1e9 if dp_n else None
+        cells = sum(cap * cnt for cap, cnt in hist.items()) * L        # DP cells one launch evaluates
+        opc = 2 if args.fast_fma else 3
+        # FP64 lane-operations actually issued: row 0 of a one-lane-per-read class (budget <= 16) is a single
+        # multiply (there is no row -1), every other cell costs `opc`
+        issued = sum((opc * cap - (opc - 1 if cap <= 16 else 0)) * cnt for cap, cnt in hist.items()) * L
+        traffic, valu_pmc, pmc_source = (None, None, None) if args.fast_fma else committed_traffic(n, L, args.seed)
+        fp64_floor_ms = cells * opc / FP64_VALU_PEAK * 1e3
+        hbm40_ms = alg_bytes / (0.40 * HBM_PEAK_GBS * 1e9) * 1e3
+        line.update({
             "per_rank": [_decode_rank(t) for t in per_rank_text],
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
@@ -465,14 +489,15 @@ def main():
             "kernel_event_pass": {"steps": ev_steps, "note": "HIP events on the library's stream, separate from the wall-clock region"},
             "outcome": {"pass": n_pass, "fail": n_fail, "overflow_reruns": n_ovf},
             "row_budget_histogram": {str(k): v for k, v in hist.items() if v},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             line.update(cpu_baseline(args.seed, L, stride))
+    if rank == 0:
         # ---- the headline is complete: out it goes, before anything optional runs ----
         emit(line)
-        # N = 1 only: with more ranks the others would sit in the closing barrier (120 s timeout) while rank 0 runs the extras,
-        # and they describe the single-GPU library, not the multi-GPU run
-        if world == 1 and not args.no_extras:
+        # --full, N = 1 only: with more ranks the others would sit in the closing barrier (120 s timeout) while rank 0 runs the
+        # extras, and they describe the single-GPU library, not the multi-GPU run
+        if args.full and world == 1 and not args.no_extras:
             import bench_extras as X
             if not args.no_live_pmc and not args.fast_fma:
                 sys.stderr.write("bench.py: live counter passes (rocprofv3 --pmc in fresh child processes) ...\n")

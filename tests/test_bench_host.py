@@ -113,7 +113,8 @@ def test_eight_rank_rehearsal_on_cpu_with_unequal_ranks():
     torchrun as a child, picks a port, every rank goes through the same collectives (gloo) although rank r's stub
     step is (1 + 4 r) ms long -- i.e. the ranks measure very different local step times -- and rank 0 prints one line
     with one rate and one device string per rank."""
-    p, _ = _run_bench(["--gpus", "8", "--rehearse-on-cpu", "--steps", "6", "--warmup", "1", "--reads", "1000", "--_rank-delay-ms", "4"])
+    p, _ = _run_bench(["--gpus", "8", "--rehearse-on-cpu", "--steps", "6", "--warmup", "1", "--reads", "1000", "--_rank-delay-ms", "4",
+                       "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 8 and line["steps"] == 6 and line["config"]["world_size"] == 8
@@ -140,7 +141,7 @@ def test_rccl_failure_falls_back_to_gloo_in_the_same_process():
     """if the RCCL communicator does not come up the ranks must carry the 24-byte totals over gloo IN THE
     SAME PROCESS and still print the line.  Without a GPU the attempt fails on every rank (no device to put the
     communicator on): three ranks, the vote, the fallback, the totals, the exit without tearing down a half-made group."""
-    p, took = _run_bench(["--gpus", "3", "--rehearse-on-cpu", "--steps", "3", "--warmup", "1", "--reads", "1000", "--_try-rccl"])
+    p, took = _run_bench(["--gpus", "3", "--rehearse-on-cpu", "--steps", "3", "--warmup", "1", "--reads", "1000", "--_try-rccl", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["outcome"]["pass"] + line["outcome"]["fail"] == 3000
@@ -206,7 +207,7 @@ def test_the_headline_is_out_before_the_extras_and_survives_a_kill():
     import signal
     env = dict(os.environ, PYTHONUNBUFFERED="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rehearse-on-cpu", "--steps", "3", "--warmup", "1",
-           "--reads", "1000", "--_stub-extras"]
+           "--reads", "1000", "--full", "--_stub-extras"]
     p = subprocess.Popen(cmd + ["60"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=ROOT)
     try:
         first = p.stdout.readline()                       # blocks until the headline is flushed; the "extras" then sleep 3 x 60 s
@@ -314,3 +315,52 @@ def test_a_failing_counter_pass_is_an_error_entry_not_an_exception(monkeypatch, 
     monkeypatch.setenv("PATH", str(slow) + os.pathsep + os.environ.get("PATH", ""))
     r = X.pmc_live(1000, 300, 1, 320, deadline_s=6.0)
     assert set(r) == {"error"} and "deadline" in r["error"]
+
+
+def test_a_plain_run_prints_the_headline_only():
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: exactly N timed steps and one line with the headline's fields --
+    no totals pass, no extras (CPU rehearsal: the step is a stub)."""
+    p, _ = _run_bench(["--gpus", "1", "--rehearse-on-cpu", "--steps", "7", "--warmup", "2", "--reads", "1000"])
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 7 and line["warmup"] == 2
+    assert line["metric"].startswith("reads/sec") and line["unit"] == "reads/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["ms_per_step"] > 0
+    assert abs(line["ms_per_step"] - line["timed_region_s"] / 7 * 1e3) < 1e-9
+    assert "outcome" not in line and "extras" not in line and "roofline" not in line
+    q, _ = _run_bench(["--gpus", "1", "--rehearse-on-cpu", "--steps", "2", "--warmup", "1", "--reads", "1000", "--dump-outputs", "x"])
+    assert q.returncode != 0 and "--dump-outputs needs the GPU path" in q.stderr
+
+
+def test_dump_outputs_writes_a_fixed_sample_in_float64(tmp_path):
+    """--dump-outputs: ee / Ns / pass of the same seeded sample of reads on every run, float64, under 64 MB at the headline's
+    10 M reads; all reads when there are fewer than the sample size."""
+    bench = load_bench()
+
+    class Buf:
+        def __init__(self, a):
+            self.a = a
+
+        def download(self, dtype, count, offset=0):
+            assert offset == 0 and self.a.dtype == np.dtype(dtype) and count == len(self.a)
+            return self.a.copy()
+
+    n = bench.CONFIG2_READS
+    rng = np.random.default_rng(1)
+    ee = rng.random(n) * 5
+    ns = rng.integers(0, 9, n).astype(np.int32)
+    ps = (ee < 2.5).astype(np.uint8)
+    got = bench.dump_outputs(str(tmp_path / "a"), Buf(ee), Buf(ns), Buf(ps), n)
+    assert got == {k: [1 << 20] for k in ("read_id", "ee", "ns", "passed")}
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in got}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(os.path.getsize(str(tmp_path / "a" / (k + ".npy"))) for k in got) < 64e6
+    idx = a["read_id"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(a["ee"], ee[idx]) and np.array_equal(a["ns"], ns[idx]) and np.array_equal(a["passed"], ps[idx])
+    bench.dump_outputs(str(tmp_path / "b"), Buf(ee), Buf(ns), Buf(ps), n)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "read_id.npy")), a["read_id"])      # the same reads on every run
+    small = bench.dump_outputs(str(tmp_path / "c"), Buf(ee[:1000]), Buf(ns[:1000]), Buf(ps[:1000]), 1000)
+    assert small["ee"] == [1000] and np.array_equal(np.load(str(tmp_path / "c" / "ee.npy")), ee[:1000])

@@ -67,6 +67,28 @@ def _random_pair(rng):
     return f, [int(x) for x in rng.integers(2, 41, len(f))], rrc, [int(x) for x in rng.integers(2, 41, len(rrc))]
 
 
+CONTIG_MODES = (("best", 40, False), ("sum", 0, False), ("posterior", 40, False), ("best", 40, True))
+
+
+def test_against_recorded_python_reference():
+    """tests/golden/contig_random_pairs.json (tests/golden/make_contig_pairs.py): the reference's own reverse_complement and
+    make_contig on the seeded random pairs below, recorded -- the comparison of the next test without the reference checkout."""
+    import json
+    import os
+    rec = json.load(open(os.path.join(G.GOLDEN, "contig_random_pairs.json")))
+    assert [tuple(m) for m in rec["modes"]] == list(CONTIG_MODES) and len(rec["pairs"]) == 60
+    rng = np.random.default_rng(11)
+    for it, p in enumerate(rec["pairs"]):
+        f, fq, r, rq = _random_pair(rng)
+        assert (f, fq, r, rq) == (p["f"], p["fq"], p["r"], p["rq"]), it
+        rrc, rrq = CT.reverse_complement(r, rq)
+        assert [rrc, list(rrq)] == p["rc"], it
+        a1, a2, sc = CT.nw_align(f, rrc, 1, -1, -2)
+        for (mode, cap, trim), want in zip(CONTIG_MODES, p["contigs"]):
+            got = CT.make_contig(a1, fq, a2, rrq, 20, 6, mode, cap, trim)
+            assert list(got) == want, (it, mode)
+
+
 def test_against_python_reference_when_available(tmp_path):
     import os
     import shutil

@@ -96,7 +96,7 @@ def test_bench_starts_its_own_ranks_from_the_plain_command():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu",
-                        "--reads", "300000", "--steps", "3", "--warmup", "1", "--no-extras"],
+                        "--reads", "300000", "--steps", "3", "--warmup", "1", "--full", "--no-extras"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -140,7 +140,7 @@ def test_bench_rccl_failure_falls_back_to_gloo_on_hardware():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--_try-rccl",
-                        "--reads", "300000", "--steps", "3", "--warmup", "1", "--no-extras"],
+                        "--reads", "300000", "--steps", "3", "--warmup", "1", "--full", "--no-extras"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -160,7 +160,7 @@ def test_bench_four_rank_rehearsal_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--rehearse-on-one-gpu",
-                        "--reads", "2000000", "--steps", "4", "--warmup", "1", "--no-extras"],
+                        "--reads", "2000000", "--steps", "4", "--warmup", "1", "--full", "--no-extras"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -182,7 +182,7 @@ def test_bench_threads_mode_four_contexts_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--launch", "threads", "--rehearse-on-one-gpu",
-                        "--reads", "2000000", "--steps", "6", "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--reads", "2000000", "--steps", "6", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["launch"] == "threads" and line["n_gpus"] == 4 and line["steps"] == 6 and line["scaling"] == "weak"
@@ -197,7 +197,7 @@ def test_bench_threads_mode_four_contexts_on_one_gpu():
     assert line["value"] > 0 and line["roofline"]["frac"] > 0 and line["fell_back_from"] is None
     # the four shards are the four read-id ranges of the process-per-GPU run: same totals
     q = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--launch", "processes", "--rehearse-on-one-gpu",
-                        "--reads", "2000000", "--steps", "2", "--warmup", "1", "--no-extras"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--reads", "2000000", "--steps", "2", "--warmup", "1", "--full", "--no-extras"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert q.returncode == 0, q.stderr[-2000:]
     line2 = json.loads([l for l in q.stdout.splitlines() if l.startswith("{")][-1])
     assert line2["outcome"] == line["outcome"] and line2["launch"] == "processes"
@@ -215,7 +215,7 @@ def test_bench_falls_back_to_threads_when_the_process_launch_fails():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["BENCH_FAKE_LAUNCHER_FAILURE"] = "1"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--reads", "300000",
-                        "--steps", "3", "--warmup", "1", "--no-extras"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--steps", "3", "--warmup", "1", "--full", "--no-extras"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["launch"] == "threads" and "exit code 7" in line["fell_back_from"] and line["n_gpus"] == 2

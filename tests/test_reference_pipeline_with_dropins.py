@@ -13,7 +13,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/moira"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout exists in the build container only")
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (its moira.py and test reads)")
 
 
 @pytest.fixture(scope="module")
@@ -34,6 +34,7 @@ def reference_with_dropin_aligner(oracle):
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+@needs_reference
 @pytest.mark.parametrize("case", ["pe_shipped_default", "pe_scores_2_-3_-1", "pe_sum_cap0_fastq", "pe_trim_overlap"])
 def test_reference_pipeline_on_the_dropin_aligner_writes_the_references_files(case, reference_with_dropin_aligner):
     import golden_io as G
@@ -61,6 +62,7 @@ def _serve_stub(path, name):
     os._exit(abs(lib.mpb_broker_serve(C.c_void_p(1), name.encode(), 8, 0)))
 
 
+@needs_reference
 @pytest.mark.parametrize("case", ["se_shipped_default", "se_relabel_usearch_truncate", "se_alpha05_uncert02"])
 def test_reference_pipeline_on_the_dropin_bernoulli_module(case, reference_with_dropin_aligner, oracle, tmp_path_factory, monkeypatch):
     """The other half of the boundary, as far as it goes without a GPU: moira.py's own process_data calling

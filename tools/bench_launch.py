@@ -326,7 +326,8 @@ def threads_main(args):
     """--launch threads: the N > 1 measurement without a launcher and without any collective.  ONE process,
     N contexts (one per GPU) on N host threads: each thread owns its device-resident shard (read ids r*R .., generated on its
     own device), runs the same warm-up / settle / timed steps behind a thread barrier on both sides, and the line carries the
-    max over the threads, every thread's own rate, per-device kernel times (HIP events) and the clock each device held.
+    max over the threads, every thread's own rate and, with --full, per-device kernel times (HIP events), the clock each device
+    held and the pass / fail totals.
     ctypes releases the GIL in every library call, and a step is asynchronous, so the threads never wait for each other
     outside the two barriers.  Replaces moira/moira.py:398-399 (`Pool(args.processors)`) the way SURVEY 8e puts it."""
     import threading
@@ -371,7 +372,7 @@ def threads_main(args):
             for _ in range(settle):
                 step()
             eng.synchronize()
-            clock = ClockSampler(bus).start()
+            clock = ClockSampler(bus).start() if args.full else None
             bar.wait()                                       # ---- the timed region ----
             t0 = time.perf_counter()
             for _ in range(steps):
@@ -380,18 +381,23 @@ def threads_main(args):
             dts[r] = time.perf_counter() - t0
             bar.wait()
             t_all = time.perf_counter() - t0                 # after the barrier: the slowest thread's end, as every thread saw it
-            held = clock.stop()
-            counts = step(True)
-            ev = min(steps, 10)
-            eng.timing(True); eng.timing_reset()
-            for _ in range(ev):
-                step()
-            eng.synchronize()
-            kt = {k: v[0] / max(v[1], 1) for k, v in eng.kernel_times().items() if v[1]}
-            eng.timing(False)
-            res[r] = {"device": dev, "pci_bus_id": bus, "t_all": t_all, "kernels_ms_per_step": kt, "held_clock": held,
-                      "pass": counts.n_pass, "fail": counts.n_fail, "overflow": counts.n_overflow,
-                      "path": eng.last_path()["narrow_rows"]}
+            res_r = {"device": dev, "pci_bus_id": bus, "t_all": t_all}
+            if r == 0 and args.dump_outputs:                 # thread 0's shard, as the last timed step left it
+                dump_outputs(args.dump_outputs, d_ee, d_ns, d_pass, n)
+            if args.full:                                    # per-device kernel times, held clock and totals: --full only
+                held = clock.stop()
+                counts = step(True)
+                ev = min(steps, 10)
+                eng.timing(True); eng.timing_reset()
+                for _ in range(ev):
+                    step()
+                eng.synchronize()
+                kt = {k: v[0] / max(v[1], 1) for k, v in eng.kernel_times().items() if v[1]}
+                eng.timing(False)
+                res_r.update({"kernels_ms_per_step": kt, "held_clock": held,
+                              "pass": counts.n_pass, "fail": counts.n_fail, "overflow": counts.n_overflow,
+                              "path": eng.last_path()["narrow_rows"]})
+            res[r] = res_r
             for b in (d_q, d_ee, d_ns, d_pass):
                 b.free()
         except BaseException as e:                           # noqa: BLE001 -- whatever it is, nobody waits for this thread
@@ -421,7 +427,6 @@ def threads_main(args):
           "per GPU, seed %d)" % (n * world, L, world, n, n * stride / 1e9, n, stride, args.seed))
     if args.rehearse_on_one_gpu:
         wl = "REHEARSAL: %d contexts share GPU 0 -- exercises the threads launch, not a scaling number; " % world + wl
-    dp = [x["kernels_ms_per_step"].get("dp") for x in res]
     line = {"metric": "reads/sec filtered (300 bp synthetic)", "value": n * world * steps / dt, "unit": "reads/s",
             "n_gpus": world, "steps": steps, "warmup": args.warmup, "settle_steps": settle, "ms_per_step": dt / steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -435,7 +440,10 @@ def threads_main(args):
                                    "(= extras.config4_shard of the plain N = 1 line)" % (n, n),
             "devices": ["thread %d: GPU %d pci %s" % (r, x["device"], x["pci_bus_id"]) for r, x in enumerate(res)],
             "timed_region_s": dt, "t_step_rank_uniform_s": plan["t_step"],
-            "reads_per_s_per_rank": [n * steps / t for t in dts],
+            "reads_per_s_per_rank": [n * steps / t for t in dts]}
+    if args.full:
+        dp = [x["kernels_ms_per_step"].get("dp") for x in res]
+        line.update({
             "per_rank": [{"kernels_ms_per_step": x["kernels_ms_per_step"], "held_clock": x["held_clock"]} for x in res],
             "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "kernel": "k_dp",
                          "algorithmic_bytes_per_launch": (L + 13) * n,
@@ -444,10 +452,39 @@ def threads_main(args):
                          "frac": ((L + 13) * n / (sum(dp) / len(dp)) / 1e6 / HBM_PEAK_GBS) if all(dp) else None,
                          "frac_whole_step": (L + 13) * n * world / (dt / steps) / 1e9 / HBM_PEAK_GBS / world, "traffic": None},
             "outcome": {"pass": sum(x["pass"] for x in res), "fail": sum(x["fail"] for x in res),
-                        "overflow_reruns": sum(x["overflow"] for x in res)}}
+                        "overflow_reruns": sum(x["overflow"] for x in res)}})
     print(json.dumps(line))
     sys.stdout.flush()
     return 0
+
+
+DUMP_SAMPLE = 1 << 20          # reads written by --dump-outputs: 4 float64 arrays of 2^20 = 32 MiB (cap: 64 MB)
+DUMP_SEED = 20240501
+
+
+def dump_sample_index(n):
+    """The reads --dump-outputs writes: all of them when n <= DUMP_SAMPLE, else a fixed, seeded, sorted sample of DUMP_SAMPLE
+    read ids (the same for every run with the same --reads)."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(out_dir, d_ee, d_ns, d_pass, n):
+    """--dump-outputs DIR: what the timed step hands its caller -- ee (float64), Ns (int32) and the pass flags (uint8) of every
+    read -- for the sampled read ids, written as DIR/<name>.npy in float64 (exact for all three).  `read_id.npy` says which
+    reads they are.  Returns {name: shape}."""
+    import numpy as np
+    idx = dump_sample_index(n)
+    arrays = {"read_id": idx.astype(np.float64),
+              "ee": d_ee.download(np.float64, n)[idx],
+              "ns": d_ns.download(np.int32, n)[idx].astype(np.float64),
+              "passed": d_pass.download(np.uint8, n)[idx].astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def plan_steps(t_step_max, steps_arg, warmup):

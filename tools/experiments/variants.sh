@@ -24,7 +24,7 @@ done; fi
 for i in $(seq $N); do for v in "${names[@]}"; do
   export MOIRA_PB_LIB=/tmp/var/$v.so
   if [ -n "$VARIANT_CMD" ]; then echo "$v: $($VARIANT_CMD 2>&1 | tail -${VARIANT_TAIL:-1})"; else
-  python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-extras $BENCH_ARGS 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$v', round(d['ms_per_step'],3), {k: round(v,3) for k,v in d['kernels_ms_per_step'].items() if v})"; fi
+  python bench.py --steps 30 --warmup 3 --full --no-cpu-baseline --no-extras $BENCH_ARGS 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$v', round(d['ms_per_step'],3), {k: round(v,3) for k,v in d['kernels_ms_per_step'].items() if v})"; fi
 done; done
 if [ -n "$PMC" ]; then for v in "${names[@]}"; do
   export MOIRA_PB_LIB=/tmp/var/$v.so
