@@ -1702,11 +1702,18 @@ static int serve_one(mpb_ctx *c, const uint8_t *row, int32_t len, double alpha, 
     return MPB_OK;
 }
 
+// the parameters of a per-read call (bernoulli's calculate_errors_PB / calculate_errors_poisson): alpha, the rest moira's defaults
+static mpb_filter_params per_read_params(double alpha)
+{
+    mpb_filter_params p;
+    p.alpha = alpha; p.uncert = 1.0; p.maxerrors = NAN; p.ambig_mode = MPB_AMBIG_IGNORE; p.flags = 0;
+    return p;
+}
+
 int mpbi_run_packed_read(mpb_ctx *c, const uint8_t *row, int32_t len, int32_t stride, const double2 *h, double alpha,
                          double *ee, int32_t *ns)
 {
-    mpb_filter_params prm;
-    prm.alpha = alpha; prm.uncert = 1.0; prm.maxerrors = NAN; prm.ambig_mode = MPB_AMBIG_IGNORE; prm.flags = 0;
+    const mpb_filter_params prm = per_read_params(alpha);
     uint8_t pass = 0;
     PrivateTable guard(c);
     int rc;
@@ -1740,8 +1747,7 @@ int mpbi_small_async(mpb_ctx *c, const uint8_t *d_q, int64_t m, int64_t stride, 
                      double *d_ee, int32_t *d_ns, uint8_t *d_pass, uint8_t *d_cls, int32_t *d_ident, hipStream_t s,
                      const MpbSmallHost *host)
 {
-    mpb_filter_params prm;
-    prm.alpha = alpha; prm.uncert = 1.0; prm.maxerrors = NAN; prm.ambig_mode = MPB_AMBIG_IGNORE; prm.flags = 0;
+    const mpb_filter_params prm = per_read_params(alpha);
     const int32_t max_len = (int32_t)(stride < MPB_MAX_LEN ? stride : MPB_MAX_LEN);
     const MpbDevParams dp = make_dev_params(&prm, 0, max_len);
     int rc = ensure_workspace(c, m);               // (the broker sizes it once, before anything is in flight)
@@ -1757,8 +1763,7 @@ int mpbi_small_async(mpb_ctx *c, const uint8_t *d_q, int64_t m, int64_t stride, 
 
 void mpbi_small_params(double alpha, MpbDevParams *out)
 {
-    mpb_filter_params prm;
-    prm.alpha = alpha; prm.uncert = 1.0; prm.maxerrors = NAN; prm.ambig_mode = MPB_AMBIG_IGNORE; prm.flags = 0;
+    const mpb_filter_params prm = per_read_params(alpha);
     *out = make_dev_params(&prm, 0, MPB_SERVE_STRIDE);
 }
 
@@ -1885,17 +1890,10 @@ int mpb_poisson_finish_host(const double *lambda, const int32_t *ns, const int32
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!lambda || !ns || !ee || !pass))) return fail(MPB_E_INVALID, "bad arguments");
     const double *fact = factorial_table();
-    const bool has_me = p->maxerrors == p->maxerrors;
     auto run = [=](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; i++) {
-            double e = poisson_tail(lambda[i], p->alpha, fact);
-            if (p->ambig_mode == MPB_AMBIG_TREAT_AS_ERRORS) e = e + ns[i];          // moira.py:827-828
-            if (p->flags & MPB_FLAG_ROUND) e = floor(e);                              // moira.py:830-831
-            const int li = len ? len[i] : fixed_len;
-            bool keep;
-            if (p->ambig_mode == MPB_AMBIG_DISALLOW && ns[i] > 0) keep = false;       // moira.py:911
-            else if (has_me) keep = e <= p->maxerrors;
-            else keep = e <= li * p->uncert;
+            double e = mpb_add_ns(*p, poisson_tail(lambda[i], p->alpha, fact), ns[i]);
+            const bool keep = mpb_round_and_keep(*p, e, ns[i] > 0, len ? len[i] : fixed_len);    // (ns counts 'N' only here)
             ee[i] = e;
             pass[i] = keep ? 1 : 0;
         }
@@ -1959,8 +1957,7 @@ int mpb_calculate_errors_poisson(mpb_ctx *c, const char *sequence, const int32_t
     if (sequence && (int32_t)strlen(sequence) != len) return fail(MPB_E_INVALID, "sequence and quals must have the same length");
     const int32_t stride = (int32_t)align_up(len > 0 ? len : 1, 16);
     std::vector<uint8_t> row((size_t)stride);
-    mpb_filter_params prm;
-    prm.alpha = alpha; prm.uncert = 1.0; prm.maxerrors = NAN; prm.ambig_mode = MPB_AMBIG_IGNORE; prm.flags = 0;
+    const mpb_filter_params prm = per_read_params(alpha);
     uint8_t pass = 0;
     bool priv = false;
     double2 h[256];

@@ -4,7 +4,37 @@
 #define MPB_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include "../../include/moira_pb.h"     // MPB_FLAG_*, MPB_AMBIG_*
+
+// ---- the reference's verdict on one read (moira.py:827-831, 911, 925-926, 949-950) -------------------------------------------
+// Shared by every kernel that finishes a read and by the host Poisson tail.  P is MpbDevParams or mpb_filter_params (the fields
+// maxerrors, uncert, ambig_mode, flags).  Between mpb_add_ns and mpb_round_and_keep a caller may look at the ee (MPB_FLAG_FAST_FMA's
+// "unsure" test); the helpers write no memory.
+// the read's limit: --maxerrors if set, else len x --uncert (moira.py:925-926, 949-950)
+template <typename P>
+__host__ __device__ __forceinline__ double mpb_limit(const P &p, int li)
+{
+    return (p.maxerrors == p.maxerrors) ? p.maxerrors : (double)li * p.uncert;
+}
+// --ambigs treat_as_errors: the ambiguous bases (N and n) count as errors (moira.py:827-828)
+template <typename P>
+__host__ __device__ __forceinline__ double mpb_add_ns(const P &p, double e, int nsv)
+{
+    return p.ambig_mode == MPB_AMBIG_TREAT_AS_ERRORS ? e + (double)nsv : e;
+}
+// Rounds e IN PLACE -- --round floors the reported ee (moira.py:830-831) -- and returns whether the read is kept: e <= its limit,
+// unless --ambigs disallow finds an upper-case 'N' in it (moira.py:911: 'n' does not count there, so has_n is the caller's,
+// apart from the ambiguity count).  (The limit is computed here, after the disallow test: taking it precomputed as an argument
+// costs k_serve four spilled registers.)
+template <typename P>
+__host__ __device__ __forceinline__ bool mpb_round_and_keep(const P &p, double &e, bool has_n, int li)
+{
+    if (p.flags & MPB_FLAG_ROUND) e = floor(e);
+    if (p.ambig_mode == MPB_AMBIG_DISALLOW && has_n) return false;
+    return e <= mpb_limit(p, li);
+}
 
 // ---- DP row-budget classes -------------------------------------------------------------
 // A read predicted to need J rows of the DP table goes to the smallest class with

@@ -97,6 +97,16 @@ __device__ __forceinline__ void wave_lds_fence()
 // a length read from a caller-supplied device array never takes a kernel outside its row
 __device__ __forceinline__ int clamp_len(int li, int max_len) { return min(max(li, 0), max_len); }
 
+// MPB_FLAG_DECISION_ONLY: Chernoff: P(X <= (1-d)mu) <= exp(-d^2 mu / 2) <= 1-alpha for d = clow/sqrt(mu), so the first CDF row
+// above 1-alpha is > t = mu - clow*sqrt(mu) and ee >= floor(t).  mu is an fp32 sum of approximated p: shave 1e-4 relative and
+// 0.02 absolute before trusting it.  True: the read is certainly rejected without a DP.
+__device__ __forceinline__ bool settled_by_chernoff(const MpbDevParams &prm, float mu, int li)
+{
+    if (!(prm.flags & MPB_FLAG_DECISION_ONLY)) return false;
+    const float t = mu * (1.0f - 1e-4f) - prm.clow * sqrtf(mu) - 0.02f;
+    return mu > 1.0f && (double)floorf(t) > mpb_limit(prm, li);
+}
+
 // ------------------------------------------------------------------------------------------
 // k_prepass
 // ------------------------------------------------------------------------------------------
@@ -243,21 +253,13 @@ __device__ __forceinline__ void class_read(int64_t i, float mu, float var, float
     const float v = fmaxf(var, 1e-12f);
     const float x = mu + prm.z * sqrtf(v) + (k3 / v) * prm.zq;
     int rows = (int)floorf(fminf(x, 1e9f) + 0.5f) + 1;
-    if (prm.flags & 4u) rows = rows / 2;                          // MPB_FLAG_TEST_UNDERPREDICT
+    if (prm.flags & MPB_FLAG_TEST_UNDERPREDICT) rows = rows / 2;
     const int scored = li - nzero - n255;
     rows = min(rows, scored + 1);
     rows = max(rows, 1);
     o.ns[i] = bad ? 0 : nzero + n255;
     const int c = c_class_of_rows.t[min(rows, MPB_TILE_MAX_ROWS)];
-    bool settled = false;
-    if (!bad && (prm.flags & 8u)) {                               // MPB_FLAG_DECISION_ONLY
-        // Chernoff: P(X <= (1-d)mu) <= exp(-d^2 mu / 2) <= 1-alpha for d = clow/sqrt(mu), so the
-        // first CDF row above 1-alpha is > t = mu - clow*sqrt(mu) and ee >= floor(t).  mu is an
-        // fp32 sum of approximated p: shave 1e-4 relative and 0.02 absolute before trusting it.
-        const float t = mu * (1.0f - 1e-4f) - prm.clow * sqrtf(mu) - 0.02f;
-        const double limit = (prm.maxerrors == prm.maxerrors) ? prm.maxerrors : (double)li * prm.uncert;
-        settled = mu > 1.0f && (double)floorf(t) > limit;
-    }
+    const bool settled = !bad && settled_by_chernoff(prm, mu, li);
     if (bad) {
         // a length outside 0..max_len is never clamped silently: the read gets no result (NaN, rejected) --
         // also for a caller that never fetches the counts -- and the call that does fetch them fails
@@ -777,6 +779,45 @@ __device__ __forceinline__ void dp_chunk(double (&v)[R], const uint4 x, int keep
     }
 }
 
+// ---- the end of a read: sequential CDF (ref: bernoullimodule.c:233-251), interpolation, verdict -------------------------------
+// Every kernel that finishes a read does it with these (the stores, and what a read that did not cross becomes, are the caller's).
+// The first of rows j0 .. j0+R-1 (the lane's registers v) whose CDF -- the running sum `acc` of the rows before them, then one
+// addition per row, in order -- exceeds thr: its number (-1: none of these), and the CDF before it (lo) and at it (hi).
+template <int R>
+__device__ __forceinline__ int cdf_cross(const double (&v)[R], double acc, double thr, int j0, double &lo, double &hi)
+{
+    int js = -1;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const double na = acc + v[r];              // acc == 0, r == 0: 0 + v0 is exact
+        const bool hit = (js < 0) && (na > thr);
+        lo = hit ? acc : lo;
+        hi = hit ? na : hi;
+        js = hit ? j0 + r : js;
+        acc = na;
+    }
+    return js;
+}
+
+// The crossing -> ee: the interpolation of ref: bernoullimodule.c:170-178, errors1 + ((errors2-errors1)*((1-alpha)-prob1)/
+// (prob2-prob1)), clamped at 0; NaN when the CDF never crossed (!crossed: the reference runs off its table).  `crossed` is the
+// caller's (where it is a constant, the NaN costs nothing).
+__device__ __forceinline__ double cross_ee(bool crossed, int js, double thr, double lo, double hi)
+{
+    if (!crossed) return __builtin_nan("");
+    double e = (double)(js - 1) + ((thr - lo) / (hi - lo));
+    if (e < 0) e = 0;
+    return e;
+}
+
+// The crossing -> the reported ee (e) and the verdict (mpb_add_ns, mpb_round_and_keep: nsv ambiguous bases, has_n = an upper-case 'N')
+__device__ __forceinline__ bool read_result(const MpbDevParams &prm, bool crossed, int js, double lo, double hi, int nsv, bool has_n,
+                                            int li, double &e)
+{
+    e = mpb_add_ns(prm, cross_ee(crossed, js, prm.thr, lo, hi), nsv);
+    return mpb_round_and_keep(prm, e, has_n, li);
+}
+
 // Register budget of the DP kernel: 4 waves per SIMD = at most 128 VGPRs per lane.
 #define MPB_DP_WAVES_PER_EU 4
 
@@ -796,6 +837,12 @@ struct DpArgs {
     MpbDevParams prm;
     int final_pass;
 };
+
+// --ambigs disallow's "has an upper-case N" bit of read idx (its class byte), read only when that mode asks for it
+__device__ __forceinline__ bool class_has_n(const DpArgs &A, int idx)
+{
+    return A.prm.ambig_mode == MPB_AMBIG_DISALLOW && (gload(A.cls + idx) & 0x80);
+}
 
 // A run of consecutive tiles of one class.  Deliberately NOT inlined: each (R,G) body gets its own
 // register allocation, so the kernel's VGPR budget is the widest body's, not the sum of all of them.
@@ -901,23 +948,14 @@ __device__ __noinline__ void dp_tiles(const DpArgs *__restrict__ Ap, const int32
         }
     }
 
-    // ---- epilogue: sequential CDF (ref: bernoullimodule.c:233-251), first row above thr ----
+    // ---- epilogue: sequential CDF, first row above thr ----
     const double thr = A.prm.thr;
     double lo = 0.0, hi = 0.0;
     int js = -1;
     bool writer;                                   // the lane that reports this read
     bool never_crossed = false;
     if (G == 1) {
-        double acc = 0.0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const double na = acc + v[r];          // r == 0: 0 + v0 is exact
-            const bool hit = (js < 0) && (na > thr);
-            lo = hit ? acc : lo;
-            hi = hit ? na : hi;
-            js = hit ? r : js;
-            acc = na;
-        }
+        js = cdf_cross(v, 0.0, thr, 0, lo, hi);
         writer = valid;
         never_crossed = js < 0;
     } else {
@@ -948,18 +986,7 @@ __device__ __noinline__ void dp_tiles(const DpArgs *__restrict__ Ap, const int32
             }
         }
         // Phase B: only the crossing lane walks its rows again to pick out the two CDF values.
-        if (mine) {
-            double a = acc_in_mine;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const double na = a + v[r];
-                const bool hit = (js < 0) && (na > thr);
-                lo = hit ? a : lo;
-                hi = hit ? na : hi;
-                js = hit ? (lig * R + r) : js;
-                a = na;
-            }
-        }
+        if (mine) js = cdf_cross(v, acc_in_mine, thr, lig * R, lo, hi);
         never_crossed = (lig == G - 1) && !found;  // the last lane has seen the whole CDF
         writer = valid && (mine || never_crossed);
     }
@@ -970,42 +997,30 @@ __device__ __noinline__ void dp_tiles(const DpArgs *__restrict__ Ap, const int32
         } else if (never_crossed && A.final_pass == 2) {
             A.pass[idx] = 2;                                   // small-batch path: the host re-runs the batch
         } else {
-            double e;
-            if (never_crossed) {
-                e = __builtin_nan("");                 // CDF never crosses: reference runs off its table
-            } else {
-                // ref: bernoullimodule.c:170-178  errors1 + ((errors2-errors1)*((1-alpha)-prob1)/(prob2-prob1))
-                e = (double)(js - 1) + ((thr - lo) / (hi - lo));
-                if (e < 0) e = 0;
-            }
+            double e = cross_ee(!never_crossed, js, thr, lo, hi);
             const int nsv = A.perm_ns ? (int)gload(A.perm_ns + (perm_cls - A.perm) + slot) : gload(A.ns + idx);
-            if ((A.prm.flags & 32u) && !never_crossed) {                 // MPB_FLAG_COUNT_CELLS (diagnostic, off by default)
+            if ((A.prm.flags & MPB_FLAG_COUNT_CELLS) && !never_crossed) {      // diagnostic, off by default
                 // the table the reference fills for this read: rows 0..js over the L' = len - Ns scored bases, of which
                 // row j is non-zero from base j on: sum_k min(k + 1, J), J = js + 1 (SURVEY 8d "algorithmic flops")
                 const int J = js + 1, Lp = li - nsv;                 // J <= 1024, Lp <= 16383: 32-bit arithmetic is enough
                 const int cells = J <= Lp ? ((J * (J + 1)) >> 1) + (Lp - J) * J : (Lp * (Lp + 1)) >> 1;
                 atomicAdd(&mpb_s_cells, (unsigned long long)(unsigned int)cells);
             }
-            if (A.prm.ambig_mode == 0) e = e + (double)nsv;              // moira.py:827-828
-            const double limit = (A.prm.maxerrors == A.prm.maxerrors) ? A.prm.maxerrors          // moira.py:925-926
-                                                                      : (double)li * A.prm.uncert; // moira.py:949-950
+            e = mpb_add_ns(A.prm, e, nsv);
             if (FMA && A.final_pass != 1 && !never_crossed) {
                 // MPB_FLAG_FAST_FMA keeps the DECISIONS exact: an ee that lands within 1e-9 relative of the
                 // threshold (or, with --round, of an integer) is not trusted -- the read goes to the second
                 // pass, which always runs the three-rounding arithmetic
                 const double tol = 1e-9 * fmax(1.0, fabs(e));
-                bool unsure = fabs(e - limit) <= tol;
-                if (A.prm.flags & 1u) unsure = unsure || fabs(e - rint(e)) <= tol;
+                bool unsure = fabs(e - mpb_limit(A.prm, li)) <= tol;
+                if (A.prm.flags & MPB_FLAG_ROUND) unsure = unsure || fabs(e - rint(e)) <= tol;
                 if (unsure) {
                     if (A.final_pass == 0) { const int pos = atomicAdd(A.ovf_count, 1); A.ovf_list[pos] = idx; }
                     else A.pass[idx] = 2;
                     continue;
                 }
             }
-            if (A.prm.flags & 1u) e = floor(e);                          // moira.py:830-831
-            bool keep_read;
-            if (A.prm.ambig_mode == 2 && (gload(A.cls + idx) & 0x80)) keep_read = false;    // moira.py:911
-            else keep_read = e <= limit;
+            const bool keep_read = mpb_round_and_keep(A.prm, e, class_has_n(A, idx), li);
             gstore(A.ee + idx, e);
             gstore(A.pass + idx, (uint8_t)(keep_read ? 1 : 0));
         }
@@ -1054,7 +1069,7 @@ __global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_dp(DpArgs args,
             }
         }
     }
-    if (args.prm.flags & 32u) {                                // MPB_FLAG_COUNT_CELLS: one device atomic per workgroup
+    if (args.prm.flags & MPB_FLAG_COUNT_CELLS) {               // one device atomic per workgroup
         __syncthreads();
         if (threadIdx.x == 0 && mpb_s_cells) atomicAdd(args.alg_cells, mpb_s_cells);
     }
@@ -1076,24 +1091,11 @@ __global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_dp(DpArgs args,
 // ------------------------------------------------------------------------------------------
 #define MPB_WIDE_R 16
 
-// result of one read: ref bernoullimodule.c:170-178 + moira.py:827-831,911,925-926,949-950 (as the tile epilogue)
-__device__ __forceinline__ void wide_report(const DpArgs &A, int idx, int li, int js, double lo, double hi, bool never_crossed)
+// result of one read (read_result)
+__device__ __forceinline__ void wide_report(const DpArgs &A, int idx, int li, bool crossed, int js, double lo, double hi)
 {
-    const double thr = A.prm.thr;
     double e;
-    if (never_crossed) {
-        e = __builtin_nan("");                     // CDF never crosses: the reference runs off its table
-    } else {
-        e = (double)(js - 1) + ((thr - lo) / (hi - lo));
-        if (e < 0) e = 0;
-    }
-    const int nsv = gload(A.ns + idx);
-    if (A.prm.ambig_mode == 0) e = e + (double)nsv;
-    const double limit = (A.prm.maxerrors == A.prm.maxerrors) ? A.prm.maxerrors : (double)li * A.prm.uncert;
-    if (A.prm.flags & 1u) e = floor(e);
-    bool keep_read;
-    if (A.prm.ambig_mode == 2 && (gload(A.cls + idx) & 0x80)) keep_read = false;
-    else keep_read = e <= limit;
+    const bool keep_read = read_result(A.prm, crossed, js, lo, hi, gload(A.ns + idx), class_has_n(A, idx), li, e);
     gstore(A.ee + idx, e);
     gstore(A.pass + idx, (uint8_t)(keep_read ? 1 : 0));
 }
@@ -1198,18 +1200,9 @@ __global__ __launch_bounds__(64 * W) void k_wide(DpArgs A, const double2 *__rest
                         }
                     }
                     if (mine) {
-                        double a = acc_in_mine, lo = 0.0, hi = 0.0;
-                        int js = -1;
-#pragma unroll
-                        for (int r = 0; r < R; r++) {
-                            const double na = a + v[r];
-                            const bool hit = (js < 0) && (na > thr);
-                            lo = hit ? a : lo;
-                            hi = hit ? na : hi;
-                            js = hit ? (w * 64 * R + lane * R + r) : js;
-                            a = na;
-                        }
-                        wide_report(A, idx, li, js, lo, hi, false);
+                        double lo = 0.0, hi = 0.0;
+                        const int js = cdf_cross(v, acc_in_mine, thr, w * 64 * R + lane * R, lo, hi);
+                        wide_report(A, idx, li, true, js, lo, hi);
                     }
                 }
                 if (lane == 63) { s_acc[ww] = acc; s_found[ww] = found; }
@@ -1218,7 +1211,7 @@ __global__ __launch_bounds__(64 * W) void k_wide(DpArgs A, const double2 *__rest
         }
         if (tid == 0 && !s_found[nw - 1]) {                        // the CDF did not cross inside the row budget
             if (FINAL) {
-                wide_report(A, idx, li, -1, 0.0, 0.0, true);
+                wide_report(A, idx, li, false, -1, 0.0, 0.0);
             } else {
                 const int pos = atomicAdd(A.ovf_count, 1);
                 A.ovf_list[pos] = idx;
@@ -1292,7 +1285,7 @@ __device__ __forceinline__ bool small_one_read(const DpArgs &args, const DpArgs 
     const float v = fmaxf(var, 1e-12f);
     const float x = mu + prm.z * sqrtf(v) + (k3 / v) * prm.zq;           // as k_prepass
     int rows = (int)floorf(fminf(x, 1e9f) + 0.5f) + 1;
-    if (prm.flags & 4u) rows = rows / 2;                                  // MPB_FLAG_TEST_UNDERPREDICT
+    if (prm.flags & MPB_FLAG_TEST_UNDERPREDICT) rows = rows / 2;
     rows = max(min(rows, li - nzero - n_lower + 1), 1);
     if (rows > MPB_TILE_MAX_ROWS) {                                       // a wide read: the host sends the batch down the pipeline
         if (lane == 0) args.pass[i] = 2;
@@ -1301,7 +1294,7 @@ __device__ __forceinline__ bool small_one_read(const DpArgs &args, const DpArgs 
     // (the resident server only -- interleaved A/B there: the in-process entry 17.0 against 18.4 us per call, the broker's
     // workers no different; in k_small's launches it was equal for one read and SLOWER for batches of 64-2048 reads,
     // 35 / 74 / 109 us against 29 / 43 / 60: profiles/r05_per_read_server.txt)
-    if (SYS && !FMA && li <= 1024 && rows <= 64 && !(prm.flags & ~1u)) {
+    if (SYS && !FMA && li <= 1024 && rows <= 64 && !(prm.flags & ~MPB_FLAG_ROUND)) {
         // The resident server's common case, entirely in registers: the row is already here (lane k holds chunk k), so the
         // class body's trips to memory -- the parked row, ns / cls / ident read back, the callee-saved registers of a
         // non-inlined body -- are not needed: 2.5 us of a request's 12.9.  One row per lane (the latency bodies' shape), the
@@ -1345,14 +1338,10 @@ __device__ __forceinline__ bool small_one_read(const DpArgs &args, const DpArgs 
             if (js < 0) {
                 __hip_atomic_store(args.pass + i, (uint8_t)2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             } else {
-                double e = (double)(js - 1) + ((thr - lo) / (hi - lo));     // ref: bernoullimodule.c:170-178
-                if (e < 0) e = 0;
-                if (prm.ambig_mode == 0) e = e + (double)nsv;                // moira.py:827-828
-                const double limit = (prm.maxerrors == prm.maxerrors) ? prm.maxerrors : (double)li * prm.uncert;
-                if (prm.flags & 1u) e = floor(e);                            // moira.py:830-831
+                double e;
+                const bool keep = read_result(prm, true, js, lo, hi, nsv, nzero > 0, li, e);
                 __hip_atomic_store((unsigned long long *)(args.ee + i), (unsigned long long)__double_as_longlong(e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(args.pass + i, (uint8_t)((prm.ambig_mode == 2 && nzero > 0) ? 0 : (e <= limit ? 1 : 0)),   // moira.py:911
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(args.pass + i, (uint8_t)(keep ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
         return true;
@@ -1363,12 +1352,7 @@ __device__ __forceinline__ bool small_one_read(const DpArgs &args, const DpArgs 
     // base costs ~10 instead of ~3 * rows instructions of the wave's dependent chain (a 300-base read of 10 rows:
     // ~18 -> ~8 us).  Same cell arithmetic, same sequential CDF: the split of the rows over lanes never shows in a result.
     const int thin = rows <= 2 ? 0 : 31 - __builtin_clz(rows - 1);
-    bool settled = false;
-    if (prm.flags & 8u) {                                                 // MPB_FLAG_DECISION_ONLY, as k_prepass
-        const float t = mu * (1.0f - 1e-4f) - prm.clow * sqrtf(mu) - 0.02f;
-        const double limit = (prm.maxerrors == prm.maxerrors) ? prm.maxerrors : (double)li * prm.uncert;
-        settled = mu > 1.0f && (double)floorf(t) > limit;
-    }
+    const bool settled = settled_by_chernoff(prm, mu, li);               // as k_prepass
     if (lane == 0) {
         ns_out[i] = nzero + n_lower;
         if (args.ns != ns_out) const_cast<int32_t *>(args.ns)[i] = nzero + n_lower;
@@ -1506,7 +1490,7 @@ __global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_serve(MpbServeBox 
                     // forced to what mpbi_small_params writes (no opt-in flag, ambiguous bases ignored, no limit), and a threshold
                     // outside (0, 1) makes the request one the host answers itself through its checked path (pass = 2 below).
                     prm.flags = 0;
-                    prm.ambig_mode = 1;                             // MPB_AMBIG_IGNORE
+                    prm.ambig_mode = MPB_AMBIG_IGNORE;
                     prm.uncert = 1.0;
                     prm.maxerrors = __builtin_nan("");
                     bad_request = !(prm.thr > 0.0 && prm.thr < 1.0);
@@ -2016,32 +2000,19 @@ __global__ __launch_bounds__(256) void k_narrow(const uint8_t *__restrict__ q, i
             request(ring_lds[S]);
         }
         if (++cur_c == ncq) {
-            // ---- a row block is done: sequential CDF, interpolation, predicate (as the tile classes' epilogue) ----
+            // ---- a row block is done: cdf_cross, read_result ----
             const int64_t i = cur_b * 64 + lane;
             const bool valid = i < n;
-            double acc = 0.0, lo = 0.0, hi = 0.0;
-            int js = -1;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const double na = acc + v[r];
-                const bool hit = (js < 0) && (na > thr);
-                lo = hit ? acc : lo;
-                hi = hit ? na : hi;
-                js = hit ? r : js;
-                acc = na;
-            }
+            double lo = 0.0, hi = 0.0;
+            const int js = cdf_cross(v, 0.0, thr, 0, lo, hi);
             const bool done = valid && js >= 0;
             if (done) {
-                double e = (double)(js - 1) + ((thr - lo) / (hi - lo));     // ref: bernoullimodule.c:170-178
-                if (e < 0) e = 0;
                 const int nsv = 4 * ndw - (int)nonzero;                      // 'N' bases (a read with an 'n' never gets here)
-                if (prm.ambig_mode == 0) e = e + (double)nsv;                // moira.py:827-828
-                const double limit = (prm.maxerrors == prm.maxerrors) ? prm.maxerrors            // moira.py:925-926
-                                                                      : (double)li * prm.uncert; // moira.py:949-950
-                if (prm.flags & 1u) e = floor(e);                            // moira.py:830-831
+                double e;
+                const bool keep = read_result(prm, true, js, lo, hi, nsv, nsv > 0, li, e);
                 ee[i] = e;
                 ns[i] = nsv;
-                pass[i] = (uint8_t)((prm.ambig_mode == 2 && nsv > 0) ? 0 : (e <= limit ? 1 : 0));   // moira.py:911
+                pass[i] = (uint8_t)(keep ? 1 : 0);
             }
             const unsigned long long todo = __ballot(valid && js < 0);
             if (todo) {
@@ -2180,7 +2151,7 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
     uint32_t nonzero = 0;                                      // as k_narrow: the bytes that are NOT zero, four per instruction
     int u = 0, sread = 0;                                      // position in the stream: byte u of its read number sread (wave-uniform)
 
-    // ---- a read is done: sequential CDF, interpolation, predicate (as k_narrow / the tile classes' epilogue) ----
+    // ---- a read is done: cdf_cross, read_result ----
     // `nonzero` has counted the non-zero bytes of the read's chunks; the bytes of its last chunk past its end were made zero
     // before they were looked up (the identity step) and so count as 'N' here: 'N' bases = li - nonzero.
     // (two reads per lane, result arrays aligned for a lane's pair: see finish; R <= 3 only: with four rows the held results do
@@ -2193,27 +2164,13 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
     auto finish = [&](const int64_t sb, const int sr) {
         const int64_t i = sb * rows_sb + (int64_t)lane * k + sr;
         const bool valid = i < n;
-        double acc = 0.0, lo = 0.0, hi = 0.0;
-        int js = -1;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const double na = acc + v[r];
-            const bool hit = (js < 0) && (na > thr);
-            lo = hit ? acc : lo;
-            hi = hit ? na : hi;
-            js = hit ? r : js;
-            acc = na;
-        }
+        double lo = 0.0, hi = 0.0;
+        const int js = cdf_cross(v, 0.0, thr, 0, lo, hi);
         const bool done = valid && js >= 0;
         if (done) {
-            double e = (double)(js - 1) + ((thr - lo) / (hi - lo));     // ref: bernoullimodule.c:170-178
-            if (e < 0) e = 0;
             const int nsv = li - (int)nonzero;                           // 'N' bases (a read with an 'n' never gets here)
-            if (prm.ambig_mode == 0) e = e + (double)nsv;                // moira.py:827-828
-            const double limit = (prm.maxerrors == prm.maxerrors) ? prm.maxerrors            // moira.py:925-926
-                                                                  : (double)li * prm.uncert; // moira.py:949-950
-            if (prm.flags & 1u) e = floor(e);                            // moira.py:830-831
-            const uint8_t ps = (uint8_t)((prm.ambig_mode == 2 && nsv > 0) ? 0 : (e <= limit ? 1 : 0));   // moira.py:911
+            double e;
+            const uint8_t ps = (uint8_t)(read_result(prm, true, js, lo, hi, nsv, nsv > 0, li, e) ? 1 : 0);
             if (pair_stores && sr == 0) {
                 // two reads per lane: the first one's results wait in registers for the second's, and go out together -- 16 + 8 + 2
                 // contiguous bytes per lane instead of two half-used sectors a panel and a half apart (writes 0.26 -> 0.13 GB)
@@ -2685,11 +2642,13 @@ __global__ __launch_bounds__(256, 4) void k_narrow_rg(const uint8_t *__restrict_
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        // ---- the group is done: sequential CDF, interpolation, predicate (as k_narrow / the tile classes' epilogue) ----
+        // ---- the group is done: the crossing (cdf_cross, written out), read_result ----
         {
             const int64_t i = cur_idx;
             const int li = cur_len;
             const bool valid = cur_idx >= 0, good = valid && li >= 0;
+            // cdf_cross's loop, written out here: this kernel sits at its register cap, and the call (whatever its form) lets the
+            // compiler fold the crossing into `done` differently -- 3 more VGPRs spilled, reloaded inside the panel loop (R = 4: 1.5 %)
             double acc = 0.0, lo = 0.0, hi = 0.0;
             int js = -1;
 #pragma unroll
@@ -2703,16 +2662,12 @@ __global__ __launch_bounds__(256, 4) void k_narrow_rg(const uint8_t *__restrict_
             }
             const bool done = good && js >= 0;
             if (done) {
-                double e = (double)(js - 1) + ((thr - lo) / (hi - lo));     // ref: bernoullimodule.c:170-178
-                if (e < 0) e = 0;
                 const int nsv = li - (int)nonzero;                           // 'N' bases (a read with an 'n' never gets here)
-                if (prm.ambig_mode == 0) e = e + (double)nsv;                // moira.py:827-828
-                const double limit = (prm.maxerrors == prm.maxerrors) ? prm.maxerrors            // moira.py:925-926
-                                                                      : (double)li * prm.uncert; // moira.py:949-950
-                if (prm.flags & 1u) e = floor(e);                            // moira.py:830-831
+                double e;
+                const bool keep = read_result(prm, true, js, lo, hi, nsv, nsv > 0, li, e);
                 ee[i] = e;
                 ns[i] = nsv;
-                pass[i] = (uint8_t)((prm.ambig_mode == 2 && nsv > 0) ? 0 : (e <= limit ? 1 : 0));   // moira.py:911
+                pass[i] = (uint8_t)(keep ? 1 : 0);
             }
             const unsigned long long todo = __ballot(valid && !done);
             if (todo) {
@@ -2944,7 +2899,7 @@ void mpb_launch_dp(const uint8_t *q, int64_t n, int64_t stride, const int32_t *l
     int64_t want = (tiles + 4 * chunk_tiles - 1) / (4 * chunk_tiles);   // blocks if every wave took one chunk
     const int blocks = (int)(want < grid_cap ? (want > 0 ? want : 1) : grid_cap);
     DpArgs A = make_args(q, stride, len, prm, ws, ns, ee, pass, 0);
-    if (prm.flags & 2u)
+    if (prm.flags & MPB_FLAG_FAST_FMA)
         hipLaunchKernelGGL((k_dp<true, false>), dim3(blocks), dim3(256), 0, s, A, ws.lut, ws.tables, ws.perm, chunk_tiles);
     else
         hipLaunchKernelGGL((k_dp<false, false>), dim3(blocks), dim3(256), 0, s, A, ws.lut, ws.tables, ws.perm, chunk_tiles);
@@ -3048,7 +3003,7 @@ void mpb_launch_small(const uint8_t *q, int64_t n, int64_t stride, const int32_t
     uint8_t *stage = host ? host->stage : nullptr;
     uint32_t *done = host ? host->done : nullptr;
     const uint32_t token = host ? host->token : 0u;
-    if (prm.flags & 2u)
+    if (prm.flags & MPB_FLAG_FAST_FMA)
         hipLaunchKernelGGL((k_small<true>), dim3(blocks), dim3(256), 0, s, A, ws.lut, n, ns, ws.cls, ws.perm, stage, done, token);
     else
         hipLaunchKernelGGL((k_small<false>), dim3(blocks), dim3(256), 0, s, A, ws.lut, n, ns, ws.cls, ws.perm, stage, done, token);

@@ -95,16 +95,17 @@ def test_small_and_partial_row_blocks(eng, oracle, n):
                                 dict(ambigs="treat_as_errors", round_=True), dict(ambigs="ignore", maxerrors=0.4),
                                 dict(alpha=0.05, uncert=0.002), dict(alpha=0.3), dict(alpha=1e-4), dict(alpha=0.9)])
 def test_modes(eng, oracle, kw):
-    """--ambigs / --round / --maxerrors / alpha: the pass' epilogue is the tile classes' epilogue.  alpha = 0.9 and 0.3 put the
-    crossing on the FIRST row for clean reads (the reference's undefined case: ee = 0 by the Python twin's definition)."""
+    """--ambigs / --round / --maxerrors / alpha: the pass finishes a read with the kernels' shared read_result.  alpha = 0.9 and
+    0.3 put the crossing on the FIRST row for clean reads (the reference's undefined case: ee = 0 by the Python twin's definition)."""
     n, L = 20_000, 300
     q, _ = oracle.synth_fill(n, 320, fixed_len=L, seed=21, profile=1)
     q[::7, 5] = 0
     q[::11, 17] = 255
     ee, ns, ps, _ = oracle.filter_batch(q, fixed_len=L, threads=8, **kw)
-    for rows in (2, 3):
-        e1, n1, p1, c, path = run_device(eng, q, L, narrow_rows=rows, **kw)
-        assert same(e1, ee) and np.array_equal(n1, ns) and np.array_equal(p1, ps), (kw, rows)
+    # stride 320: k_narrow_rs at both row counts; stride 304 (the same reads): k_narrow_rs at 2 rows, k_narrow (LDS-DMA ring) at 3
+    for stride, rows in ((320, 2), (320, 3), (304, 2), (304, 3)):
+        e1, n1, p1, c, path = run_device(eng, q[:, :stride], L, narrow_rows=rows, **kw)
+        assert same(e1, ee) and np.array_equal(n1, ns) and np.array_equal(p1, ps), (kw, stride, rows)
         assert c.n_pass == int(ps.sum())
 
 

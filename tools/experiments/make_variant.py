@@ -93,8 +93,8 @@ VARIANTS = {
     ],
     # k_narrow_rg: no result stores at all (the list of handed-back reads stays)
     "rg_no_results": [
-        ("                ee[i] = e;\n                ns[i] = nsv;\n                pass[i] = (uint8_t)((prm.ambig_mode == 2 && nsv > 0) ? 0 : (e <= limit ? 1 : 0));   // moira.py:911\n            }\n            const unsigned long long todo = __ballot(valid && !done);",
-         "                if (e == 1.2345e-300) ee[i] = e;\n            }\n            const unsigned long long todo = __ballot(valid && !done);"),
+        ("                ee[i] = e;\n                ns[i] = nsv;\n                pass[i] = (uint8_t)(keep ? 1 : 0);\n            }\n            const unsigned long long todo = __ballot(valid && !done);",
+         "                (void)keep;\n                if (e == 1.2345e-300) ee[i] = e;\n            }\n            const unsigned long long todo = __ballot(valid && !done);"),
     ],
 }
 
