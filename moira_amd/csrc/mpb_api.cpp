@@ -100,15 +100,20 @@ struct mpb_ctx {
     // ---- natural-order narrow pass (round 5) ----
     int n_cu = 0;                        // compute units of the device (the persistent grid of k_narrow)
     bool narrow_ok = false;              // the default table satisfies a == 1 - b for every score (checked by mpb_create)
-    void *ws_nar = nullptr;              // wave segments + dense list + per-wave counts / offsets
+    void *ws_nar = nullptr;              // wave segments + dense list + per-wave counts
     int64_t ws_nar_cap = 0;
-    int32_t *pin_words = nullptr;        // pinned host words: [0] list count, [16..32) the sample histogram
+    void *ws_rg = nullptr; int64_t ws_rg_cap = 0;   // the ragged pass' order entries, group costs, wave ranges (first ragged call)
+    int rg_per_cu[MPB_NRG_FORMS] = {0};  // blocks per CU of the ragged pass' instantiations (the first ragged call)
+    // pinned host words: [0] list count, [2..3] passes, [4] overflow re-runs, [5] bad lengths, [16..34) the sample histogram
+    int32_t *pin_words = nullptr;
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)
         bool valid = false; int64_t n = 0, stride = 0; int32_t fixed_len = 0; double alpha = 0; uint32_t flags = 0;
         int rows0 = 0; int split = 0; int calls = 0;
         double expect_back = 0;          // share of the sample (by weight) that needs more rows than rows0 or holds an 'n'
     } nar_choice;
     mpb_path_info last_path{};
+    // the class workspace (cls, tables) describes the last filtered batch as a whole: mpb_last_class_histogram, mpb_last_read_budgets
+    bool classes_whole = true;
     // ---- the per-read entry's resident server (round 5; k_serve with ONE mailbox entry, see serve_one) ----
     struct CtxServe {
         bool tried = false, ok = false, running = false;
@@ -290,6 +295,7 @@ int mpb_destroy(mpb_ctx *c)
     if (c->pin_host) (void)hipHostFree(c->pin_host);
     if (c->pin_words) (void)hipHostFree(c->pin_words);
     if (c->ws_nar) (void)hipFree(c->ws_nar);
+    if (c->ws_rg) (void)hipFree(c->ws_rg);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_lut_private) (void)hipFree(c->d_lut_private);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -656,6 +662,33 @@ static int prepare_batch(mpb_ctx *c, int64_t n, int32_t max_len)
     return MPB_OK;
 }
 
+// The counts of a batch, through the pinned words: passes, overflow re-runs (sorted: the sorted pipeline ran, k_tables zeroed the
+// pass counter) and bad lengths, which fail the call (raised by this call or an earlier one that fetched no counts: moira_pb.h;
+// the prepass gave those reads ee = NaN, pass = 0, never a result computed on a clamped length).
+static int fetch_counts(mpb_ctx *c, int64_t n, int64_t row_stride, const int32_t *d_len, int32_t max_len, const uint8_t *d_pass,
+                        bool sorted, mpb_filter_counts *counts)
+{
+    hipStream_t s = c->stream;
+    unsigned long long *np = reinterpret_cast<unsigned long long *>(c->pin_words + 2);
+    int32_t *novf = c->pin_words + 4, *bad = c->pin_words + 5;
+    *novf = *bad = 0;
+    if (!sorted) HIPCHK(hipMemsetAsync(c->ws.pass_count, 0, sizeof(unsigned long long), s));
+    mpb_launch_count(d_pass, n, c->ws, s);
+    HIPCHK(hipMemcpyAsync(np, c->ws.pass_count, sizeof(*np), hipMemcpyDeviceToHost, s));
+    if (sorted) HIPCHK(hipMemcpyAsync(novf, c->ws.ovf_count, sizeof(*novf), hipMemcpyDeviceToHost, s));
+    if (d_len) HIPCHK(hipMemcpyAsync(bad, c->ws.bad_len, sizeof(*bad), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (*bad) {
+        HIPCHK(hipMemsetAsync(c->ws.bad_len, 0, sizeof(int32_t), s));
+        return fail(MPB_E_INVALID, "%d read length(s) in d_len outside 0..%d (row_stride %lld; reads longer than %d bases "
+                    "are not supported); those reads were given ee = NaN, pass = 0", *bad, max_len, (long long)row_stride, MPB_MAX_LEN);
+    }
+    counts->n_pass = (int64_t)*np;
+    counts->n_fail = n - (int64_t)*np;
+    counts->n_overflow = *novf;
+    return MPB_OK;
+}
+
 // everything after the classification: scan -> scatter -> DP -> wide reads -> overflow pass (-> counts)
 static int filter_device_tail(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t row_stride, const int32_t *d_len,
                               const MpbDevParams &prm, double *d_ee, int32_t *d_ns, uint8_t *d_pass, mpb_filter_counts *counts,
@@ -669,53 +702,41 @@ static int filter_device_tail(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t
     if (max_len + 1 > MPB_TILE_MAX_ROWS) { Span t(c, MPB_K_WIDE); mpb_launch_wide(d_q, row_stride, d_len, prm, c->ws, d_ns, d_ee, d_pass, s); }
     { Span t(c, MPB_K_OVERFLOW); mpb_launch_overflow(d_q, n, row_stride, d_len, prm, c->ws, d_ns, d_ee, d_pass, s); }
     HIPCHK(hipGetLastError());
-    if (counts) {
-        mpb_launch_count(d_pass, n, c->ws, s);
-        unsigned long long np = 0;
-        int32_t novf = 0, bad = 0;
-        HIPCHK(hipMemcpyAsync(&np, c->ws.pass_count, sizeof(np), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&novf, c->ws.ovf_count, sizeof(novf), hipMemcpyDeviceToHost, s));
-        if (d_len) HIPCHK(hipMemcpyAsync(&bad, c->ws.bad_len, sizeof(bad), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (bad) {
-            // a length in d_len was negative or above max_len: those reads were given ee = NaN, pass = 0 by the prepass
-            // (never a result computed on a clamped length), and the call that fetches the counts fails
-            HIPCHK(hipMemsetAsync(c->ws.bad_len, 0, sizeof(int32_t), s));
-            return fail(MPB_E_INVALID, "%d read length(s) in d_len outside 0..%d (row_stride %lld; reads longer than %d bases "
-                        "are not supported); those reads were given ee = NaN, pass = 0", bad, max_len, (long long)row_stride, MPB_MAX_LEN);
-        }
-        counts->n_pass = (int64_t)np;
-        counts->n_fail = n - (int64_t)np;
-        counts->n_overflow = novf;
-    }
-    return MPB_OK;
+    return counts ? fetch_counts(c, n, row_stride, d_len, max_len, d_pass, true, counts) : MPB_OK;
 }
 
 // ---- the natural-order narrow pass (round 5; mpb_internal.h, include/moira_pb.h: mpb_path_info) ---------------------------
 
-static int ensure_narrow_workspace(mpb_ctx *c, int64_t n)
+static int ensure_narrow_workspace(mpb_ctx *c, int64_t n, bool ragged)
 {
-    if (n <= c->ws_nar_cap) return MPB_OK;
+    const bool lists = n > c->ws_nar_cap, rg = ragged && n > c->ws_rg_cap;
+    if (!lists && !rg) return MPB_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
     serve_quiesce(c);
-    if (c->ws_nar) { HIPCHK(hipFree(c->ws_nar)); c->ws_nar = nullptr; c->ws_nar_cap = 0; }
     const int64_t cap = n + n / 8 + 1024;
     const int64_t b_list = align_up((cap + 64) * 4, 256), b_waves = align_up((int64_t)(MPB_NAR_MAX_WAVES + 1) * 4, 256);
-    const int64_t b_groups = align_up((cap / 64 + 2) * 4, 256);
-    // (the ragged pass' order entries, 8 bytes per read, + group costs + wave ranges lie behind the lists)
-    const int64_t b_wins = align_up((cap / 4096 + 2) * 8, 256);
-    HIPCHK(hipMalloc(&c->ws_nar, (size_t)(4 * b_list + 3 * b_waves + b_groups + 2 * b_wins)));
-    char *p = (char *)c->ws_nar;
-    c->ws.nar_seg = (int32_t *)p; p += b_list;
-    c->ws.nar_list = (int32_t *)p; p += b_list;
-    c->ws.nar_wave_count = (int32_t *)p; p += b_waves;
-    c->ws.nar_wave_off = (int32_t *)p; p += b_waves;
-    c->ws.rg_ord = (int2 *)p; p += 2 * b_list;
-    c->ws.rg_gpre = (int32_t *)p; p += b_groups;
-    c->ws.rg_wsum = (unsigned long long *)p; p += b_wins;
-    c->ws.rg_wpre = (unsigned long long *)p; p += b_wins;
-    c->ws.rg_gstart = (int32_t *)p;
-    c->ws_nar_cap = cap;
+    if (lists) {
+        if (c->ws_nar) { HIPCHK(hipFree(c->ws_nar)); c->ws_nar = nullptr; c->ws_nar_cap = 0; }
+        HIPCHK(hipMalloc(&c->ws_nar, (size_t)(2 * b_list + b_waves)));
+        char *p = (char *)c->ws_nar;
+        c->ws.nar_seg = (int32_t *)p; p += b_list;
+        c->ws.nar_list = (int32_t *)p; p += b_list;
+        c->ws.nar_wave_count = (int32_t *)p;
+        c->ws_nar_cap = cap;
+    }
+    if (rg) {
+        if (c->ws_rg) { HIPCHK(hipFree(c->ws_rg)); c->ws_rg = nullptr; c->ws_rg_cap = 0; }
+        const int64_t b_groups = align_up((cap / 64 + 2) * 4, 256), b_wins = align_up((cap / 4096 + 2) * 8, 256);
+        HIPCHK(hipMalloc(&c->ws_rg, (size_t)(2 * b_list + b_groups + 2 * b_wins + b_waves)));
+        char *p = (char *)c->ws_rg;
+        c->ws.rg_ord = (int2 *)p; p += 2 * b_list;
+        c->ws.rg_gpre = (int32_t *)p; p += b_groups;
+        c->ws.rg_wsum = (unsigned long long *)p; p += b_wins;
+        c->ws.rg_wpre = (unsigned long long *)p; p += b_wins;
+        c->ws.rg_gstart = (int32_t *)p;
+        c->ws_rg_cap = cap;
+        if (!c->rg_per_cu[0]) mpb_narrow_rg_blocks_per_cu(c->rg_per_cu);
+    }
     return MPB_OK;
 }
 
@@ -829,15 +850,10 @@ static int filter_device_narrow(mpb_ctx *c, int rows0, int split, const uint8_t 
 {
     int rc;
     hipStream_t s = c->stream;
-    if ((rc = ensure_narrow_workspace(c, n))) return rc;
-    // persistent grid: as many workgroups as fit the CUs' LDS at once
-    const int lds = d_len ? mpb_narrow_rs_lds_bytes()
-                          : (mpb_narrow_rs_reads_per_lane(row_stride, rows0) ? mpb_narrow_rs_lds_bytes() : mpb_narrow_lds_bytes());
-    const int per_cu = (160 * 1024) / lds;
-    const int grid = (c->n_cu > 0 ? c->n_cu : 256) * (per_cu > 0 ? per_cu : 1);
+    if ((rc = ensure_narrow_workspace(c, n, d_len != nullptr))) return rc;
     { Span t(c, MPB_K_NARROW);
-      if (d_len) mpb_launch_narrow_ragged(rows0, split, d_q, n, row_stride, d_len, prm, c->ws, d_ee, d_ns, d_pass, c->ws.nar_list, grid, s);
-      else mpb_launch_narrow(rows0, d_q, n, row_stride, fixed_len, prm, c->ws, d_ee, d_ns, d_pass, c->ws.nar_list, grid, s); }
+      mpb_launch_narrow(rows0, split, d_q, n, row_stride, fixed_len, d_len, prm, c->ws, d_ee, d_ns, d_pass, c->n_cu > 0 ? c->n_cu : 256,
+                        c->rg_per_cu, s); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->pin_words, c->ws.nar_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -852,7 +868,7 @@ static int filter_device_narrow(mpb_ctx *c, int rows0, int split, const uint8_t 
     // was not the batch's -- so that clearly more came back than the sample's own share of unfinished reads): the next calls of this
     // shape run without a cut
     if (!forced && split > 0 && (double)m > (1.5 * c->nar_choice.expect_back + 0.002) * (double)n) c->nar_choice.split = 0;
-    int32_t novf = 0;
+    c->classes_whole = false;                        // the class workspace: the handed-back reads at most
     if (m > 0) {
         // The reads handed back go through the sorted pipeline WHERE THEY LIE (round 6: the prepass and the scatter walk the list,
         // the DP addresses rows and results by read anyway): no dense copy of their rows, no block of memory for it.  When they
@@ -860,34 +876,15 @@ static int filter_device_narrow(mpb_ctx *c, int rows0, int split, const uint8_t 
         // the same results, one pass over everything is cheaper than a list of most of it (break-even near one half).
         if (!forced && m > n / 2) {
             c->last_path.n_fallback = n;
+            c->classes_whole = true;
             return filter_device_general(c, d_q, n, row_stride, d_len, fixed_len, prm.max_len, params, d_ee, d_ns, d_pass, counts);
         }
         mpb_filter_params sub = *params;
         sub.flags = (sub.flags & ~((15u << 8) | (255u << 12))) | MPB_FLAG_NO_NARROW;
         if ((rc = filter_device_general(c, d_q, m, row_stride, d_len, fixed_len, prm.max_len, &sub, d_ee, d_ns, d_pass, nullptr, c->ws.nar_list, n))) return rc;
         HIPCHK(hipGetLastError());
-        if (counts) HIPCHK(hipMemcpyAsync(&novf, c->ws.ovf_count, sizeof(novf), hipMemcpyDeviceToHost, s));
     }
-    if (counts) {
-        if ((rc = ensure_workspace(c, 1))) return rc;
-        HIPCHK(hipMemsetAsync(c->ws.pass_count, 0, sizeof(unsigned long long), s));
-        mpb_launch_count(d_pass, n, c->ws, s);
-        unsigned long long np = 0;
-        int32_t bad = 0;
-        HIPCHK(hipMemcpyAsync(&np, c->ws.pass_count, sizeof(np), hipMemcpyDeviceToHost, s));
-        if (d_len) HIPCHK(hipMemcpyAsync(&bad, c->ws.bad_len, sizeof(bad), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (bad) {
-            // raised by an earlier call that fetched no counts (include/moira_pb.h: "the next call that fetches counts fails")
-            HIPCHK(hipMemsetAsync(c->ws.bad_len, 0, sizeof(int32_t), s));
-            return fail(MPB_E_INVALID, "%d read length(s) in d_len outside 0..%d (row_stride %lld; reads longer than %d bases "
-                        "are not supported); those reads were given ee = NaN, pass = 0", bad, prm.max_len, (long long)row_stride, MPB_MAX_LEN);
-        }
-        counts->n_pass = (int64_t)np;
-        counts->n_fail = n - (int64_t)np;
-        counts->n_overflow = novf;
-    }
-    return MPB_OK;
+    return counts ? fetch_counts(c, n, row_stride, d_len, prm.max_len, d_pass, m > 0, counts) : MPB_OK;
 }
 
 int mpb_filter_device(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t row_stride,
@@ -903,6 +900,7 @@ int mpb_filter_device(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t row_str
     if (n == 0) return MPB_OK;
     c->classified.valid = false;                     // the workspace now describes THIS batch
     c->last_path = mpb_path_info{};
+    c->classes_whole = true;                         // (unless the narrow pass takes it)
     if ((rc = ensure_workspace(c, 1))) return rc;    // the small block (tables, counters) exists from here on
     if (narrow_eligible(c, n, row_stride, d_len, fixed_len, params)) {
         const MpbDevParams prm = make_dev_params(params, fixed_len, max_len);
@@ -988,6 +986,7 @@ int mpb_filter_device_classified(mpb_ctx *c, const uint8_t *d_q, int64_t n, int6
         return fail(MPB_E_INVALID, "mpb_filter_device_classified: the last call on this context that classified a batch "
                                    "(mpb_decode_classify_device) did not produce THIS batch with THESE parameters and result arrays");
     c->classified.valid = false;                     // consumed: the DP passes overwrite parts of the workspace
+    c->classes_whole = true;
     const MpbDevParams prm = make_dev_params(params, fixed_len, max_len);
     return filter_device_tail(c, d_q, n, row_stride, d_len, prm, d_ee, d_ns, d_pass, counts);
 }
@@ -1010,7 +1009,7 @@ int mpb_last_class_histogram(mpb_ctx *c, int32_t *caps, int64_t *cnts, int32_t m
 {
     CTXCHK(c);
     if (!caps || !cnts || max_classes < 0) return fail(MPB_E_INVALID, "bad arguments");
-    if (c->last_path.narrow_rows != 0)      // (the workspace then describes the handed-back sub-batch, or an earlier batch: ADVICE r5)
+    if (!c->classes_whole)                  // (the workspace then describes the handed-back sub-batch, or an earlier batch: ADVICE r5)
         return fail(MPB_E_INVALID, "the last filter call took the narrow pass (%d rows): there is no class histogram of its batch; "
                                    "call with MPB_FLAG_NO_NARROW to get one", c->last_path.narrow_rows);
     if (!c->ws.tables) return 0;
@@ -1027,7 +1026,7 @@ int mpb_last_read_budgets(mpb_ctx *c, int32_t *caps_out, int64_t n)
 {
     CTXCHK(c);
     if (!caps_out || n < 0) return fail(MPB_E_INVALID, "bad arguments");
-    if (c->last_path.narrow_rows != 0)
+    if (!c->classes_whole)
         return fail(MPB_E_INVALID, "the last filter call took the narrow pass (%d rows): there are no per-read row budgets of its "
                                    "batch; call with MPB_FLAG_NO_NARROW to get them", c->last_path.narrow_rows);
     if (n > c->ws_cap || !c->ws.cls) return fail(MPB_E_INVALID, "no filter call of at least %lld reads precedes", (long long)n);

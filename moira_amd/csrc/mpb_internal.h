@@ -140,13 +140,13 @@ struct MpbWorkspace {
     unsigned long long *pass_count;  // [1]
     unsigned long long *alg_cells;   // [1] MPB_FLAG_COUNT_CELLS: algorithmic DP cells of the last mpb_filter_device call
     const double2 *lut;    // [256] {1-p, p'} on device
-    int32_t  *nar_count;   // [1] reads the natural-order narrow pass (k_narrow) could not finish
-    int32_t  *nar_seg;     // [n + 64] ... as the waves of k_narrow listed them, a segment per wave
-    int32_t  *nar_list;    // [n + 64] ... compacted: the dense list the sub-batch is gathered by
-    int32_t  *nar_wave_count, *nar_wave_off;   // [MPB_NAR_MAX_WAVES] entries of each wave's segment / where it goes in nar_list
+    int32_t  *nar_count;   // [1] reads the natural-order narrow pass could not finish
+    int32_t  *nar_seg;     // [n + 64] ... as the waves of the pass listed them, a segment per wave
+    int32_t  *nar_list;    // [n + 64] ... compacted: the dense list the sorted pipeline walks
+    int32_t  *nar_wave_count;   // [MPB_NAR_MAX_WAVES] entries of each wave's segment
     int32_t  *nar_sample;  // [MPB_NAR_BUCKETS + 2] histogram of the batch sample that picks the pass (k_sample) + the chunks of the
                            // shortest sampled reads that need a third / a fourth row (ragged batches)
-    // the narrow pass of RAGGED batches (k_narrow_rg, round 6)
+    // the narrow pass of RAGGED batches (k_narrow_rg, round 6; allocated by the first ragged call)
     int2     *rg_ord;      // [n + 64] {read, length} in the order the pass walks them: windows of 4096 reads sorted by length
     int32_t  *rg_gpre;     // [n / 64 + 2] cost of each group of 64 entries (from its longest read), summed up inside its window
     unsigned long long *rg_wsum, *rg_wpre;   // [n / 4096 + 2] cost of each window; exclusive prefix ([nwin] = the total)
@@ -160,8 +160,9 @@ struct MpbWorkspace {
 // the read turns out to need, so every read whose CDF crosses inside them is finished bit for bit; the others -- and every read
 // with a lower-case 'n', whose table entry is a NaN in this pass -- go on a list, are gathered into a dense sub-batch and run
 // through the ordinary pipeline.  The choice is made per batch from a sample of <= 0.1 % of the reads.
-// Two forms of the same pass: k_narrow_rs (row strides that are a multiple of 64 bytes: a lane walks one or two rows as one stream
-// of whole 128-byte lines, panels staged in registers) and k_narrow (any stride: 64-byte panels through an LDS-DMA ring).
+// Three kernels, one arithmetic (nar_run) and one end of a read (nar_finish): k_narrow_rs (a lane walks one or more rows as one
+// stream of whole 128-byte lines, panels staged in registers), k_narrow (any stride: 64-byte panels through an LDS-DMA ring) and
+// k_narrow_rg (ragged batches, groups of 64 reads of nearly one length).
 #define MPB_NAR_MIN_ROWS 2
 #define MPB_NAR_MAX_ROWS 4
 #define MPB_NAR_BUCKETS 16                // k_sample: [0] reads with a lower-case 'n', [r] reads that need r rows (r = 1..14), [15] more
@@ -232,22 +233,21 @@ void mpb_launch_lambda(const uint8_t *q, int64_t n, int64_t stride, const int32_
 void mpb_launch_decode(const uint8_t *seq, const uint8_t *qual, int64_t n, int64_t stride, const int32_t *len,
                        int32_t fixed_len, int32_t offset, uint8_t *out, int32_t *err, hipStream_t s);
 void mpb_launch_count(const uint8_t *pass, int64_t n, const MpbWorkspace &ws, hipStream_t s);
-// the natural-order narrow pass (fixed-length batches, the context's default table): rows0 in MPB_NAR_MIN_ROWS..MPB_NAR_MAX_ROWS.
-// Finished reads get ee / ns (= 0) / pass; the others end up in `list` (dense, in wave order; their number in ws.nar_count).
-void mpb_launch_narrow(int rows0, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const MpbDevParams &prm,
-                       const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int32_t *list, int grid_blocks, hipStream_t s);
-int mpb_narrow_lds_bytes();               // static LDS of one k_narrow workgroup (the host sizes the persistent grid from it)
-int mpb_narrow_rs_reads_per_lane(int64_t stride, int rows0);   // k_narrow_rs (whole-line panels staged in registers): reads per lane, 0 = k_narrow
-int mpb_narrow_rs_lds_bytes();
+// the natural-order narrow pass (the context's default table), rows0 in MPB_NAR_MIN_ROWS..MPB_NAR_MAX_ROWS: fixed-length batches
+// (len == nullptr: k_narrow_rs, or k_narrow for rows of no multiple of 64 bytes at three or four rows) and ragged ones (k_rag_sort,
+// k_rag_scan, k_narrow_rg: rows of up to MPB_RG_MAX_STRIDE bytes; split_chunks > 0, rows0 >= 3: groups whose longest read has at
+// most that many 16-byte chunks run with rows0 - 1 rows).  Finished reads get ee / ns / pass; the others end up in ws.nar_list
+// (dense, in wave order; their number in ws.nar_count).  A persistent grid on n_cu CUs; rg_per_cu: the blocks per CU of the
+// MPB_NRG_FORMS ragged instantiations (mpb_narrow_rg_blocks_per_cu; only read for ragged batches).
+#define MPB_RG_MAX_STRIDE 4096
+#define MPB_NRG_FORMS 5
+void mpb_launch_narrow(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len,
+                       const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int n_cu,
+                       const int *rg_per_cu, hipStream_t s);
+void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS]);
 // predicted row budgets of `n_sample` reads spread over the batch -> ws.nar_sample (zeroed here)
 void mpb_launch_sample(const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len, const MpbDevParams &prm,
                        const MpbWorkspace &ws, int n_sample, hipStream_t s);
-// the narrow pass of a RAGGED batch (k_rag_sort, k_rag_scan, k_narrow_rg): rows of up to MPB_RG_MAX_STRIDE bytes
-#define MPB_RG_MAX_STRIDE 4096
-// split_chunks > 0 (rows0 >= 3): groups whose longest read has at most that many 16-byte chunks run with rows0 - 1 rows
-void mpb_launch_narrow_ragged(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, const int32_t *len,
-                              const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int32_t *list,
-                              int grid_blocks, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

@@ -1808,21 +1808,158 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p)      // a __shared
 typedef double2 nar_entry_t;
 #define NAR_P(e) ((e).y)
 #define NAR_A(e) ((e).x)
+#define NAR_LOOKUP(w, t) s_p[((w) >> (8 * (t))) & 0xffu]
 
-template <int R>
-__device__ __forceinline__ void nar_step(double (&v)[R], const nar_entry_t e)
+// The table in LDS, as all three kernels hold it.  Byte 0 ('N'): the identity step {1, 0} the table holds anyway (counted by
+// nar_run); byte 255 ('n'): a NaN -- the read is handed back.  The kernel's only block barrier.
+__device__ __forceinline__ void nar_stage_table(nar_entry_t *s_p, const double2 *__restrict__ lut_g, int tid)
 {
-    const double a = NAR_A(e), p = NAR_P(e);
-#pragma unroll
-    for (int r = R - 1; r >= 1; r--) v[r] = cell<false>(a, v[r], p, v[r - 1]);
-    v[0] = a * v[0];
+    s_p[tid] = tid == 255 ? make_double2(__builtin_nan(""), __builtin_nan("")) : lut_g[tid];
+    __syncthreads();
 }
 
-template <int R>
-__device__ __forceinline__ void nar_dword(double (&v)[R], const nar_entry_t *tab, uint32_t w)
+// The arithmetic of all three kernels.  ND dwords (4 ND bases) of the lane's read, already in registers: the table two dwords
+// (eight bases) ahead of the arithmetic; 1 - p one dword ahead; and inside a base the operations in an order that keeps dependent
+// FP64 instructions three issue slots apart (a dependent v_mul_f64 / v_add_f64 issues 8-9 cycles after its producer,
+// tools/experiments/fp64_latency.hip: back to back it costs a slot): every product first, then the sums, then the next dword's
+// 1 - p and the table address of the base eight ahead.  The fences pin that order (the machine scheduler otherwise puts each sum
+// right behind its product).  Fully unrolled, so the rotating register roles cost no copies.  One straight line: a branch inside
+// it makes the compiler drain the LDS queue where the paths meet (measured: a loop over 16-base chunks with the same look-ahead
+// is 8 % slower than this).  'N' bases are counted on the way: `nonzero` counts the bytes that are NOT zero, four per
+// instruction -- v_msad_u8 adds |a - b| over the bytes whose reference byte b is non-zero, and a = b ^ 1 differs from b by
+// exactly one -- which costs half an instruction per base where looking for zero bytes would cost one.
+template <int R, int ND>
+__device__ __forceinline__ void nar_run(double (&v)[R], uint32_t &nonzero, const nar_entry_t *s_p, const uint32_t (&wd)[16])
+{
+    nar_entry_t P[ND + 2][4];
+    double A[ND + 1][4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) P[0][t] = NAR_LOOKUP(wd[0], t);
+#pragma unroll
+    for (int t = 0; t < 4; t++) P[1][t] = NAR_LOOKUP(wd[1], t);
+#pragma unroll
+    for (int t = 0; t < 4; t++) A[0][t] = NAR_A(P[0][t]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int d = 0; d < ND; d++) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const double a = A[d][t], p = NAR_P(P[d][t]);
+            double x[R], y[R];
+#pragma unroll
+            for (int r = R - 1; r >= 1; r--) x[r] = a * v[r];
+#pragma unroll
+            for (int r = R - 1; r >= 1; r--) y[r] = p * v[r - 1];
+            v[0] = a * v[0];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = R - 1; r >= 1; r--) v[r] = x[r] + y[r];
+            __builtin_amdgcn_sched_barrier(0);
+            if (d < ND - 1) A[d + 1][t] = NAR_A(P[d + 1][t]);
+            if (d < ND - 2) P[d + 2][t] = NAR_LOOKUP(wd[d + 2], t);
+            if (t == 0) nonzero = __builtin_amdgcn_msad_u8(wd[d] ^ 0x01010101u, wd[d], nonzero);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+// NC 16-byte chunks of the lane's read (chunk(c): where chunk c lies in LDS) into registers.  Chunks from `full` on (the first
+// `full` are complete in every lane: wave-uniform) are masked by the lane's own `nb` bases from the first chunk on: the bytes
+// past its end become zero -- the identity step, so a read's last bases take the same code as the others, and 'N' bases =
+// length - nonzero.  UNIFORM (every lane's read has the same length: k_narrow, k_narrow_rs): only the last chunk can be partial,
+// and no other is tested.
+template <int NC, bool UNIFORM, typename Chunk>
+__device__ __forceinline__ void nar_load(uint32_t (&wd)[16], const Chunk &chunk, int full, int nb)
 {
 #pragma unroll
-    for (int t = 0; t < 4; t++) nar_step<R>(v, tab[(w >> (8 * t)) & 0xffu]);
+    for (int c = 0; c < NC; c++) {
+        const u32x4 x = *reinterpret_cast<const u32x4 *>(chunk(c));
+        wd[4 * c] = x.x; wd[4 * c + 1] = x.y; wd[4 * c + 2] = x.z; wd[4 * c + 3] = x.w;
+        if ((!UNIFORM || c == NC - 1) && c >= full) {
+#pragma unroll
+            for (int d = 0; d < 4; d++) wd[4 * c + d] = mask_dword(wd[4 * c + d], nb - 16 * c - 4 * d);
+        }
+    }
+}
+
+struct NarNothing { __device__ void operator()() const {} };
+
+// One run of nch chunks (1..4, wave-uniform) of the lane's read: nar_load, then `loaded()` (k_narrow: its ring slot is free
+// again), then nar_run<R, 4 nch>.
+template <int R, bool UNIFORM, typename Chunk, typename Loaded = NarNothing>
+__device__ __forceinline__ void nar_chunks(double (&v)[R], uint32_t &nonzero, const nar_entry_t *s_p, const Chunk &chunk, int nch,
+                                           int full, int nb, const Loaded &loaded = Loaded())
+{
+    uint32_t wd[16];
+    switch (nch) {
+    case 4: nar_load<4, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 16>(v, nonzero, s_p, wd); break;
+    case 3: nar_load<3, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 12>(v, nonzero, s_p, wd); break;
+    case 2: nar_load<2, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 8>(v, nonzero, s_p, wd); break;
+    default: nar_load<1, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 4>(v, nonzero, s_p, wd); break;
+    }
+}
+
+// ---- a read is done (k_narrow, k_narrow_rs; k_narrow_rg writes the same out, see there): the crossing, read_result, the hand-back
+// valid: a read of the batch; good: one the pass may finish.  A good read whose CDF crosses 1 - alpha inside the R rows is done:
+// its results are returned, the stores are the caller's.  Every other valid read (more rows needed, or a lower-case 'n': a NaN
+// never crosses) is appended to the wave's segment, in lane order.  The crossing is cdf_cross's loop written out, as k_narrow_rg
+// needs it (called there, cdf_cross spilled 3 more VGPRs inside the panel loop).
+struct NarRead { bool done, keep; int nsv; double e; };
+template <int R>
+__device__ __forceinline__ NarRead nar_finish(double (&v)[R], uint32_t &nonzero, const MpbDevParams &prm, bool valid, bool good,
+                                              int li, int64_t i, int32_t *my_seg, int &nlist, int lane)
+{
+    double acc = 0.0, lo = 0.0, hi = 0.0;
+    int js = -1;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const double na = acc + v[r];
+        const bool hit = (js < 0) && (na > prm.thr);
+        lo = hit ? acc : lo;
+        hi = hit ? na : hi;
+        js = hit ? r : js;
+        acc = na;
+    }
+    NarRead o;
+    o.done = good && js >= 0;
+    o.nsv = li - (int)nonzero;                                       // 'N' bases (a read with an 'n' is never done)
+    if (o.done) o.keep = read_result(prm, true, js, lo, hi, o.nsv, o.nsv > 0, li, o.e);
+    const unsigned long long todo = __ballot(valid && !o.done);
+    if (todo) {
+        if (valid && !o.done) my_seg[nlist + __popcll(todo & ((1ull << lane) - 1ull))] = (int32_t)i;
+        nlist += __popcll(todo);
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
+    nonzero = 0;
+    return o;
+}
+
+// The register-staged tile of k_narrow_rs and k_narrow_rg: a wave's private 8 KB, 64 streams x 128 bytes, whose 16-byte slots are
+// XOR-swizzled by the stream number (writes and reads both conflict-free, no padding).  Loading: lane (r8, c8) of load
+// instruction j holds slot c8 of stream 8 j + r8, which goes to stream * 128 + ((slot ^ ((stream >> 1) & 7)) * 16), and
+// (8 j + r8) >> 1 & 7 = 4 (j & 1) + (r8 >> 1); reading: lane = stream, slot c at x0 ^ (c << 4).
+#define MPB_NRS_TILE 8192                   // 64 streams x 128 bytes
+// (Out-parameters, not a struct: with a struct's constructor k_narrow_rg<4, 3> spilled two more registers inside its panel loop.)
+__device__ __forceinline__ void nar_tile_lane(int lane, int &wr_even, int &wr_odd, int &x0)
+{
+    const int r8 = lane >> 3, c8 = lane & 7;
+    wr_even = r8 * 128 + ((c8 ^ (r8 >> 1)) << 4);
+    wr_odd = r8 * 128 + ((c8 ^ (4 + (r8 >> 1))) << 4);
+    x0 = lane * 128 + (((lane >> 1) & 7) << 4);
+}
+__device__ __forceinline__ void nar_tile_write(uint8_t *tile, int wr_even, int wr_odd, const u32x4 (&pre)[8])
+{
+#pragma unroll
+    for (int j = 0; j < 8; j++) *reinterpret_cast<u32x4 *>(tile + j * 1024 + ((j & 1) ? wr_odd : wr_even)) = pre[j];
+}
+// Between a tile's writes and its reads, and its reads and the next panel's writes: the wave's LDS operations in order, and no
+// wait for lgkmcnt (wave_lds_fence's drain is what this fence deliberately leaves out).
+__device__ __forceinline__ void nar_tile_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 
@@ -1849,9 +1986,7 @@ __global__ __launch_bounds__(256) void k_narrow(const uint8_t *__restrict__ q, i
     __shared__ __attribute__((aligned(16))) uint8_t s_ring3[D > 3 ? 4 : 1][D > 3 ? MPB_NAR_PANEL : 16];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // byte 0 ('N'): the identity step {1, 0} the table holds anyway (counted below); byte 255 ('n'): a NaN -- the read is handed back
-    s_p[tid] = tid == 255 ? make_double2(__builtin_nan(""), __builtin_nan("")) : lut_g[tid];
-    __syncthreads();                                          // the only block barrier
+    nar_stage_table(s_p, lut_g, tid);
     const int64_t nblk = (n + 63) >> 6;                       // row blocks of 64 reads
     const int ncq = (li + 63) >> 6;                           // 64-byte panels per row block (li >= 1)
     const int64_t gw = (int64_t)blockIdx.x * 4 + w, W = (int64_t)gridDim.x * 4;
@@ -1910,12 +2045,7 @@ __global__ __launch_bounds__(256) void k_narrow(const uint8_t *__restrict__ q, i
 #pragma unroll
     for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
     const uint32_t tl = (uint32_t)((lane >> 4) * 1024 + (lane & 15) * 16);      // this lane's row inside a panel
-    const double thr = prm.thr;
-    // 'N' bases of the lane's read: the bytes that are NOT zero are counted, four per instruction -- v_msad_u8 adds |a - b| over the
-    // bytes whose reference byte b is non-zero, and a = b ^ 1 differs from b by exactly one -- which costs half an instruction
-    // per base where looking for zero bytes would cost one
     uint32_t nonzero = 0;
-    const int ndw = (li + 3) >> 2;                            // dwords counted per read (bytes past its end are made non-zero)
 
     auto step = [&](const int S, const int64_t s) {
         (void)s;
@@ -1927,101 +2057,23 @@ __global__ __launch_bounds__(256) void k_narrow(const uint8_t *__restrict__ q, i
         else if (younger == 1) nar_wait<4>();
         else nar_wait<0>();
         }
+        // The lane's chunks of the panel -- all four, or (the last panel of a row whose length is no multiple of 64) those the read
+        // reaches, the bytes past its end masked -- in registers; the slot is free then, and refilled before the run starts.
         const uint8_t *mine = ring[S] + tl;
         const int nbases = min(64, li - cur_c * 64);        // wave-uniform
-        if (nbases == 64) {
-            // All four chunks of the panel at once; the table two dwords (eight bases) ahead of the arithmetic; 1 - p one dword
-            // ahead; and inside a base the operations in an order that keeps dependent FP64 instructions three issue slots apart
-            // (a dependent v_mul_f64 / v_add_f64 issues 8-9 cycles after its producer, tools/experiments/fp64_latency.hip: back
-            // to back it costs a slot): every product first, then the sums, then the next dword's 1 - p and the table address of
-            // the base eight ahead.  The fences pin that order (the machine scheduler otherwise puts each sum right behind its
-            // product).  Fully unrolled, so the rotating register roles cost no copies.
-            uint32_t wd[16];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint4 x = *reinterpret_cast<const uint4 *>(mine + k * 256);
-                wd[4 * k] = x.x; wd[4 * k + 1] = x.y; wd[4 * k + 2] = x.z; wd[4 * k + 3] = x.w;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the panel is in registers: its slot may be overwritten
+        nar_chunks<R, true>(v, nonzero, s_p, [&](const int c) { return mine + c * 256; }, (nbases + 15) >> 4, nbases >> 4, nbases, [&] {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             request(ring_lds[S]);
-#define NAR_LOOKUP(w, t) s_p[((w) >> (8 * (t))) & 0xffu]
-            nar_entry_t P[18][4];                       // P[d]: table entries of dword d (static indices only)
-            double A[17][4];                            // A[d]: their 1 - p
-#pragma unroll
-            for (int t = 0; t < 4; t++) P[0][t] = NAR_LOOKUP(wd[0], t);
-#pragma unroll
-            for (int t = 0; t < 4; t++) P[1][t] = NAR_LOOKUP(wd[1], t);
-#pragma unroll
-            for (int t = 0; t < 4; t++) A[0][t] = NAR_A(P[0][t]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int d = 0; d < 16; d++) {
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const double a = A[d][t], p = NAR_P(P[d][t]);
-                    double x[R], y[R];
-#pragma unroll
-                    for (int r = R - 1; r >= 1; r--) x[r] = a * v[r];
-#pragma unroll
-                    for (int r = R - 1; r >= 1; r--) y[r] = p * v[r - 1];
-                    v[0] = a * v[0];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int r = R - 1; r >= 1; r--) v[r] = x[r] + y[r];
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (d < 15) A[d + 1][t] = NAR_A(P[d + 1][t]);
-                    if (d < 14) P[d + 2][t] = NAR_LOOKUP(wd[d + 2], t);
-                    if (t == 0) nonzero = __builtin_amdgcn_msad_u8(wd[d] ^ 0x01010101u, wd[d], nonzero);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        } else {
-            for (int k = 0; k * 16 < nbases; k++) {
-                const uint4 x = *reinterpret_cast<const uint4 *>(mine + k * 256);
-                uint32_t w0 = x.x, w1 = x.y, w2 = x.z, w3 = x.w;
-                const int nb = min(16, nbases - k * 16);
-                int d = 0;
-#pragma unroll 1
-                for (; d * 4 + 4 <= nb; d++) {
-                    nonzero = __builtin_amdgcn_msad_u8(w0 ^ 0x01010101u, w0, nonzero);
-                    nar_dword<R>(v, s_p, w0);
-                    w0 = w1; w1 = w2; w2 = w3;
-                }
-                if (d * 4 < nb) {                           // a length that is not a multiple of 4: its last 1..3 bases
-                    const uint32_t wf = w0 | (0x01010101u << (8 * (nb - d * 4)));     // bytes past the end: non-zero
-                    nonzero = __builtin_amdgcn_msad_u8(wf ^ 0x01010101u, wf, nonzero);
-                    for (int t = d * 4; t < nb; t++) {
-                        nar_step<R>(v, s_p[w0 & 0xffu]);
-                        w0 >>= 8;
-                    }
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (a partial panel is read chunk by chunk: free at its end)
-            request(ring_lds[S]);
-        }
+        });
         if (++cur_c == ncq) {
-            // ---- a row block is done: cdf_cross, read_result ----
             const int64_t i = cur_b * 64 + lane;
             const bool valid = i < n;
-            double lo = 0.0, hi = 0.0;
-            const int js = cdf_cross(v, 0.0, thr, 0, lo, hi);
-            const bool done = valid && js >= 0;
-            if (done) {
-                const int nsv = 4 * ndw - (int)nonzero;                      // 'N' bases (a read with an 'n' never gets here)
-                double e;
-                const bool keep = read_result(prm, true, js, lo, hi, nsv, nsv > 0, li, e);
-                ee[i] = e;
-                ns[i] = nsv;
-                pass[i] = (uint8_t)(keep ? 1 : 0);
+            const NarRead r = nar_finish(v, nonzero, prm, valid, valid, li, i, my_seg, nlist, lane);
+            if (r.done) {
+                ee[i] = r.e;
+                ns[i] = r.nsv;
+                pass[i] = (uint8_t)(r.keep ? 1 : 0);
             }
-            const unsigned long long todo = __ballot(valid && js < 0);
-            if (todo) {
-                if (valid && js < 0) my_seg[nlist + __popcll(todo & ((1ull << lane) - 1ull))] = (int32_t)i;
-                nlist += __popcll(todo);
-            }
-#pragma unroll
-            for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-            nonzero = 0;
             cur_c = 0;
             cur_b += W;
         }
@@ -2048,51 +2100,11 @@ __global__ __launch_bounds__(256) void k_narrow(const uint8_t *__restrict__ q, i
 // instruction (eight lanes = one line) into registers, one panel (32 VGPRs) ahead of the arithmetic through a range-checked
 // buffer (rows past the end of the matrix read zeros = 'N' = the identity step), written into a private 8 KB tile whose
 // 16-byte slots are XOR-swizzled by the stream number (writes and reads both conflict-free, no padding: 16 waves per CU),
-// and read back a stream per lane.  The reads of a lane follow each other in its stream: at every end of a read the same
-// epilogue as k_narrow's; bytes between a read's end and the next read's start (the row padding) are skipped by whole
+// and read back a stream per lane.  The reads of a lane follow each other in its stream: at every end of a read nar_finish;
+// bytes between a read's end and the next read's start (the row padding) are skipped by whole
 // 64-byte halves (wave-uniform) or never looked at.  Same cell arithmetic, same sequential CDF, same list of reads handed
 // back (a wave's segment holds 64 k slots per stream block).
 // ------------------------------------------------------------------------------------------
-#define MPB_NRS_TILE 8192                   // 64 streams x 128 bytes
-
-// ND dwords (4 ND bases) of the lane's stream, already in registers: the table two dwords ahead of the arithmetic, products
-// before sums (k_narrow's unrolled body; see there).  One straight line: a branch inside it makes the compiler drain the LDS
-// queue where the paths meet (measured: a loop over 16-base chunks with the same look-ahead is 8 % slower than this).
-template <int R, int ND>
-__device__ __forceinline__ void nar_run(double (&v)[R], uint32_t &nonzero, const nar_entry_t *s_p, const uint32_t (&wd)[16])
-{
-    nar_entry_t P[ND + 2][4];
-    double A[ND + 1][4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) P[0][t] = NAR_LOOKUP(wd[0], t);
-#pragma unroll
-    for (int t = 0; t < 4; t++) P[1][t] = NAR_LOOKUP(wd[1], t);
-#pragma unroll
-    for (int t = 0; t < 4; t++) A[0][t] = NAR_A(P[0][t]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int d = 0; d < ND; d++) {
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const double a = A[d][t], p = NAR_P(P[d][t]);
-            double x[R], y[R];
-#pragma unroll
-            for (int r = R - 1; r >= 1; r--) x[r] = a * v[r];
-#pragma unroll
-            for (int r = R - 1; r >= 1; r--) y[r] = p * v[r - 1];
-            v[0] = a * v[0];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int r = R - 1; r >= 1; r--) v[r] = x[r] + y[r];
-            __builtin_amdgcn_sched_barrier(0);
-            if (d < ND - 1) A[d + 1][t] = NAR_A(P[d + 1][t]);
-            if (d < ND - 2) P[d + 2][t] = NAR_LOOKUP(wd[d + 2], t);
-            if (t == 0) nonzero = __builtin_amdgcn_msad_u8(wd[d] ^ 0x01010101u, wd[d], nonzero);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
 template <int R, bool ALIGNED>
 __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q, int64_t n, int64_t stride, int32_t li, int32_t k,
                                                    MpbDevParams prm, const double2 *__restrict__ lut_g,
@@ -2103,8 +2115,7 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
     __shared__ __attribute__((aligned(128))) uint8_t s_tile[4][MPB_NRS_TILE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    s_p[tid] = tid == 255 ? make_double2(__builtin_nan(""), __builtin_nan("")) : lut_g[tid];
-    __syncthreads();                                          // the only block barrier
+    nar_stage_table(s_p, lut_g, tid);
     const int64_t rows_sb = 64 * (int64_t)k;                  // reads of a stream block: 64 lanes x k reads each
     const int64_t nsb = (n + rows_sb - 1) / rows_sb;
     const int KB = __builtin_amdgcn_readfirstlane((int)(k * stride));      // bytes of a lane's stream: a multiple of 128
@@ -2119,13 +2130,10 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
     int32_t *const my_seg = seg + rows_sb * (gw * (nsb / W) + min(gw, nsb % W));
     int nlist = 0;                                            // wave-uniform
     uint8_t *const tile = s_tile[w];
-    // loading: lane (r8, c8) of instruction j holds the 16-byte slot c8 of panel bytes of stream 8 j + r8
-    const int r8 = lane >> 3, c8 = lane & 7;
+    const int r8 = lane >> 3, c8 = lane & 7;                  // stream 8 j + r8 of load instruction j: the lane's slot c8 of panel bytes
     const int voff = r8 * KB + c8 * 16;
-    // its place in the tile: stream * 128 + ((slot ^ ((stream >> 1) & 7)) * 16); (8 j + r8) >> 1 & 7 = 4 (j & 1) + (r8 >> 1)
-    const int wr_even = r8 * 128 + ((c8 ^ (r8 >> 1)) << 4), wr_odd = r8 * 128 + ((c8 ^ (4 + (r8 >> 1))) << 4);
-    // reading: lane = stream; slot c at x0 ^ (c << 4)
-    const int x0 = lane * 128 + (((lane >> 1) & 7) << 4);
+    int wr_even, wr_odd, x0;
+    nar_tile_lane(lane, wr_even, wr_odd, x0);
 
     u32x4 pre[8];
     auto load_panel = [&](const int64_t sb, const int pk) {
@@ -2147,15 +2155,11 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
     double v[R];
 #pragma unroll
     for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-    const double thr = prm.thr;
-    uint32_t nonzero = 0;                                      // as k_narrow: the bytes that are NOT zero, four per instruction
+    uint32_t nonzero = 0;
     int u = 0, sread = 0;                                      // position in the stream: byte u of its read number sread (wave-uniform)
 
-    // ---- a read is done: cdf_cross, read_result ----
-    // `nonzero` has counted the non-zero bytes of the read's chunks; the bytes of its last chunk past its end were made zero
-    // before they were looked up (the identity step) and so count as 'N' here: 'N' bases = li - nonzero.
-    // (two reads per lane, result arrays aligned for a lane's pair: see finish; R <= 3 only: with four rows the held results do
-    // not fit the 128 registers of four waves per SIMD)
+    // ---- a read is done: nar_finish.  Two reads per lane: result arrays aligned for a lane's pair (R <= 3 only: with four rows the
+    // held results do not fit the 128 registers of four waves per SIMD)
     const bool pair_stores = R <= 3 && k == 2 && (((uintptr_t)ee & 15) | ((uintptr_t)ns & 7) | ((uintptr_t)pass & 1)) == 0;
     double held_e = 0.0;
     int held_ns = 0;
@@ -2163,14 +2167,11 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
     bool held_ok = false;
     auto finish = [&](const int64_t sb, const int sr) {
         const int64_t i = sb * rows_sb + (int64_t)lane * k + sr;
-        const bool valid = i < n;
-        double lo = 0.0, hi = 0.0;
-        const int js = cdf_cross(v, 0.0, thr, 0, lo, hi);
-        const bool done = valid && js >= 0;
-        if (done) {
-            const int nsv = li - (int)nonzero;                           // 'N' bases (a read with an 'n' never gets here)
-            double e;
-            const uint8_t ps = (uint8_t)(read_result(prm, true, js, lo, hi, nsv, nsv > 0, li, e) ? 1 : 0);
+        const NarRead r = nar_finish(v, nonzero, prm, i < n, i < n, li, i, my_seg, nlist, lane);
+        if (r.done) {
+            const double e = r.e;
+            const int nsv = r.nsv;
+            const uint8_t ps = (uint8_t)(r.keep ? 1 : 0);
             if (pair_stores && sr == 0) {
                 // two reads per lane: the first one's results wait in registers for the second's, and go out together -- 16 + 8 + 2
                 // contiguous bytes per lane instead of two half-used sectors a panel and a half apart (writes 0.26 -> 0.13 GB)
@@ -2186,34 +2187,21 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
             }
         }
         if (pair_stores) {
-            if (sr == 0) held_ok = done;
-            else if (held_ok && !done) { ee[i - 1] = held_e; ns[i - 1] = held_ns; pass[i - 1] = held_ps; }   // the second one is handed back (or past the end)
+            if (sr == 0) held_ok = r.done;
+            else if (held_ok && !r.done) { ee[i - 1] = held_e; ns[i - 1] = held_ns; pass[i - 1] = held_ps; }   // the second one is handed back (or past the end)
         }
-        const unsigned long long todo = __ballot(valid && js < 0);
-        if (todo) {
-            if (valid && js < 0) my_seg[nlist + __popcll(todo & ((1ull << lane) - 1ull))] = (int32_t)i;
-            nlist += __popcll(todo);
-        }
-#pragma unroll
-        for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-        nonzero = 0;
     };
     for (int64_t t = 0; t < total; t++) {
         // the panel requested one panel ago -> tile (the tile's last reads were issued before: LDS runs a wave's operations in order)
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            *reinterpret_cast<u32x4 *>(tile + j * 1024 + ((j & 1) ? wr_odd : wr_even)) = pre[j];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        nar_tile_write(tile, wr_even, wr_odd, pre);
+        nar_tile_fence();
         if (t + 1 < total) {                                    // in flight while this panel is computed on
             load_panel(pf_sb, pf_pk);
             if (++pf_pk == NP) { pf_pk = 0; pf_sb += W; }
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- the panel's two 64-byte halves, four 16-byte chunks each.  The chunks of a half that belong to ONE read go through
-        // one straight-line run (nar_run<R, 4 x chunks>); the bytes of a read's last chunk past its end are made zero first (the
-        // identity step), so a 300-base read's last 44 bases take the same code as the others, as 48.  A read may end -- and the
+        // one run (nar_chunks), so a 300-base read's last 44 bases take the same code as the others, as 48.  A read may end -- and the
         // next one begin -- anywhere a chunk does (strides that are no multiple of 64): then the half is several runs; row
         // padding is skipped by whole chunks.  All of it wave-uniform.
 #pragma unroll
@@ -2223,24 +2211,7 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
                 // address a constant (the form measured in profiles/r05_narrow_variants.txt; the loop below costs it 2-3 %)
                 const int nb = li - u;                          // bases of the current read from this half on
                 if (nb > 0) {
-                    const int nch = nb >= 64 ? 4 : (nb + 15) >> 4;
-                    uint32_t wd[16];
-#define NRS_LOADA(NC)                                                                                        \
-                    _Pragma("unroll") for (int c = 0; c < NC; c++) {                                         \
-                        const u32x4 x = *reinterpret_cast<const u32x4 *>(tile + (x0 ^ ((h * 4 + c) << 4)));  \
-                        wd[4 * c] = x.x; wd[4 * c + 1] = x.y; wd[4 * c + 2] = x.z; wd[4 * c + 3] = x.w;       \
-                    }                                                                                        \
-                    if (nb < 16 * NC) {                                                                      \
-                        _Pragma("unroll") for (int d = 0; d < 4; d++)                                        \
-                            wd[4 * (NC - 1) + d] = mask_dword(wd[4 * (NC - 1) + d], nb - 16 * (NC - 1) - 4 * d); \
-                    }
-                    switch (nch) {
-                    case 4: { NRS_LOADA(4) nar_run<R, 16>(v, nonzero, s_p, wd); break; }
-                    case 3: { NRS_LOADA(3) nar_run<R, 12>(v, nonzero, s_p, wd); break; }
-                    case 2: { NRS_LOADA(2) nar_run<R, 8>(v, nonzero, s_p, wd); break; }
-                    default: { NRS_LOADA(1) nar_run<R, 4>(v, nonzero, s_p, wd); break; }
-                    }
-#undef NRS_LOADA
+                    nar_chunks<R, true>(v, nonzero, s_p, [&](const int c) { return tile + (x0 ^ ((h * 4 + c) << 4)); }, nb >= 64 ? 4 : (nb + 15) >> 4, nb >> 4, nb);
                     if (nb <= 64) finish(cur_sb, sread);
                 }
                 u += 64;
@@ -2257,23 +2228,7 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
                 } else {
                     const int nch = min((nb + 15) >> 4, 4 - p); // chunks of this read in what is left of the half
                     const int c0 = h * 4 + p;
-                    uint32_t wd[16];
-#define NRS_LOAD(NC)                                                                                         \
-                    _Pragma("unroll") for (int c = 0; c < NC; c++) {                                         \
-                        const u32x4 x = *reinterpret_cast<const u32x4 *>(tile + (x0 ^ ((c0 + c) << 4)));     \
-                        wd[4 * c] = x.x; wd[4 * c + 1] = x.y; wd[4 * c + 2] = x.z; wd[4 * c + 3] = x.w;       \
-                    }                                                                                        \
-                    if (nb < 16 * NC) {                                                                      \
-                        _Pragma("unroll") for (int d = 0; d < 4; d++)                                        \
-                            wd[4 * (NC - 1) + d] = mask_dword(wd[4 * (NC - 1) + d], nb - 16 * (NC - 1) - 4 * d); \
-                    }
-                    switch (nch) {
-                    case 4: { NRS_LOAD(4) nar_run<R, 16>(v, nonzero, s_p, wd); break; }
-                    case 3: { NRS_LOAD(3) nar_run<R, 12>(v, nonzero, s_p, wd); break; }
-                    case 2: { NRS_LOAD(2) nar_run<R, 8>(v, nonzero, s_p, wd); break; }
-                    default: { NRS_LOAD(1) nar_run<R, 4>(v, nonzero, s_p, wd); break; }
-                    }
-#undef NRS_LOAD
+                    nar_chunks<R, true>(v, nonzero, s_p, [&](const int c) { return tile + (x0 ^ ((c0 + c) << 4)); }, nch, nb >> 4, nb);
                     p += nch;
                     u += 16 * nch;
                     if (16 * nch >= nb) finish(cur_sb, sread);  // the read is done (u may stand in its padding now)
@@ -2282,9 +2237,7 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
             }
         }
         if (++cur_pk == NP) { cur_pk = 0; cur_sb += W; sread = 0; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the tile is overwritten by the next panel
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        nar_tile_fence();                                       // the tile is overwritten by the next panel
     }
     if (lane == 0) wave_count[gw] = nlist;
 }
@@ -2517,8 +2470,7 @@ __global__ __launch_bounds__(256, 4) void k_narrow_rg(const uint8_t *__restrict_
     __shared__ uint32_t s_row[4][64];                         // byte offsets of the rows of the group being loaded, from its window's base
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    s_p[tid] = tid == 255 ? make_double2(__builtin_nan(""), __builtin_nan("")) : lut_g[tid];
-    __syncthreads();                                          // the only block barrier
+    nar_stage_table(s_p, lut_g, tid);
     const int gw = blockIdx.x * 4 + w;
     const int ngroups = (int)((n + 63) >> 6), nwin = (int)((n + MPB_RG_WIN - 1) / MPB_RG_WIN), nwaves = (int)gridDim.x * 4;
     const int g0 = __builtin_amdgcn_readfirstlane(rg_first_group(wpre, gpre, nwin, ngroups, gw, nwaves, lane));
@@ -2532,10 +2484,9 @@ __global__ __launch_bounds__(256, 4) void k_narrow_rg(const uint8_t *__restrict_
     int nlist = 0;                                            // wave-uniform
     uint8_t *const tile = s_tile[w];
     const int istride = __builtin_amdgcn_readfirstlane((int)stride);
-    // loading: lane (r8, c8) of instruction j holds the 16-byte slot c8 of the panel of stream 8 j + r8; tile layout as k_narrow_rs
-    const int r8 = lane >> 3, c8 = lane & 7;
-    const int wr_even = r8 * 128 + ((c8 ^ (r8 >> 1)) << 4), wr_odd = r8 * 128 + ((c8 ^ (4 + (r8 >> 1))) << 4);
-    const int x0 = lane * 128 + (((lane >> 1) & 7) << 4);
+    const int r8 = lane >> 3, c8 = lane & 7;                  // stream 8 j + r8 of load instruction j: the lane's row
+    int wr_even, wr_odd, x0;
+    nar_tile_lane(lane, wr_even, wr_odd, x0);
 
     // a group's order entries {read, length}: -1 / -1 past the batch or past the wave's range; length -1: outside 0..max_len
     auto fetch = [&](const int g, int &idx, int &ln) {
@@ -2584,18 +2535,13 @@ __global__ __launch_bounds__(256, 4) void k_narrow_rg(const uint8_t *__restrict_
     double v[R];
 #pragma unroll
     for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-    const double thr = prm.thr;
     uint32_t nonzero = 0;
 
     for (int g = g0; g < g1; g++) {
         const int np = __builtin_amdgcn_readfirstlane(max(1, (cur_maxc + 7) >> 3));      // panels of this group
         for (int pk = 0; pk < np; pk++) {
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                *reinterpret_cast<u32x4 *>(tile + j * 1024 + ((j & 1) ? wr_odd : wr_even)) = pre[j];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            nar_tile_write(tile, wr_even, wr_odd, pre);
+            nar_tile_fence();
             {
                 int next_pk = pk + 1;
                 const bool next_group = next_pk == np && g + 1 < g1;
@@ -2610,51 +2556,28 @@ __global__ __launch_bounds__(256, 4) void k_narrow_rg(const uint8_t *__restrict_
                 if (rem <= 0) continue;
                 const int fullc = cur_full - cb;                 // ... that are complete in every lane
                 const int nbl = cur_len - 16 * cb;               // this lane's bases from here on (may be <= 0)
-                uint32_t wd[16];
-#define NRG_LOAD(NC)                                                                                         \
-                _Pragma("unroll") for (int c = 0; c < NC; c++) {                                             \
-                    const u32x4 x = *reinterpret_cast<const u32x4 *>(tile + (x0 ^ ((h * 4 + c) << 4)));      \
-                    wd[4 * c] = x.x; wd[4 * c + 1] = x.y; wd[4 * c + 2] = x.z; wd[4 * c + 3] = x.w;           \
-                    if (c >= fullc) {                                                                        \
-                        _Pragma("unroll") for (int d = 0; d < 4; d++)                                        \
-                            wd[4 * c + d] = mask_dword(wd[4 * c + d], nbl - 16 * c - 4 * d);                 \
-                    }                                                                                        \
-                }
+                const auto chunk = [&](const int c) { return tile + (x0 ^ ((h * 4 + c) << 4)); };
                 if (RLO < R && cur_maxc <= split) {               // a short group: rows 0 .. RLO-1 only (v[RLO ..] stay zero)
                     double (&vl)[RLO] = *reinterpret_cast<double (*)[RLO]>(&v[0]);
-                    switch (rem >= 4 ? 4 : rem) {
-                    case 4: { NRG_LOAD(4) nar_run<RLO, 16>(vl, nonzero, s_p, wd); break; }
-                    case 3: { NRG_LOAD(3) nar_run<RLO, 12>(vl, nonzero, s_p, wd); break; }
-                    case 2: { NRG_LOAD(2) nar_run<RLO, 8>(vl, nonzero, s_p, wd); break; }
-                    default: { NRG_LOAD(1) nar_run<RLO, 4>(vl, nonzero, s_p, wd); break; }
-                    }
+                    nar_chunks<RLO, false>(vl, nonzero, s_p, chunk, rem >= 4 ? 4 : rem, fullc, nbl);
                 } else {
-                    switch (rem >= 4 ? 4 : rem) {
-                    case 4: { NRG_LOAD(4) nar_run<R, 16>(v, nonzero, s_p, wd); break; }
-                    case 3: { NRG_LOAD(3) nar_run<R, 12>(v, nonzero, s_p, wd); break; }
-                    case 2: { NRG_LOAD(2) nar_run<R, 8>(v, nonzero, s_p, wd); break; }
-                    default: { NRG_LOAD(1) nar_run<R, 4>(v, nonzero, s_p, wd); break; }
-                    }
+                    nar_chunks<R, false>(v, nonzero, s_p, chunk, rem >= 4 ? 4 : rem, fullc, nbl);
                 }
-#undef NRG_LOAD
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the tile is overwritten by the next panel
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            nar_tile_fence();                                   // the tile is overwritten by the next panel
         }
-        // ---- the group is done: the crossing (cdf_cross, written out), read_result ----
+        // ---- the group is done: nar_finish written out, with the lane's own length (and a length outside 0..max_len is handed back).
+        // This kernel sits at its register cap: through the helper it needs a VGPR more at R = 2 and 4 more bytes of spill at R = 3, 4.
         {
             const int64_t i = cur_idx;
             const int li = cur_len;
             const bool valid = cur_idx >= 0, good = valid && li >= 0;
-            // cdf_cross's loop, written out here: this kernel sits at its register cap, and the call (whatever its form) lets the
-            // compiler fold the crossing into `done` differently -- 3 more VGPRs spilled, reloaded inside the panel loop (R = 4: 1.5 %)
             double acc = 0.0, lo = 0.0, hi = 0.0;
             int js = -1;
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 const double na = acc + v[r];
-                const bool hit = (js < 0) && (na > thr);
+                const bool hit = (js < 0) && (na > prm.thr);
                 lo = hit ? acc : lo;
                 hi = hit ? na : hi;
                 js = hit ? r : js;
@@ -3017,16 +2940,11 @@ void mpb_launch_serve(const MpbServeBox &box, const double2 *lut, uint32_t gener
 }
 
 // ---- natural-order narrow pass ----------------------------------------------------------------------------------------
-int mpb_narrow_lds_bytes()
-{
-    return 256 * (int)sizeof(nar_entry_t) + MPB_NAR_DEPTH * 4 * MPB_NAR_PANEL + 32;
-}
-
 // k_narrow_rs (register-staged, whole lines): reads per lane, 0: not this form.  Rows of a multiple of 64 bytes: always (a read
 // starts with a half panel: one run per half).  Other strides: a lane's reads begin anywhere a 16-byte chunk does and a half may
 // be several runs -- measured at stride 304 (profiles/r05_narrow_variants.txt): 7 % faster than the ring at R = 2 (and 3.04
 // instead of 4.2 GB read), 4-5 % slower at R = 3, 4: so only for two rows.
-int mpb_narrow_rs_reads_per_lane(int64_t stride, int rows0)
+static int nar_rs_reads_per_lane(int64_t stride, int rows0)
 {
     if (stride % 16 != 0 || stride > (1 << 16)) return 0;
     if (stride % 64 != 0 && rows0 != 2) return 0;
@@ -3035,90 +2953,72 @@ int mpb_narrow_rs_reads_per_lane(int64_t stride, int rows0)
     return k;
 }
 
-int mpb_narrow_rs_lds_bytes()
-{
-    return 256 * (int)sizeof(nar_entry_t) + 4 * MPB_NRS_TILE;
-}
-
-void mpb_launch_narrow(int rows0, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const MpbDevParams &prm,
-                       const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int32_t *list, int grid_blocks, hipStream_t s)
-{
-    const int rs_k = mpb_narrow_rs_reads_per_lane(stride, rows0);
-    const int per_blk = 64 * (rs_k ? rs_k : 1);              // reads of one row block / stream block
-    const int64_t nblk = (n + per_blk - 1) / per_blk;
-    int64_t blocks = (nblk + 3) / 4;
-    if (blocks > grid_blocks) blocks = grid_blocks;         // persistent: a wave walks row blocks gw, gw + W, ...
-    if (blocks > MPB_NAR_MAX_WAVES / 4) blocks = MPB_NAR_MAX_WAVES / 4;
-    if (blocks < 1) blocks = 1;
-    const int nwaves = (int)blocks * 4;
-#define MPB_NAR_LAUNCH(RR) hipLaunchKernelGGL((k_narrow<RR, MPB_NAR_DEPTH>), dim3((unsigned)blocks), dim3(256), 0, s, q, n, stride, fixed_len, prm, ws.lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count)
-#define MPB_NRS_LAUNCH(RR) hipLaunchKernelGGL((k_narrow_rs<RR, true>), dim3((unsigned)blocks), dim3(256), 0, s, q, n, stride, fixed_len, rs_k, prm, ws.lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count)
-    if (rs_k && stride % 64 != 0) {                        // (two rows only: mpb_narrow_rs_reads_per_lane)
-        hipLaunchKernelGGL((k_narrow_rs<2, false>), dim3((unsigned)blocks), dim3(256), 0, s, q, n, stride, fixed_len, rs_k, prm, ws.lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count);
-    } else if (rs_k) {
-        switch (rows0) {
-        case 2: MPB_NRS_LAUNCH(2); break;
-        case 3: MPB_NRS_LAUNCH(3); break;
-        default: MPB_NRS_LAUNCH(4); break;
-        }
-    } else {
-        switch (rows0) {
-        case 2: MPB_NAR_LAUNCH(2); break;
-        case 3: MPB_NAR_LAUNCH(3); break;
-        default: MPB_NAR_LAUNCH(4); break;
-        }
-    }
-#undef MPB_NRS_LAUNCH
-#undef MPB_NAR_LAUNCH
-    hipLaunchKernelGGL(k_nar_compact, dim3((unsigned)nwaves), dim3(256), 0, s, ws.nar_seg, ws.nar_wave_count, nblk, nwaves, per_blk, (const int32_t *)nullptr, list, ws.nar_count);
-}
-
-// ragged batches (k_narrow_rg): sort windows by length, cut the groups into one range per wave, walk them
-int mpb_narrow_rg_key_shift(int64_t stride)
+// ragged batches: sort windows by length, cut the groups into one range per wave, walk them
+static int mpb_narrow_rg_key_shift(int64_t stride)
 {
     int ks = 0;                                              // ceil(len / 16) <= stride / 16; the key must stay below MPB_RG_BINS
     while (((stride >> 4) >> ks) >= MPB_RG_BINS) ks++;
     return ks;
 }
 
-void mpb_launch_narrow_ragged(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, const int32_t *len,
-                              const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int32_t *list,
-                              int grid_blocks, hipStream_t s)
+// k_narrow_rg<R, RLO> by form: [0..2] R = 2..4 rows everywhere, [3..4] R = 3, 4 with mixed rows (RLO = R - 1)
+static decltype(&k_narrow_rg<2, 2>) const nar_rg_forms[MPB_NRG_FORMS] = {k_narrow_rg<2, 2>, k_narrow_rg<3, 3>, k_narrow_rg<4, 4>,
+                                                                          k_narrow_rg<3, 2>, k_narrow_rg<4, 3>};
+
+void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS])
 {
-    const int64_t ngroups = (n + 63) / 64, nwin = (n + MPB_RG_WIN - 1) / MPB_RG_WIN;
-    int64_t blocks = (ngroups + 3) / 4;
-    // persistent, and every wave's range is fixed before the launch: the grid must be resident at once, so it is sized by what
-    // the runtime says fits a CU (registers as well as LDS), never by more than the caller's LDS-only figure
-    static int per_cu[5] = {0, 0, 0, 0, 0};
-    const int ri = rows0 < 2 ? 2 : rows0 > 4 ? 4 : rows0;
-    if (!per_cu[ri]) {
+    for (int f = 0; f < MPB_NRG_FORMS; f++) {
         int nb = 0;
-        const void *fn = ri == 2 ? (const void *)k_narrow_rg<2, 2> : ri == 3 ? (const void *)k_narrow_rg<3, 2> : (const void *)k_narrow_rg<4, 3>;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
-        per_cu[ri] = nb;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)nar_rg_forms[f], 256, 0) != hipSuccess || nb < 1) {
+            (void)hipGetLastError();
+            nb = 1;
+        }
+        per_cu[f] = nb;
     }
-    {
-        int dev = 0, n_cu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-        if ((int64_t)n_cu * per_cu[ri] < grid_blocks) grid_blocks = n_cu * per_cu[ri];
-    }
-    if (blocks > grid_blocks) blocks = grid_blocks;          // a wave walks a contiguous range of groups
+}
+
+void mpb_launch_narrow(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len,
+                       const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int n_cu,
+                       const int *rg_per_cu, hipStream_t s)
+{
+    const int ri = rows0 <= 2 ? 0 : rows0 == 3 ? 1 : 2;
+    const bool mixed = len && split_chunks > 0 && rows0 >= 3;          // short groups with a row less (k_narrow_rg<R, R - 1>)
+    const int rg = mixed ? ri + 2 : ri;
+    const int rs_k = len ? 0 : nar_rs_reads_per_lane(stride, rows0);
+    // persistent grid: as many workgroups as fit the CUs' LDS at once.  The ragged pass fixes every wave's range before the
+    // launch, so its grid must be resident at once: never more than the runtime says fits a CU (registers as well as LDS).
+    const int lds = len || rs_k ? 256 * (int)sizeof(nar_entry_t) + 4 * MPB_NRS_TILE
+                                : 256 * (int)sizeof(nar_entry_t) + MPB_NAR_DEPTH * 4 * MPB_NAR_PANEL + 32;
+    int per_cu = (160 * 1024) / lds;
+    if (len && rg_per_cu[rg] < per_cu) per_cu = rg_per_cu[rg];
+    const int per_blk = 64 * (rs_k ? rs_k : 1);              // reads of one row block / stream block / group
+    const int64_t nblk = (n + per_blk - 1) / per_blk;
+    int64_t blocks = (nblk + 3) / 4;
+    if (blocks > (int64_t)n_cu * per_cu) blocks = (int64_t)n_cu * per_cu;
     if (blocks > MPB_NAR_MAX_WAVES / 4) blocks = MPB_NAR_MAX_WAVES / 4;
     if (blocks < 1) blocks = 1;
     const int nwaves = (int)blocks * 4;
-    // (what a short group costs against a full one, from the pure kernels' times at R - 1 and R: 0.86 at 2 / 3, 0.80 at 3 / 4)
-    hipLaunchKernelGGL(k_rag_sort, dim3((unsigned)nwin), dim3(256), 0, s, len, n, prm.max_len, mpb_narrow_rg_key_shift(stride),
-                       split_chunks > 0 && rows0 >= 3 ? split_chunks : -1, rows0 >= 4 ? 80 : 86, ws.rg_ord, ws.rg_gpre, ws.rg_wsum);
-    hipLaunchKernelGGL(k_rag_scan, dim3(1), dim3(1024), 0, s, ws.rg_wsum, (int)nwin, ws.rg_wpre);
-#define MPB_NRG_LAUNCH(RR, RL) hipLaunchKernelGGL((k_narrow_rg<RR, RL>), dim3((unsigned)blocks), dim3(256), 0, s, q, n, stride, ws.rg_ord, ws.rg_wpre, ws.rg_gpre, ws.rg_gstart, split_chunks, prm, ws.lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count)
-    const bool mixed = split_chunks > 0 && rows0 >= 3;       // short groups with a row less (k_narrow_rg<R, R - 1>)
-    switch (rows0) {
-    case 2: MPB_NRG_LAUNCH(2, 2); break;
-    case 3: if (mixed) MPB_NRG_LAUNCH(3, 2); else MPB_NRG_LAUNCH(3, 3); break;
-    default: if (mixed) MPB_NRG_LAUNCH(4, 3); else MPB_NRG_LAUNCH(4, 4); break;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (len) {
+        const int64_t nwin = (n + MPB_RG_WIN - 1) / MPB_RG_WIN;
+        // (what a short group costs against a full one, from the pure kernels' times at R - 1 and R: 0.86 at 2 / 3, 0.80 at 3 / 4)
+        hipLaunchKernelGGL(k_rag_sort, dim3((unsigned)nwin), dim3(256), 0, s, len, n, prm.max_len, mpb_narrow_rg_key_shift(stride),
+                           mixed ? split_chunks : -1, rows0 >= 4 ? 80 : 86, ws.rg_ord, ws.rg_gpre, ws.rg_wsum);
+        hipLaunchKernelGGL(k_rag_scan, dim3(1), dim3(1024), 0, s, ws.rg_wsum, (int)nwin, ws.rg_wpre);
+        hipLaunchKernelGGL(nar_rg_forms[rg], grid, block, 0, s, q, n, stride, ws.rg_ord, ws.rg_wpre, ws.rg_gpre, ws.rg_gstart,
+                           split_chunks, prm, ws.lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count);
+    } else if (rs_k) {
+        static decltype(&k_narrow_rs<2, true>) const forms[4] = {k_narrow_rs<2, true>, k_narrow_rs<3, true>, k_narrow_rs<4, true>,
+                                                                 k_narrow_rs<2, false>};     // (rows of no multiple of 64: two rows only)
+        hipLaunchKernelGGL(forms[stride % 64 != 0 ? 3 : ri], grid, block, 0, s, q, n, stride, fixed_len, rs_k, prm, ws.lut, ee, ns, pass,
+                           ws.nar_seg, ws.nar_wave_count);
+    } else {
+        static decltype(&k_narrow<2, MPB_NAR_DEPTH>) const forms[3] = {k_narrow<2, MPB_NAR_DEPTH>, k_narrow<3, MPB_NAR_DEPTH>,
+                                                                       k_narrow<4, MPB_NAR_DEPTH>};
+        hipLaunchKernelGGL(forms[ri], grid, block, 0, s, q, n, stride, fixed_len, prm, ws.lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count);
     }
-#undef MPB_NRG_LAUNCH
-    hipLaunchKernelGGL(k_nar_compact, dim3((unsigned)nwaves), dim3(256), 0, s, ws.nar_seg, ws.nar_wave_count, (int64_t)0, nwaves, 64, ws.rg_gstart, list, ws.nar_count);
+    hipLaunchKernelGGL(k_nar_compact, dim3((unsigned)nwaves), dim3(256), 0, s, ws.nar_seg, ws.nar_wave_count, nblk, nwaves, per_blk,
+                       len ? (const int32_t *)ws.rg_gstart : nullptr, ws.nar_list, ws.nar_count);
 }
 
 void mpb_launch_sample(const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len, const MpbDevParams &prm,

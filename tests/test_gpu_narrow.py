@@ -187,6 +187,50 @@ def test_a_stale_choice_costs_time_not_results(eng, oracle):
             b.free()
 
 
+def test_the_class_getters_answer_for_the_last_batch_as_a_whole(eng, oracle):
+    """mpb_last_class_histogram / mpb_last_read_budgets describe the last batch the sorted pipeline classified as a whole.  A narrow
+    call that hands back a sub-batch leaves them nothing to describe (refused); a classified-at-source batch after it, or the whole
+    batch taken by the sorted pipeline after a stale choice, is described again -- the counts of that batch, summing to n."""
+    n, stride, L = 300_064, 320, 300            # (a shape of its own: no choice of an earlier test is reused)
+    d_q, d_ee, d_ns, d_pass = eng.alloc(n * stride), eng.alloc(n * 8), eng.alloc(n * 4), eng.alloc(n)
+    m, ts = 5000, 128
+    rng = np.random.default_rng(12)
+    seq = rng.choice(np.frombuffer(b"ACGTN", np.uint8), (m, ts), p=[0.24, 0.24, 0.24, 0.24, 0.04])
+    qual = (rng.integers(0, 42, (m, ts)) + 33).astype(np.uint8)
+    d_seq, d_qual, d_out = eng.alloc(m * ts).upload(seq), eng.alloc(m * ts).upload(qual), eng.alloc(m * ts)
+    try:
+        eng.synth_fill(d_q, n, stride, fixed_len=L, seed=41, profile=0)            # BASELINE's model: many reads handed back
+        eng.filter_device(d_q, n, stride, fixed_len=L, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass, params=eng.params(narrow_rows=3))
+        p = eng.last_path()
+        assert p["narrow_rows"] == 3 and 0 < p["n_fallback"] < n, p
+        with pytest.raises(ValueError, match="narrow pass"):
+            eng.class_histogram()
+        with pytest.raises(ValueError, match="narrow pass"):
+            eng.read_budgets(10)
+        # classified at source: the decode pass classifies, the filter starts at the scan
+        eng.filter_ascii_device(d_seq, d_qual, m, ts, d_out, fixed_len=100, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass)
+        hist = eng.class_histogram()
+        assert sum(hist.values()) == m
+        budgets = eng.read_budgets(m)
+        eng.filter_device(d_out, m, ts, fixed_len=100, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass, params=eng.params(no_narrow=True))
+        assert eng.class_histogram() == hist and np.array_equal(eng.read_budgets(m), budgets)
+        # a stale choice: the clean batch chooses the pass, the same shape of BASELINE's model falls back as a whole
+        eng.synth_fill(d_q, n, stride, fixed_len=L, seed=41, profile=1)
+        eng.filter_device(d_q, n, stride, fixed_len=L, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass)
+        assert eng.last_path()["narrow_rows"] == 2
+        eng.synth_fill(d_q, n, stride, fixed_len=L, seed=41, profile=0)
+        eng.filter_device(d_q, n, stride, fixed_len=L, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass)
+        p = eng.last_path()
+        assert p["narrow_rows"] == 2 and p["n_fallback"] == n, p
+        hist = eng.class_histogram()
+        assert sum(hist.values()) == n
+        eng.filter_device(d_q, n, stride, fixed_len=L, d_ee=d_ee, d_ns=d_ns, d_pass=d_pass, params=eng.params(no_narrow=True))
+        assert eng.class_histogram() == hist
+    finally:
+        for b in (d_q, d_ee, d_ns, d_pass, d_seq, d_qual, d_out):
+            b.free()
+
+
 def test_high_quality_full_size(eng, oracle):
     """bench.py's extras.high_quality_300 at its size: 10 M x 300 bp of the clean profile, resident, the pass chosen by the
     library; every read compared with the oracle."""

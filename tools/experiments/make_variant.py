@@ -27,7 +27,7 @@ VARIANTS = {
         ("typedef double2 nar_entry_t;\n#define NAR_P(e) ((e).y)\n#define NAR_A(e) ((e).x)\n",
          "typedef double nar_entry_t;\n#define NAR_P(e) (e)\n#define NAR_A(e) (1.0 - (e))\n"),
         ("s_p[tid] = tid == 255 ? make_double2(__builtin_nan(\"\"), __builtin_nan(\"\")) : lut_g[tid];",
-         "s_p[tid] = tid == 255 ? __builtin_nan(\"\") : lut_g[tid].y;", 3),
+         "s_p[tid] = tid == 255 ? __builtin_nan(\"\") : lut_g[tid].y;"),
     ],
     # k_narrow_rs (rows of a multiple of 64 bytes): the two halves of a panel as CHAINED runs -- half 0's run looks up the first
     # eight bases of half 1 in its tail, half 1's run starts without waiting for the LDS.  Bit-exact; a unified diff.
