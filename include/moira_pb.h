@@ -67,6 +67,26 @@ extern "C" {
                                     band below keeps every pass/fail flag EQUAL to the exact computation's: a read
                                     whose ee lands within 1e-9 relative of the threshold (or of an integer with
                                     MPB_FLAG_ROUND) is recomputed with the three-rounding arithmetic.  Off by default. */
+#define MPB_FLAG_ODDS      128u  /* opt-in: the MAIN PASS of the sorted pipeline may run ONE fma per DP cell.  It factors
+                                    prod (a_k + b_k x) = (prod a_k) * prod (1 + r_k x), r_k = p_k / (1 - p_k): the registers hold
+                                    the coefficients w of the second product (w[j] += r_k * w[j-1], w[0] == 1), P0 = prod a_k is
+                                    the reference's row 0 bit for bit, and row j of its table is P0 * w[j] (ODDS_MODE.md).
+                                    Contract: ee within 1e-9 relative of the bit-exact result; ns identical; pass identical for
+                                    every read; a read without a result (NaN) stays one.  The flag PERMITS the cheaper
+                                    arithmetic, it never requires it: every read the mode cannot vouch for is recomputed by the
+                                    three-rounding code, and mpb_filter_counts.n_overflow counts those reads too (as it does
+                                    for MPB_FLAG_FAST_FMA).  They are: a read whose P0 is not >= 2^-900 (every w[j] <= 1 / P0,
+                                    so above that nothing has overflowed; long reads of poor quality); a read whose ee lands
+                                    within 1e-9 relative of its limit, or of an integer with MPB_FLAG_ROUND; a read whose CDF
+                                    does not cross inside its class's rows; wide reads (more than 1024 rows); every read of a
+                                    call that runs on a private table (scores above 254) or takes the one-read-per-wave path
+                                    (mpb_filter_host: at most 4096 reads without MPB_FLAG_BATCHED_ONLY).  A call with the flag takes the sorted
+                                    pipeline, never the narrow pass.  The error grows like 1/alpha, as MPB_FLAG_FAST_FMA's does
+                                    (worst relative difference of a numpy model over 1500 reads of 300 bases: 1.4e-12 at alpha
+                                    1e-4, 1.3e-11 at 1e-5, 1.0e-10 at 1e-6; at most 5e-13 on the golden sets at alpha 0.005 ..
+                                    0.5), so the flag is ACCEPTED ONLY FOR alpha >= 1e-5 (MPB_E_INVALID below), a factor of
+                                    about 70 under the contract.  Not together with MPB_FLAG_FAST_FMA (MPB_E_INVALID); combines
+                                    with ROUND, DECISION_ONLY, COUNT_CELLS, TEST_UNDERPREDICT, NO_NARROW.  Off by default. */
 #define MPB_FLAG_DECISION_ONLY 8u /* opt-in, NOT the reference's contract: a read whose expected errors are
                                     PROVABLY above the threshold (multiplicative Chernoff lower-tail bound on the
                                     Poisson-binomial quantile, from the prepass' mean) is reported pass = 0,

@@ -15,6 +15,7 @@ OK, E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_RANGE = 0, -1, -2, -3, -4, -5
 AMBIG = {"treat_as_errors": 0, "ignore": 1, "disallow": 2}
 FLAG_ROUND, FLAG_FAST_FMA, FLAG_TEST_UNDERPREDICT, FLAG_DECISION_ONLY, FLAG_BATCHED_ONLY, FLAG_COUNT_CELLS = 1, 2, 4, 8, 16, 32
 FLAG_NO_NARROW = 64
+FLAG_ODDS = 128                # MPB_FLAG_ODDS: one fma per DP cell in the sorted pipeline's main pass (ODDS_MODE.md)
 
 
 def FLAG_NARROW_ROWS(r):

@@ -68,6 +68,7 @@ struct mpb_ctx {
     HostSlot slot[MPB_HOST_SLOTS];
     int copy_threads = 1;
     double2 *d_lut = nullptr;
+    double2 *d_lut_odds = nullptr;       // {1-p, p / (1-p)}: the table of MPB_FLAG_ODDS' main pass (k_dp_odds)
     double2 *d_lut_private = nullptr;    // one call's table when a read carries qualities above 254 (mpb_calculate_errors_PB)
     // workspace, grown on demand
     int64_t ws_cap = 0;
@@ -191,7 +192,8 @@ int mpb_device_count(void)
 //   b  = prob_j_errors(p, 1, 1) = ((1-1+1)/(1.0*1)) * (p/(1-p)) * pow(1 - p, 1)
 // evaluated on the host with libm (this TU is built with -ffp-contract=off).  Bytes 0 ('N')
 // and 255 ('n') are the identity step of the DP: skipping a base == multiplying by {1, 0}.
-static void lut_entry(int q, double2 *e)          // any quality the reference's int can hold (p underflows to 0 near Q = 3240)
+// odds != nullptr: also {a, r = p / (1 - p)}, the entry of MPB_FLAG_ODDS' table (a * r is the reference's b before its rounding)
+static void lut_entry(int q, double2 *e, double2 *odds = nullptr)   // any quality the reference's int can hold (p underflows to 0 near Q = 3240)
 {
     volatile double p = pow(10, (q / -10.0));
     volatile double a = pow((1 - p), 1);
@@ -200,13 +202,18 @@ static void lut_entry(int q, double2 *e)          // any quality the reference's
     volatile double b = b1 * a;
     e->x = a;
     e->y = b;
+    if (odds) { odds->x = a; odds->y = r; }
 }
 
-static void build_lut(double2 *lut)
+static void build_lut(double2 *lut, double2 *odds = nullptr)
 {
     for (int q = 0; q < 256; q++) {
-        if (q == 0 || q == 255) { lut[q].x = 1.0; lut[q].y = 0.0; continue; }
-        lut_entry(q, &lut[q]);
+        if (q == 0 || q == 255) {                       // the identity step, in the odds form too: {1, 0}
+            lut[q].x = 1.0; lut[q].y = 0.0;
+            if (odds) odds[q] = lut[q];
+            continue;
+        }
+        lut_entry(q, &lut[q], odds ? &odds[q] : nullptr);
     }
 }
 
@@ -241,9 +248,10 @@ int mpb_create(int device_id, mpb_ctx **out)
     }
     c->copy_threads = staging_threads();
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_lut, 256 * sizeof(double2));
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_lut_odds, 256 * sizeof(double2));
     if (e == hipSuccess) {
-        double2 h[256];
-        build_lut(h);
+        double2 h[256], h_odds[256];
+        build_lut(h, h_odds);
         // the narrow pass keeps {p'} alone and recomputes 1 - p' on the device: only sound if the table's a IS that difference
         // (it is: p' == p bit for bit for every encodable score, tests/test_oracle_golden.py::test_lut_pins)
         c->narrow_ok = true;
@@ -252,7 +260,8 @@ int mpb_create(int device_id, mpb_ctx **out)
             if (memcmp((const void *)&d, &h[qq].x, sizeof(double)) != 0) c->narrow_ok = false;
         }
         e = hipMemcpyAsync(c->d_lut, h, sizeof(h), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // h is on this frame
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_lut_odds, h_odds, sizeof(h_odds), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // h, h_odds are on this frame
     }
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->pin_words, 64 * sizeof(int32_t), hipHostMallocDefault);
     if (e == hipSuccess) {
@@ -297,6 +306,7 @@ int mpb_destroy(mpb_ctx *c)
     if (c->ws_nar) (void)hipFree(c->ws_nar);
     if (c->ws_rg) (void)hipFree(c->ws_rg);
     if (c->d_lut) (void)hipFree(c->d_lut);
+    if (c->d_lut_odds) (void)hipFree(c->d_lut_odds);
     if (c->d_lut_private) (void)hipFree(c->d_lut_private);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -605,6 +615,10 @@ static int check_params(const mpb_filter_params *p)
     if (p->ambig_mode < 0 || p->ambig_mode > 2) return fail(MPB_E_INVALID, "unknown ambig_mode %d", p->ambig_mode);
     if ((p->flags & MPB_FLAG_FAST_FMA) && p->alpha < 1e-5)      // the fma error grows like 1/alpha (include/moira_pb.h)
         return fail(MPB_E_INVALID, "MPB_FLAG_FAST_FMA needs alpha >= 1e-5 (its error bound does not hold below)");
+    if ((p->flags & MPB_FLAG_ODDS) && (p->flags & MPB_FLAG_FAST_FMA))
+        return fail(MPB_E_INVALID, "MPB_FLAG_ODDS and MPB_FLAG_FAST_FMA are two arithmetics for the same pass: set one");
+    if ((p->flags & MPB_FLAG_ODDS) && p->alpha < 1e-5)          // the same 1/alpha growth (include/moira_pb.h)
+        return fail(MPB_E_INVALID, "MPB_FLAG_ODDS needs alpha >= 1e-5 (its error bound does not hold below)");
     const bool has_me = p->maxerrors == p->maxerrors;
     if (has_me && !(p->maxerrors > 0)) return fail(MPB_E_INVALID, "maxerrors must be > 0");           // moira.py:732
     if (!has_me && !(p->uncert > 0 && p->uncert <= 1)) return fail(MPB_E_INVALID, "uncert must be in (0,1]");  // moira.py:728
@@ -698,7 +712,9 @@ static int filter_device_tail(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t
     const int32_t max_len = prm.max_len;
     { Span t(c, MPB_K_SCAN);     mpb_launch_scan(n, d_len, c->ws, s); }
     { Span t(c, MPB_K_SCATTER);  mpb_launch_scatter(n, d_len, d_ns, prm, c->ws, s, d_list); }
-    { Span t(c, MPB_K_DP);       mpb_launch_dp(d_q, n, row_stride, d_len, prm, c->ws, d_ns, d_ee, d_pass, s); }
+    // MPB_FLAG_ODDS: the main pass alone, and only on the context's own table (a private one -- scores above 254 -- has no odds twin)
+    const double2 *lut_odds = (prm.flags & MPB_FLAG_ODDS) && c->ws.lut == c->d_lut ? c->d_lut_odds : nullptr;
+    { Span t(c, MPB_K_DP);       mpb_launch_dp(d_q, n, row_stride, d_len, prm, c->ws, d_ns, d_ee, d_pass, s, lut_odds); }
     if (max_len + 1 > MPB_TILE_MAX_ROWS) { Span t(c, MPB_K_WIDE); mpb_launch_wide(d_q, row_stride, d_len, prm, c->ws, d_ns, d_ee, d_pass, s); }
     { Span t(c, MPB_K_OVERFLOW); mpb_launch_overflow(d_q, n, row_stride, d_len, prm, c->ws, d_ns, d_ee, d_pass, s); }
     HIPCHK(hipGetLastError());
@@ -773,7 +789,7 @@ static int narrow_rows_from_sample(const int32_t *hist, int n_sample)
 // Fixed-length batches, and (round 6) ragged ones whose rows hold up to MPB_RG_MAX_STRIDE bytes (k_narrow_rg).
 static bool narrow_eligible(const mpb_ctx *c, int64_t n, int64_t row_stride, const int32_t *d_len, int32_t fixed_len, const mpb_filter_params *p)
 {
-    const uint32_t forbidden = MPB_FLAG_FAST_FMA | MPB_FLAG_TEST_UNDERPREDICT | MPB_FLAG_DECISION_ONLY | MPB_FLAG_COUNT_CELLS | MPB_FLAG_NO_NARROW;
+    const uint32_t forbidden = MPB_FLAG_FAST_FMA | MPB_FLAG_ODDS | MPB_FLAG_TEST_UNDERPREDICT | MPB_FLAG_DECISION_ONLY | MPB_FLAG_COUNT_CELLS | MPB_FLAG_NO_NARROW;
     if (!(c->narrow_ok && n >= 1 && !(p->flags & forbidden) && c->ws.lut == c->d_lut)) return false;
     return d_len ? row_stride <= MPB_RG_MAX_STRIDE : fixed_len >= 1;
 }

@@ -219,9 +219,10 @@ void mpb_launch_serve(const MpbServeBox &box, const double2 *lut, uint32_t gener
 void mpb_launch_scan(int64_t n, const int32_t *len, const MpbWorkspace &ws, hipStream_t s);
 void mpb_launch_scatter(int64_t n, const int32_t *len, const int32_t *ns, const MpbDevParams &prm, const MpbWorkspace &ws,
                         hipStream_t s, const int32_t *list = nullptr);
+// lut_odds != nullptr (MPB_FLAG_ODDS): the main pass runs the one-FMA recurrence on that {a, r = p / (1 - p)} table (k_dp_odds)
 void mpb_launch_dp(const uint8_t *q, int64_t n, int64_t stride, const int32_t *len,
                    const MpbDevParams &prm, const MpbWorkspace &ws, const int32_t *ns,
-                   double *ee, uint8_t *pass, hipStream_t s);
+                   double *ee, uint8_t *pass, hipStream_t s, const double2 *lut_odds = nullptr);
 void mpb_launch_overflow(const uint8_t *q, int64_t n, int64_t stride, const int32_t *len,
                          const MpbDevParams &prm, const MpbWorkspace &ws, const int32_t *ns,
                          double *ee, uint8_t *pass, hipStream_t s);

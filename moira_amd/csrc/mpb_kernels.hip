@@ -718,64 +718,77 @@ __device__ __forceinline__ double cell(double a, double v, double b, double w)
     return x + y;                // fl(x+y): three roundings, as the reference
 }
 
-// one base: advance the running vector by (a,b)
-template <int R, int G, bool FMA>
-__device__ __forceinline__ void dp_step(double (&v)[R], const double2 ab, const int keep)
+// The arithmetic of a class body.  EXACT: the reference's three roundings per cell.  FMA: MPB_FLAG_FAST_FMA, two operations.
+// ODDS: MPB_FLAG_ODDS, one (ODDS_MODE.md): the table is {a, r = p / (1 - p)} and the registers hold the coefficients w of
+// prod (1 + r_k x), row j of the reference's table being P0 * w[j] with P0 = prod a_k, which every lane keeps in p0.
+enum { MPB_AR_EXACT = 0, MPB_AR_FMA = 1, MPB_AR_ODDS = 2 };
+
+// one base: advance the running vector by (a,b) -- ODDS: by (a,r), w[j] += r * w[j-1] and p0 *= a; the first row of a read is the
+// constant 1 (its leader lane shifts in 0, a one-lane read never touches it)
+template <int R, int G, int AR>
+__device__ __forceinline__ void dp_step(double (&v)[R], double &p0, const double2 ab, const int keep)
 {
     double cin = 0.0;
     if (G > 1) cin = dpp_prev_row(v[R - 1], keep);
+    if (AR == MPB_AR_ODDS) {
 #pragma unroll
-    for (int r = R - 1; r >= 1; r--) v[r] = cell<FMA>(ab.x, v[r], ab.y, v[r - 1]);
-    if (G > 1) v[0] = cell<FMA>(ab.x, v[0], ab.y, cin);
+        for (int r = R - 1; r >= 1; r--) v[r] = __builtin_fma(ab.y, v[r - 1], v[r]);
+        if (G > 1) v[0] = __builtin_fma(ab.y, cin, v[0]);
+        p0 *= ab.x;
+        return;
+    }
+#pragma unroll
+    for (int r = R - 1; r >= 1; r--) v[r] = cell<AR == MPB_AR_FMA>(ab.x, v[r], ab.y, v[r - 1]);
+    if (G > 1) v[0] = cell<AR == MPB_AR_FMA>(ab.x, v[0], ab.y, cin);
     else v[0] = ab.x * v[0];
 }
 
-template <int R, int G, bool FMA>
-__device__ __forceinline__ void dp_dword(double (&v)[R], uint32_t w, int keep)
+template <int R, int G, int AR>
+__device__ __forceinline__ void dp_dword(double (&v)[R], double &p0, uint32_t w, int keep)
 {
 #pragma unroll
-    for (int t = 0; t < 4; t++) dp_step<R, G, FMA>(v, mpb_s_lut[(w >> (8 * t)) & 0xffu], keep);
+    for (int t = 0; t < 4; t++) dp_step<R, G, AR>(v, p0, mpb_s_lut[(w >> (8 * t)) & 0xffu], keep);
 }
 
 // 16 bases.  Narrow bodies are unrolled completely; wide ones loop over the 4 dwords so that the
 // LUT entries in flight (registers) and the code size stay bounded.
-template <int R, int G, bool FMA>
-__device__ __forceinline__ void dp_chunk_compact(double (&v)[R], const uint4 x, int keep)
+template <int R, int G, int AR>
+__device__ __forceinline__ void dp_chunk_compact(double (&v)[R], double &p0, const uint4 x, int keep)
 {
     uint32_t w0 = x.x, w1 = x.y, w2 = x.z, w3 = x.w;
 #pragma unroll 1
     for (int d = 0; d < 2; d++) {          // 8 bases per trip
-        dp_dword<R, G, FMA>(v, w0, keep);
-        dp_dword<R, G, FMA>(v, w1, keep);
+        dp_dword<R, G, AR>(v, p0, w0, keep);
+        dp_dword<R, G, AR>(v, p0, w1, keep);
         w0 = w2; w1 = w3;
     }
 }
 
 // up to 16 bases of a tail chunk: `ndw` (wave-uniform, 1..4) dwords, 8 bases per trip while two dwords remain
-template <int R, int G, bool FMA>
-__device__ __forceinline__ void dp_chunk_tail(double (&v)[R], const uint4 x, int keep, int ndw)
+template <int R, int G, int AR>
+__device__ __forceinline__ void dp_chunk_tail(double (&v)[R], double &p0, const uint4 x, int keep, int ndw)
 {
     uint32_t w0 = x.x, w1 = x.y, w2 = x.z, w3 = x.w;
     int d = 0;
 #pragma unroll 1
     for (; d + 2 <= ndw; d += 2) {
-        dp_dword<R, G, FMA>(v, w0, keep);
-        dp_dword<R, G, FMA>(v, w1, keep);
+        dp_dword<R, G, AR>(v, p0, w0, keep);
+        dp_dword<R, G, AR>(v, p0, w1, keep);
         w0 = w2; w1 = w3;
     }
-    if (d < ndw) dp_dword<R, G, FMA>(v, w0, keep);
+    if (d < ndw) dp_dword<R, G, AR>(v, p0, w0, keep);
 }
 
-template <int R, int G, bool FMA>
-__device__ __forceinline__ void dp_chunk(double (&v)[R], const uint4 x, int keep)
+template <int R, int G, int AR>
+__device__ __forceinline__ void dp_chunk(double (&v)[R], double &p0, const uint4 x, int keep)
 {
     if (R <= 8) {
-        dp_dword<R, G, FMA>(v, x.x, keep);
-        dp_dword<R, G, FMA>(v, x.y, keep);
-        dp_dword<R, G, FMA>(v, x.z, keep);
-        dp_dword<R, G, FMA>(v, x.w, keep);
+        dp_dword<R, G, AR>(v, p0, x.x, keep);
+        dp_dword<R, G, AR>(v, p0, x.y, keep);
+        dp_dword<R, G, AR>(v, p0, x.z, keep);
+        dp_dword<R, G, AR>(v, p0, x.w, keep);
     } else {
-        dp_chunk_compact<R, G, FMA>(v, x, keep);
+        dp_chunk_compact<R, G, AR>(v, p0, x, keep);
     }
 }
 
@@ -806,6 +819,17 @@ __device__ __forceinline__ double cross_ee(bool crossed, int js, double thr, dou
 {
     if (!crossed) return __builtin_nan("");
     double e = (double)(js - 1) + ((thr - lo) / (hi - lo));
+    if (e < 0) e = 0;
+    return e;
+}
+
+// The same for MPB_FLAG_ODDS, whose lo and hi are the CDF divided by p0.  The numerator is taken in the reference's own scale,
+// thr - p0 * lo in one rounding: a read that crosses in row 1 (lo == 1: ee is the fraction alone, and may be tiny) then has the
+// reference's fl(thr - P0) bit for bit, where thr / p0 - lo would have lost every digit of it.
+__device__ __forceinline__ double cross_ee_odds(bool crossed, int js, double thr, double p0, double lo, double hi)
+{
+    if (!crossed) return __builtin_nan("");
+    double e = (double)(js - 1) + (__builtin_fma(-lo, p0, thr) / (p0 * (hi - lo)));
     if (e < 0) e = 0;
     return e;
 }
@@ -847,186 +871,21 @@ __device__ __forceinline__ bool class_has_n(const DpArgs &A, int idx)
 // A run of consecutive tiles of one class.  Deliberately NOT inlined: each (R,G) body gets its own
 // register allocation, so the kernel's VGPR budget is the widest body's, not the sum of all of them.
 // The call saves the callee-saved VGPRs it uses to scratch; taking a run of tiles per call keeps
-// that traffic negligible.
+// that traffic negligible.  The body is mpb_dp_tiles.inc, here with the reference's arithmetic or MPB_FLAG_FAST_FMA's ...
+#define MPB_DP_AR (FMA ? MPB_AR_FMA : MPB_AR_EXACT)
 template <int R, int G, bool FMA>
 __device__ __noinline__ void dp_tiles(const DpArgs *__restrict__ Ap, const int32_t *perm_cls,
                                       int count, int first_tile, int n_tiles)
-{
-    const DpArgs &A = *Ap;
-    constexpr int RPT = 64 / G;
-    const int lane = lane_id();
-    const int lig = lane & (G - 1);
-    const bool leader = lig == 0;
-    int keep = leader ? 0 : -1;
-    asm volatile("" : "+v"(keep));        // opaque: keeps `& keep` a v_and (foldable into the DPP op), not a select
-#pragma unroll 1
-    for (int local_tile = first_tile; local_tile < first_tile + n_tiles; local_tile++) {
-    const int slot = local_tile * RPT + lane / G;
-    const bool valid = slot < count;
-    const int idx = gload(perm_cls + (valid ? slot : count - 1));
-    const int li = A.len ? clamp_len(gload(A.len + idx), A.prm.max_len) : A.prm.fixed_len;
-    const uint8_t *row = A.q + (int64_t)idx * A.stride;
+#include "mpb_dp_tiles.inc"
+#undef MPB_DP_AR
 
-    int limax = li;                       // the longest read of the tile
-    int nfull = li >> 4;                  // chunks that are complete in EVERY lane: no masking needed
-    if (A.len) {                          // (fixed-length batches: every lane has the same li)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            limax = max(limax, __shfl_xor(limax, off));
-            nfull = min(nfull, __shfl_xor(nfull, off));
-        }
-    }
-    limax = __builtin_amdgcn_readfirstlane(limax);  // wave-uniform trip counts
-    nfull = __builtin_amdgcn_readfirstlane(nfull);
-    const int nch = (limax + 15) >> 4;    // 16-byte chunks to walk
-
-    double v[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) v[r] = 0.0;
-    if (leader) v[0] = 1.0;
-
-    // Each lane pulls its row 64 bytes at a time (4 x dwordx4, issued together, one 64-byte
-    // segment of one line) and one super-chunk ahead of the arithmetic, so a cache line is
-    // consumed while it is still resident instead of being re-fetched 16 bytes at a time.
-    // A load is guarded by a WAVE-UNIFORM test only (the chunk lies inside the row: rows are `stride`
-    // bytes whatever the read's length, and bytes past a read's end are masked below), so the
-    // prefetch costs one 64-bit pointer bump per 64 bases instead of a compare / exec-mask / zero-fill
-    // sequence per 16.
-    const int row_chunks = __builtin_amdgcn_readfirstlane((int)(A.stride >> 4));
-    const int nsc = (nch + 3) >> 2;                // wave-uniform 64-byte super-chunks
-    const int nsc_fast = nfull >> 2;               // ... of which this many hold 64 valid bases in EVERY lane (all inside the row)
-    uint4 cur[4], nxt[4];
-#pragma unroll
-    for (int p = 0; p < 4; p++) cur[p] = nxt[p] = make_uint4(0, 0, 0, 0);
-    if (nsc_fast > 0) {
-#pragma unroll
-        for (int p = 0; p < 4; p++) cur[p] = gload16(row + p * 16);
-        // Exactly four loads per trip, whatever the trip, issued BEFORE the trip's arithmetic and first
-        // waited for at the top of the next trip: a whole super-chunk of FP64 work (1.5-6 us) covers the
-        // memory latency.  The last trip has nothing new to fetch when the row ends here; it re-reads its
-        // own (cache-resident) 64 bytes instead of branching, because a path-dependent load count makes
-        // the compiler's wait-count bookkeeping fall back to "wait for everything" at once.
-        // (Tried and rejected, bit-exact both: re-loading two chunks at a time into the registers just
-        // consumed -- no second register set, no copies, but half the prefetch distance: k_dp +2 %.)
-        for (int sc = 0; sc < nsc_fast; sc++) {
-            const int nxt_sc = (sc * 4 + 8 <= row_chunks) ? sc + 1 : sc;     // scalar select
-            const uint8_t *pf = row + (nxt_sc << 6);
-#pragma unroll
-            for (int p = 0; p < 4; p++) nxt[p] = gload16(pf + p * 16);
-            // the machine scheduler otherwise sinks these loads to the end of the trip (their registers are
-            // free there) and the next trip opens with vmcnt(0): the whole memory latency exposed
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int p = 0; p < 4; p++) dp_chunk<R, G, FMA>(v, cur[p], keep);
-#pragma unroll
-            for (int p = 0; p < 4; p++) cur[p] = nxt[p];
-        }
-    }
-    // tail: the super-chunks that are ragged in some lane (a 300-base read: bases 256..299)
-    for (int sc = nsc_fast; sc < nsc; sc++) {
-        if (!(sc > 0 && sc == nsc_fast && sc * 4 + 4 <= row_chunks)) {      // not already fetched by the loop above
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                cur[p] = make_uint4(0, 0, 0, 0);
-                if (sc * 4 + p < row_chunks) cur[p] = gload16(row + (sc * 4 + p) * 16);   // wave-uniform guard
-            }
-        }
-        const int pmax = min(4, nch - sc * 4);     // wave-uniform
-#pragma unroll 1
-        for (int p = 0; p < pmax; p++) {
-            uint4 x = cur[0];
-            cur[0] = cur[1]; cur[1] = cur[2]; cur[2] = cur[3];   // rotate: keeps every index static
-            const int c = sc * 4 + p;
-            int ndw = 4;                                 // dwords of this chunk to walk: wave-uniform
-            if (c >= nfull) {                            // wave-uniform: only ragged tail chunks are masked
-                const int nv = li - c * 16;              // may be <= 0 for reads shorter than the tile's longest
-                x.x = mask_dword(x.x, nv); x.y = mask_dword(x.y, nv - 4);
-                x.z = mask_dword(x.z, nv - 8); x.w = mask_dword(x.w, nv - 12);
-                ndw = min(4, (limax - c * 16 + 3) >> 2); // a 300-base read ends 12 bases into its last chunk: 3 dwords, not 4
-            }
-            dp_chunk_tail<R, G, FMA>(v, x, keep, ndw);
-        }
-    }
-
-    // ---- epilogue: sequential CDF, first row above thr ----
-    const double thr = A.prm.thr;
-    double lo = 0.0, hi = 0.0;
-    int js = -1;
-    bool writer;                                   // the lane that reports this read
-    bool never_crossed = false;
-    if (G == 1) {
-        js = cdf_cross(v, 0.0, thr, 0, lo, hi);
-        writer = valid;
-        never_crossed = js < 0;
-    } else {
-        // Phase A: the running sum visits the G lanes of a read in order (same additions, same
-        // order as the reference); a lane only notes whether the crossing falls inside its rows.
-        // The CDF never decreases, so that is "sum after my rows > thr and nobody before me".
-        double acc = 0.0, acc_in_mine = 0.0;
-        int found = 0;
-        bool mine = false;
-#pragma unroll 1
-        for (int g = 0; g < G; g++) {
-            double acc_s = acc;
-            int found_s = found;
-            if (g > 0) {
-                const int src = (lane & ~(G - 1)) + g - 1;
-                acc_s = __shfl(acc, src);
-                found_s = __shfl(found, src);
-            }
-            if (lig == g) {
-                double a = acc_s;
-#pragma unroll
-                for (int r = 0; r < R; r++) a = a + v[r];
-                const bool cross = !found_s && (a > thr);
-                mine = cross;
-                acc_in_mine = acc_s;
-                acc = a;
-                found = found_s | (cross ? 1 : 0);
-            }
-        }
-        // Phase B: only the crossing lane walks its rows again to pick out the two CDF values.
-        if (mine) js = cdf_cross(v, acc_in_mine, thr, lig * R, lo, hi);
-        never_crossed = (lig == G - 1) && !found;  // the last lane has seen the whole CDF
-        writer = valid && (mine || never_crossed);
-    }
-    if (writer) {
-        if (never_crossed && A.final_pass == 0) {
-            const int pos = atomicAdd(A.ovf_count, 1);
-            A.ovf_list[pos] = idx;
-        } else if (never_crossed && A.final_pass == 2) {
-            A.pass[idx] = 2;                                   // small-batch path: the host re-runs the batch
-        } else {
-            double e = cross_ee(!never_crossed, js, thr, lo, hi);
-            const int nsv = A.perm_ns ? (int)gload(A.perm_ns + (perm_cls - A.perm) + slot) : gload(A.ns + idx);
-            if ((A.prm.flags & MPB_FLAG_COUNT_CELLS) && !never_crossed) {      // diagnostic, off by default
-                // the table the reference fills for this read: rows 0..js over the L' = len - Ns scored bases, of which
-                // row j is non-zero from base j on: sum_k min(k + 1, J), J = js + 1 (SURVEY 8d "algorithmic flops")
-                const int J = js + 1, Lp = li - nsv;                 // J <= 1024, Lp <= 16383: 32-bit arithmetic is enough
-                const int cells = J <= Lp ? ((J * (J + 1)) >> 1) + (Lp - J) * J : (Lp * (Lp + 1)) >> 1;
-                atomicAdd(&mpb_s_cells, (unsigned long long)(unsigned int)cells);
-            }
-            e = mpb_add_ns(A.prm, e, nsv);
-            if (FMA && A.final_pass != 1 && !never_crossed) {
-                // MPB_FLAG_FAST_FMA keeps the DECISIONS exact: an ee that lands within 1e-9 relative of the
-                // threshold (or, with --round, of an integer) is not trusted -- the read goes to the second
-                // pass, which always runs the three-rounding arithmetic
-                const double tol = 1e-9 * fmax(1.0, fabs(e));
-                bool unsure = fabs(e - mpb_limit(A.prm, li)) <= tol;
-                if (A.prm.flags & MPB_FLAG_ROUND) unsure = unsure || fabs(e - rint(e)) <= tol;
-                if (unsure) {
-                    if (A.final_pass == 0) { const int pos = atomicAdd(A.ovf_count, 1); A.ovf_list[pos] = idx; }
-                    else A.pass[idx] = 2;
-                    continue;
-                }
-            }
-            const bool keep_read = mpb_round_and_keep(A.prm, e, class_has_n(A, idx), li);
-            gstore(A.ee + idx, e);
-            gstore(A.pass + idx, (uint8_t)(keep_read ? 1 : 0));
-        }
-    }
-    }   // tiles of this run
-}
+// ... and here with MPB_FLAG_ODDS': one FMA per cell
+#define MPB_DP_AR MPB_AR_ODDS
+template <int R, int G>
+__device__ __noinline__ void dp_tiles_odds(const DpArgs *__restrict__ Ap, const int32_t *perm_cls,
+                                           int count, int first_tile, int n_tiles)
+#include "mpb_dp_tiles.inc"
+#undef MPB_DP_AR
 
 // DpArgs arrive as a kernel argument and are parked in LDS, so that the non-inlined class bodies can
 // take a pointer to them (no extra launch to put them into device memory)
@@ -1037,13 +896,11 @@ __device__ __noinline__ void dp_tiles(const DpArgs *__restrict__ Ap, const int32
 // is made of the cheapest tiles.  The chunk loop is grid-strided because the host sizes the grid
 // from an upper bound that assumes one read per lane; every wave's loop ends when its chunk index
 // passes the tile count.
-template <bool FMA, bool OVERFLOW_PASS>
-__global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_dp(DpArgs args,
-                                            const double2 *__restrict__ lut_g,
-                                            MpbTables *__restrict__ tb,
-                                            const int32_t *__restrict__ perm, int chunk_tiles)
+// (s_args is the calling kernel's own __shared__ DpArgs: one object per kernel, as the class bodies' callers have always had)
+template <int AR>
+__device__ __forceinline__ void dp_grid(const DpArgs &args, DpArgs &s_args, const double2 *__restrict__ lut_g,
+                                        MpbTables *__restrict__ tb, const int32_t *__restrict__ perm, int chunk_tiles)
 {
-    __shared__ DpArgs s_args;
     mpb_s_lut[threadIdx.x] = lut_g[threadIdx.x];
     if (threadIdx.x == 0) { s_args = args; mpb_s_cells = 0ull; }
     __syncthreads();
@@ -1062,7 +919,10 @@ __global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_dp(DpArgs args,
             if (lo >= hi) continue;
             const int32_t *pc = perm + tb->perm_base[c];
             switch (c) {
-#define MPB_CASE(ID, RR, GG) case ID: dp_tiles<RR, GG, FMA>(A, pc, cnt, lo - s, hi - lo); break;
+#define MPB_CASE(ID, RR, GG) case ID:                                                                 \
+                if constexpr (AR == MPB_AR_ODDS) dp_tiles_odds<RR, GG>(A, pc, cnt, lo - s, hi - lo);                \
+                else dp_tiles<RR, GG, AR == MPB_AR_FMA>(A, pc, cnt, lo - s, hi - lo);                     \
+                break;
                 MPB_CLASSES(MPB_CASE)
 #undef MPB_CASE
             default: break;
@@ -1073,6 +933,26 @@ __global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_dp(DpArgs args,
         __syncthreads();
         if (threadIdx.x == 0 && mpb_s_cells) atomicAdd(args.alg_cells, mpb_s_cells);
     }
+}
+
+template <bool FMA, bool OVERFLOW_PASS>
+__global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_dp(DpArgs args,
+                                            const double2 *__restrict__ lut_g,
+                                            MpbTables *__restrict__ tb,
+                                            const int32_t *__restrict__ perm, int chunk_tiles)
+{
+    __shared__ DpArgs s_args;
+    dp_grid<FMA ? MPB_AR_FMA : MPB_AR_EXACT>(args, s_args, lut_g, tb, perm, chunk_tiles);
+}
+
+// The main pass with MPB_FLAG_ODDS: lut_g is the {a, r} table.  Reads it cannot vouch for go on the overflow list.
+__global__ __launch_bounds__(256, MPB_DP_WAVES_PER_EU) void k_dp_odds(DpArgs args,
+                                            const double2 *__restrict__ lut_g,
+                                            MpbTables *__restrict__ tb,
+                                            const int32_t *__restrict__ perm, int chunk_tiles)
+{
+    __shared__ DpArgs s_args;
+    dp_grid<MPB_AR_ODDS>(args, s_args, lut_g, tb, perm, chunk_tiles);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2809,7 +2689,7 @@ static DpArgs make_args(const uint8_t *q, int64_t stride, const int32_t *len, co
 
 void mpb_launch_dp(const uint8_t *q, int64_t n, int64_t stride, const int32_t *len,
                    const MpbDevParams &prm, const MpbWorkspace &ws, const int32_t *ns,
-                   double *ee, uint8_t *pass, hipStream_t s)
+                   double *ee, uint8_t *pass, hipStream_t s, const double2 *lut_odds)
 {
     // Upper bound for the tile count without a host round trip: every read in a G==1 class
     // (64 reads per tile) plus one partial tile per class.  Classes with G > 1 have more tiles
@@ -2822,7 +2702,9 @@ void mpb_launch_dp(const uint8_t *q, int64_t n, int64_t stride, const int32_t *l
     int64_t want = (tiles + 4 * chunk_tiles - 1) / (4 * chunk_tiles);   // blocks if every wave took one chunk
     const int blocks = (int)(want < grid_cap ? (want > 0 ? want : 1) : grid_cap);
     DpArgs A = make_args(q, stride, len, prm, ws, ns, ee, pass, 0);
-    if (prm.flags & MPB_FLAG_FAST_FMA)
+    if (lut_odds)
+        hipLaunchKernelGGL(k_dp_odds, dim3(blocks), dim3(256), 0, s, A, lut_odds, ws.tables, ws.perm, chunk_tiles);
+    else if (prm.flags & MPB_FLAG_FAST_FMA)
         hipLaunchKernelGGL((k_dp<true, false>), dim3(blocks), dim3(256), 0, s, A, ws.lut, ws.tables, ws.perm, chunk_tiles);
     else
         hipLaunchKernelGGL((k_dp<false, false>), dim3(blocks), dim3(256), 0, s, A, ws.lut, ws.tables, ws.perm, chunk_tiles);

@@ -130,6 +130,7 @@ def main():
             s = s.replace(old, new)
     # the copy lives elsewhere: make its relative includes absolute
     s = s.replace('#include "mpb_internal.h"', '#include "%s"' % os.path.join(ROOT, "moira_amd", "csrc", "mpb_internal.h"))
+    s = s.replace('#include "mpb_dp_tiles.inc"', '#include "%s"' % os.path.join(ROOT, "moira_amd", "csrc", "mpb_dp_tiles.inc"))
     s = s.replace('#include "../../include/mpb_synth.h"', '#include "%s"' % os.path.join(ROOT, "include", "mpb_synth.h"))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     open(out, "w").write(s)

@@ -69,6 +69,8 @@ with Engine(0) as eng:
             extra["decision_only"] = True
         elif rng.random() < 0.2:
             extra["fast_fma"] = True                                 # ee within 1e-9 relative, decisions exact
+        elif rng.random() < 0.25:
+            extra["odds"] = True                                     # MPB_FLAG_ODDS: the same contract
         if rng.random() < 0.1:                                       # --error_calc poisson against the reference's formula
             m = min(n, 300)
             qp = q[:m].copy()
@@ -100,7 +102,7 @@ with Engine(0) as eng:
         if extra.get("decision_only"):
             sk = np.isinf(r.ee) & ~np.isinf(ee)
             ok = ok and np.array_equal(r.ee[~sk], ee[~sk], equal_nan=True) and not ps[sk].any()
-        elif extra.get("fast_fma"):
+        elif extra.get("fast_fma") or extra.get("odds"):
             both = ~np.isnan(r.ee) & ~np.isnan(ee)
             rel = np.abs(r.ee[both] - ee[both]) / np.maximum(np.abs(ee[both]), 1e-300)
             ok = ok and np.array_equal(np.isnan(r.ee), np.isnan(ee)) and (rel.size == 0 or rel.max() <= 1e-9)
