@@ -53,6 +53,9 @@ def lib():
         L.pbo_filter_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
                                        C.POINTER(Params), C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pbo_filter_batch_model.restype = C.c_int
+        L.pbo_filter_batch_model.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                             C.POINTER(Params), C.c_int, C.c_int] + [C.c_void_p] * 7
         L.pbo_synth_fill.restype = None
         L.pbo_synth_fill.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_uint64, C.c_int64]
@@ -127,6 +130,36 @@ def filter_batch(q, lens=None, fixed_len=None, shape=0, threads=1, **kw):
     if rc != 0:
         raise ValueError("oracle rc=%d" % rc)
     return ee, ns, ps, rows
+
+
+ARITH = {"exact": 0, "fma": 1, "odds": 2}
+
+
+class ModelResult:
+    """Per read: ee_model (the model's ee after +Ns, before --round's floor), rows (crossing row + 1), p0 (ODDS; 1 otherwise),
+    hand (bool: the mode hands the read to the exact pass), and what the mode reports when it keeps it: ee, ns, passed."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def filter_batch_model(q, arith, lens=None, fixed_len=None, threads=1, **kw):
+    """CPU model of one arithmetic ("exact", "fma" = MPB_FLAG_FAST_FMA, "odds" = MPB_FLAG_ODDS) over a packed matrix."""
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    n, stride = q.shape
+    if lens is not None:
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+    out = dict(ee_model=np.empty(n), rows=np.empty(n, np.int32), p0=np.empty(n), hand=np.empty(n, np.uint8),
+               ee=np.empty(n), ns=np.empty(n, np.int32), passed=np.empty(n, np.uint8))
+    prm = make_params(**kw)
+    rc = lib().pbo_filter_batch_model(q.ctypes.data, n, stride, lens.ctypes.data if lens is not None else None,
+                                      0 if fixed_len is None else int(fixed_len), C.byref(prm), ARITH[arith], threads,
+                                      *[out[k].ctypes.data for k in ("ee_model", "rows", "p0", "hand", "ee", "ns", "passed")])
+    if rc != 0:
+        raise ValueError("oracle rc=%d" % rc)
+    out["hand"] = out["hand"].astype(bool)
+    out["passed"] = out["passed"].astype(bool)
+    return ModelResult(**out)
 
 
 def synth_fill(n, stride, fixed_len=0, min_len=0, max_len=0, seed=1, first_read=0, profile=0):
