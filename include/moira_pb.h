@@ -90,9 +90,11 @@ extern "C" {
 #define MPB_FLAG_DECISION_ONLY 8u /* opt-in, NOT the reference's contract: a read whose expected errors are
                                     PROVABLY above the threshold (multiplicative Chernoff lower-tail bound on the
                                     Poisson-binomial quantile, from the prepass' mean) is reported pass = 0,
-                                    ee = +infinity without running its DP (a NaN still means what it means without
-                                    the flag: the CDF never crossed -- the reference's ReturnedNaNError).  Every other read is computed exactly as
-                                    usual, and every pass/fail flag equals the full computation's.  For
+                                    ee = +infinity without running its DP.  The bound is taken BEFORE any DP runs, so it wins:
+                                    a read it settles is +infinity whether or not its CDF would ever have crossed 1 - alpha.  A
+                                    read it does not settle is computed exactly as usual, and there a NaN still means what it
+                                    means without the flag: the CDF never crossed -- the reference's ReturnedNaNError.  Both
+                                    are pass = 0, and every pass/fail flag equals the full computation's.  For
                                     pipelines that never look at the ee of a discarded read. */
 #define MPB_FLAG_TEST_UNDERPREDICT 4u /* test hook: halve every predicted row budget so that the
                                          overflow (second) pass is exercised; results are unchanged */
@@ -154,7 +156,11 @@ typedef struct mpb_filter_counts {
     int64_t n_reads;
     int64_t n_pass;
     int64_t n_fail;
-    int64_t n_overflow;   /* reads that needed the second (wide) pass; diagnostic */
+    int64_t n_overflow;   /* reads the second pass re-ran: their CDF did not cross 1 - alpha inside the row budget of the main pass
+                             (J > the class cap mpb_last_read_budgets reports; for a wide read, J > its predicted rows, which no
+                             entry reports -- except where 1 - alpha == 1: every budget is then all of the read's rows), which
+                             includes every read that has no result (NaN); with MPB_FLAG_FAST_FMA / MPB_FLAG_ODDS also the reads
+                             those modes hand over.  Diagnostic. */
 } mpb_filter_counts;
 
 /* ---- library ------------------------------------------------------------ */
@@ -252,6 +258,9 @@ int mpb_encode_ascii_device(mpb_ctx *ctx, const uint8_t *d_q, int64_t n, int64_t
  * behaviour (first CDF row already above 1-alpha -> ee = 0,
  * ref: moira/moira.py:1611,1629 vs moira/bernoullimodule.c:254).
  * d_ee[i] is the value process_data returns (after +Ns / floor).
+ * A read whose summed CDF never exceeds 1 - alpha has no result: ee = NaN, pass = 0 (the reference never leaves its loop there;
+ * moira.py:456,818 call it ReturnedNaNError).  That takes an alpha within a few ulp of 0 -- below 1.1e-16, 1 - alpha is exactly 1
+ * and most reads are such reads; a read without a scored base is 0 (+Ns) at every alpha, as in the reference (moira.py:1631-1632).
  * Asynchronous on the context's stream unless `counts` is given -- with one exception since round 5: a batch that is eligible for
  * the narrow pass (mpb_path_info below: fixed-length or ragged rows of up to 4096 bytes, default table, none of the opt-in flags,
  * >= 262144 reads or MPB_FLAG_NARROW_ROWS) synchronises on the stream inside the call -- once per 64 calls of the same batch shape

@@ -634,6 +634,9 @@ static MpbDevParams make_dev_params(const mpb_filter_params *p, int32_t fixed_le
     const double z = inv_norm_cdf(1 - p->alpha);
     d.z = (float)z;
     d.zq = (float)((z * z - 1) / 6);
+    // alpha below half an ulp of 1: 1 - alpha == 1 and Phi^-1 is inf / inf.  The prediction there is "every row" (no read crosses
+    // before its last one); say so with finite constants instead of leaving it to what fminf makes of a NaN in the kernels.
+    if (!(z == z) || std::isinf(z)) { d.z = 1e30f; d.zq = 0.0f; }
     d.clow = (float)(sqrt(2 * log(1 / (1 - p->alpha))) * 1.0001);
     d.ambig_mode = p->ambig_mode;
     d.flags = p->flags;

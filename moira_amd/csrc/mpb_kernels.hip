@@ -260,6 +260,10 @@ __device__ __forceinline__ void class_read(int64_t i, float mu, float var, float
     o.ns[i] = bad ? 0 : nzero + n255;
     const int c = c_class_of_rows.t[min(rows, MPB_TILE_MAX_ROWS)];
     const bool settled = !bad && settled_by_chernoff(prm, mu, li);
+    // A read without a scored base (no bases, or only N / n) has ee = 0 by definition (ref: moira.py:1631-1632,
+    // bernoullimodule.c:257-260).  The DP finds that as "row 0 is 1, and 1 > 1 - alpha" -- which fails once alpha is below half
+    // an ulp of 1 (1 - alpha == 1): there the read is settled here, with the verdict read_result gives a crossing at ee = 0.
+    const bool empty = !bad && scored <= 0 && !(1.0 > prm.thr);
     if (bad) {
         // a length outside 0..max_len is never clamped silently: the read gets no result (NaN, rejected) --
         // also for a caller that never fetches the counts -- and the call that does fetch them fails
@@ -267,6 +271,12 @@ __device__ __forceinline__ void class_read(int64_t i, float mu, float var, float
         o.cls[i] = (uint8_t)MPB_CLS_SETTLED;
         o.ee[i] = __builtin_nan("");
         o.pass[i] = 0;
+    } else if (empty) {
+        double e = mpb_add_ns(prm, 0.0, nzero + n255);
+        const bool keep = mpb_round_and_keep(prm, e, nzero > 0, li);
+        o.cls[i] = (uint8_t)(MPB_CLS_SETTLED | (nzero > 0 ? 0x80 : 0));
+        o.ee[i] = e;
+        o.pass[i] = (uint8_t)(keep ? 1 : 0);
     } else if (settled) {
         o.cls[i] = (uint8_t)(MPB_CLS_SETTLED | (nzero > 0 ? 0x80 : 0));
         o.ee[i] = __builtin_inf();              // "certainly above the threshold"; NaN stays a failure

@@ -30,6 +30,12 @@ What runs here
   * `--bigq` (round 3): reads that carry quality scores above 254 (a .qual file or a Python caller can hold them; the
     byte matrix cannot) through the real extension and the Python twin -> bigq.json (sequence, integer scores, alpha,
     the reference's (ee, Ns) as hex floats).
+  * `--tiny-alpha`: alpha below the spacing of doubles next to 1 (1e-15, 1e-17), where 1 - alpha is so close to 1 (or
+    is 1) that whether the summed CDF ever exceeds it is decided by the last bit of the sum -> edge_alpha_tiny.npz, from the
+    Python twin alone.  The twin's loop has no exit for a read whose CDF never crosses (every row past the last base adds
+    exactly 0, moira/moira.py:1568-1569), and the C extension walks off its table there; such a read is what
+    moira/moira.py:456,818 report as ReturnedNaNError.  The twin is therefore stopped through its module's `range` once it
+    starts a row past len + 1, and NaN is recorded.
 Only data (inputs + the reference's outputs) is written into the repo.
 
 The inputs are stored in the packed-qscore encoding of include/moira_pb.h
@@ -400,6 +406,66 @@ def make_bigq_fixture(ref, pyref):
     print("bigq.json: %d reads, %d of them ub" % (len(reads), sum(r["ub"] for r in reads)))
 
 
+class NeverCrosses(Exception):
+    pass
+
+
+def twin_or_nan(pyref, seq, quals, alpha):
+    """The twin's (ee, Ns); ee = NaN for a read whose CDF never exceeds 1 - alpha.  Row j of the twin's table is one pass of
+    `for k in range(len(error_probs))` (moira/moira.py:1617); rows past the number of scored bases are exactly 0, so a read
+    that has not crossed by then never will: the guard raises when that loop is entered once more than there are rows."""
+    # (the only `range` call in calculate_errors_PB's own frame is that loop, moira/moira.py:1617; the others are in its nested
+    # helpers, whose frames carry their own names)
+    scored = sum(1 for b in seq if b != "N")
+    state = {"rows": 0}
+
+    def guarded_range(*a):
+        if sys._getframe(1).f_code.co_name == "calculate_errors_PB":      # (the helpers nested in it have loops of their own)
+            state["rows"] += 1
+            if state["rows"] > scored + 1:
+                raise NeverCrosses()
+        return range(*a)
+    pyref.range = guarded_range
+    try:
+        return pyref.calculate_errors_PB(seq, quals, alpha)
+    except NeverCrosses:
+        return float("nan"), seq.count("N")
+    finally:
+        del pyref.range
+
+
+TINY_ALPHAS = (1e-15, 1e-17)
+
+
+def make_tiny_alpha_fixture(pyref):
+    """Short reads (the twin costs J^2 L Python calls and J = L + 1 here) of every kind of quality, a few with N / n."""
+    rng = np.random.default_rng(20161017)
+    n, stride = 320, 64
+    q = np.zeros((n, stride), np.uint8)
+    lens = rng.integers(0, 65, n).astype(np.int32)
+    lens[:8] = (0, 1, 1, 2, 2, 3, 64, 64)
+    for i in range(n):
+        lo, hi = [(1, 42), (1, 6), (20, 42), (1, 94), (2, 3)][i % 5]
+        q[i, :lens[i]] = rng.integers(lo, hi, lens[i])
+        if i % 6 == 1 and lens[i]:
+            q[i, rng.integers(0, lens[i])] = 0
+        if i % 17 == 3 and lens[i]:
+            q[i, rng.integers(0, lens[i])] = 255
+    q[8, :lens[8]] = 0                                  # only N
+    ee = np.full((len(TINY_ALPHAS), n), np.nan)
+    ns = np.zeros(n, np.int32)
+    for ai, alpha in enumerate(TINY_ALPHAS):
+        for i in range(n):
+            seq, quals = unpack(q[i], int(lens[i]))
+            ee[ai, i], ns[i] = twin_or_nan(pyref, seq.replace("n", "N"), quals, alpha)   # as run_set: the C semantics of 'n'
+    for ai, alpha in enumerate(TINY_ALPHAS):             # the guard fired on the reads the oracle has no result for, and no other
+        assert np.array_equal(np.isnan(ee[ai]), np.isnan(O.filter_batch(q, lens=lens, alpha=alpha, ambigs="ignore")[0])), alpha
+    out = os.path.join(HERE, "edge_alpha_tiny.npz")
+    np.savez_compressed(out, q=q, lens=lens, alphas=np.array(TINY_ALPHAS), ee_py=ee, ns_ref=ns)
+    print("edge_alpha_tiny n=%d reads x %d alphas, NaN share %s -> %s"
+          % (n, len(TINY_ALPHAS), ", ".join("%.1f %%" % (100 * np.isnan(e).mean()) for e in ee), os.path.relpath(out, ROOT)))
+
+
 def add_lut_to_kat():
     """Phred -> {p, 1-p, p'} exactly as moira/bernoullimodule.c:202,140-145 evaluate them with THIS container's libm,
     plus libm probes of the Poisson tail (moira/moira.py:1671: exp(-Lambda) * Lambda**j / factorial(j)), as hex floats."""
@@ -444,6 +510,12 @@ def main():
     ref = O.reference_module()
     assert ref is not None, "oracle/_ref/bernoulli.so missing: make -C oracle ref"
     pyref, tmp = load_python_reference()
+    if "--tiny-alpha" in sys.argv:
+        try:
+            make_tiny_alpha_fixture(pyref)
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+        return
     if "--bigq" in sys.argv:
         try:
             make_bigq_fixture(ref, pyref)

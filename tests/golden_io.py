@@ -15,6 +15,13 @@ def load_set(name):
     return {k: z[k] for k in z.files}
 
 
+def load_tiny_alpha():
+    """edge_alpha_tiny.npz (make_golden.py --tiny-alpha): q, lens, alphas (1e-15, 1e-17), ee_py[alpha][read] from the reference's
+    Python twin with NaN where its CDF never crosses, ns_ref.  Kept out of NPZ_SETS: the opt-in arithmetics that walk that
+    list refuse alpha below 1e-5."""
+    return load_set("edge_alpha_tiny")
+
+
 def load_kat():
     return json.load(open(os.path.join(GOLDEN, "kat.json")))
 

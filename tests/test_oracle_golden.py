@@ -51,6 +51,26 @@ def test_oracle_matches_reference_vectors(oracle, name):
     assert np.array_equal(ee[chk], s["ee_py"][chk])      # Python twin agrees wherever it was run
 
 
+def test_oracle_matches_the_twin_where_the_cdf_never_crosses(oracle):
+    """alpha 1e-15 and 1e-17 (1 - alpha is 1 - 9 ulp, and exactly 1): whether a read has a result is decided by the last bit of
+    its summed CDF.  The fixture holds the Python twin's values and NaN where its CDF never crosses; the oracle must agree on
+    which reads those are, and bit for bit on the others."""
+    s = G.load_tiny_alpha()
+    assert list(s["alphas"]) == [1e-15, 1e-17] and len(s["lens"]) >= 300
+    for ai, alpha in enumerate(s["alphas"]):
+        ee, ns, ps, rows = oracle.filter_batch(s["q"], lens=s["lens"], alpha=float(alpha), ambigs="ignore", threads=4)
+        want = s["ee_py"][ai]
+        assert np.array_equal(np.isnan(ee), np.isnan(want)), float(alpha)
+        assert np.array_equal(ee, want, equal_nan=True)
+        assert np.array_equal(ns, s["ns_ref"]) and not ps[np.isnan(want)].any()
+        nan = np.isnan(want)
+        assert nan.sum() >= 5 and (~nan).mean() >= 0.05, nan.mean()      # both kinds of read at both alphas (the twin costs
+                                                                          # J^2 L calls, so the reads are short: few NaN at 1e-15)
+        assert np.array_equal(rows[nan], (s["lens"] - s["ns_ref"])[nan] + 1)     # every row was looked at
+    for i in (0, 8):                                          # no scored base: 0, never NaN (moira/moira.py:1631-1632)
+        assert (s["ee_py"][:, i] == 0).all()
+
+
 @pytest.mark.parametrize("name", ["edge_alpha_0.005", "synth250", "rand_alpha05"])
 def test_refshape_equals_rowwise(oracle, name):
     s = G.load_set(name)
