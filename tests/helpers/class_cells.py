@@ -16,6 +16,9 @@ The places of a body that have code of their own are rows, so a test aims at (cl
             (js = 1023, 1024, 2047, 2048)
   thin      the ten one-read-per-wave bodies (MPB_THIN_CLASSES: cap = the next power of two >= the predicted rows):
             first reachable row (cap / 2; 0 for cap 2), last row, and one lane boundary (g = 3 G / 4) where R > 1
+  modes     MPB_FLAG_FAST_FMA and MPB_FLAG_ODDS compile every class body once more, so the main cells are required again per
+            mode, by the crossing row of the mode's CPU model (generate(mode=...), ledger_mode); ODDS keeps a read only while
+            p0 >= 2^-900, which puts the far rows of class 1024 out of every read's reach (odds_unreachable)
   narrow    the natural-order narrow forms (2, 3, 4 rows): crossing on row 0, on row R - 1, on row R (handed back), a read of
             only 'N', a read with an 'n', and a zero-length read in ragged batches
 
@@ -24,6 +27,7 @@ oracle's rows and, on the GPU, from the budgets the library itself reports.
 """
 import math
 import re
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -38,6 +42,8 @@ THIN_CLASSES = tuple((r * g, g, r) for r, g in (
 TILE_MAX_ROWS = 1024
 CAPS = np.array([c[0] for c in TILE_CLASSES], np.int32)
 ALPHAS = (0.005, 0.05, 1e-6)
+MODES = ("fma", "odds")                   # MPB_FLAG_FAST_FMA, MPB_FLAG_ODDS: each compiles every class body once more
+MODE_ALPHAS = (0.005, 0.05, 1e-5)         # both modes refuse alpha < 1e-5
 
 
 def parse_header_classes(text):
@@ -281,6 +287,17 @@ def ledger_thin(rows, budgets, nan=None):
     return {("thin", int(c), int(j) - 1) for c, j in zip(tc[ok], rows[ok])}
 
 
+def ledger_mode(model, budgets):
+    """Main-pass cells a batch fills under MPB_FLAG_FAST_FMA or MPB_FLAG_ODDS: reads the mode keeps (not handed to the exact
+    pass) whose MODEL crosses inside their budget, by (budget, model rows - 1)."""
+    return ledger_main(model.rows, budgets, nan=model.hand)
+
+
+def ledger_thin_mode(model, budgets):
+    """The same for the one-read-per-wave bodies (MPB_FLAG_FAST_FMA only: k_small has no ODDS form)."""
+    return ledger_thin(model.rows, budgets, nan=model.hand)
+
+
 def ledger_narrow(layout, R, q, lens, rows):
     """Cells of one narrow form on one batch, from the oracle's rows and the bytes alone."""
     q, lens, rows = np.asarray(q), np.asarray(lens), np.asarray(rows)
@@ -324,13 +341,15 @@ def _sprinkle(q, lens):
 
 
 def _uniform_pool(specs, stride):
-    """specs: [(qa, qb, s_lo, s_hi)] -> every read of S = s_lo .. s_hi bases that alternate between qualities qa and qb."""
-    lens = np.concatenate([np.arange(lo, hi + 1) for _, _, lo, hi in specs]).astype(np.int32)
+    """specs: [(qa, qb, s_lo, s_hi[, step])] -> every read of S = s_lo .. s_hi bases (every step-th) that alternate between
+    qualities qa and qb."""
+    specs = [tuple(sp) + (1,) * (5 - len(sp)) for sp in specs]
+    lens = np.concatenate([np.arange(lo, hi + 1, step) for _, _, lo, hi, step in specs]).astype(np.int32)
     q = np.zeros((len(lens), stride), np.uint8)
     at = 0
     col = np.arange(stride)
-    for qa, qb, lo, hi in specs:
-        n = hi - lo + 1
+    for qa, qb, lo, hi, step in specs:
+        n = len(range(lo, hi + 1, step))
         q[at:at + n] = np.where(col % 2 == 0, qa, qb)[None, :]
         at += n
     q[col[None, :] >= lens[:, None]] = 0
@@ -382,20 +401,33 @@ def _threads(oracle):
     return max(1, min(16, oracle.lib().pbo_max_threads()))
 
 
-def _oracle_rows(oracle, q, lens, alpha, sel):
+def _oracle_rows(oracle, q, lens, alpha, sel, mode=None):
     """(rows, nan) of the selected reads of a pool; rows = -1 for the others.  The oracle is the costly step (a read costs
-    length x rows cells), so a pool is first thinned with the model to the reads that can be of use."""
+    length x rows cells), so a pool is first thinned with the model to the reads that can be of use.  With a mode the rows
+    are those of the mode's CPU model (oracle.filter_batch_model) and `nan` marks the reads the mode hands to the exact pass."""
     rows = np.full(len(lens), -1, np.int32)
     nan = np.zeros(len(lens), bool)
     idx = np.nonzero(sel)[0]
-    if len(idx):
+    if len(idx) and mode is None:
         ee, _, _, r = oracle.filter_batch(np.ascontiguousarray(q[idx]), lens=lens[idx], alpha=alpha, threads=_threads(oracle))
         rows[idx], nan[idx] = r, np.isnan(ee)
+    elif len(idx):
+        # the oracle hands its threads 256 reads at a time and a pool of long reads is thinned to fewer than that, so the
+        # reads are dealt out here, one single-threaded call per worker (each read's result is its own: the same arrays)
+        def part(sub):
+            m = oracle.filter_batch_model(np.ascontiguousarray(q[sub]), mode, lens=lens[sub], alpha=alpha, threads=1)
+            return sub, m.rows, m.hand
+        order = idx[np.argsort(-lens[idx], kind="stable")]
+        workers = _threads(oracle)
+        with ThreadPoolExecutor(workers) as pool:
+            for sub, r, h in pool.map(part, [order[t::workers] for t in range(workers) if t < len(order)]):
+                rows[sub], nan[sub] = r, h
     return rows, nan
 
 
-def _main_like(oracle, name, kind, pool, alphas, wanted, rng):
-    """One batch per alpha from `pool`: the reads the model and the oracle put into a wanted main or wide cell."""
+def _main_like(oracle, name, kind, pool, alphas, wanted, rng, mode=None):
+    """One batch per alpha from `pool`: the reads the model and the oracle put into a wanted main or wide cell.  With a mode
+    the crossing row is the one of the mode's CPU model, and a read the mode hands to the exact pass is never picked."""
     q, lens = pool
     out = []
     codes = np.array(sorted(c[1] * 4096 + c[2] for c in wanted if c[0] == "main"), np.int64)
@@ -408,7 +440,7 @@ def _main_like(oracle, name, kind, pool, alphas, wanted, rng):
     for alpha in alphas:
         pred = rows_from_stats(stats, alpha)
         budgets = cap_of_rows(pred)
-        rows, nan = _oracle_rows(oracle, q, lens, alpha, np.isin(pred, need_j))
+        rows, nan = _oracle_rows(oracle, q, lens, alpha, np.isin(pred, need_j), mode)
         live = ~nan & (rows >= 1)
         code = budgets.astype(np.int64) * 4096 + rows - 1
         m = live & np.isin(code, codes) & (rows <= budgets)
@@ -466,16 +498,178 @@ def _generate(oracle):
     return batches
 
 
+# ---- MPB_FLAG_FAST_FMA and MPB_FLAG_ODDS: the same cells, by the mode's own crossing rows ---------------------------------
+
+P0_MIN_LOG2 = -900                                 # ODDS' range guard: a read with p0 < 2^-900 goes to the exact pass
+ODDS_LADDER_Q = tuple(range(3, 21))
+LONG_STRIDE_MAX = 16384                            # only the Q16 .. Q20 pool lies above it
+ODDS_FAR_MAX = 64                                  # candidates of that pool
+
+
+def q_bits(qv):
+    """-log2(1 - p) of a quality: what one base of it takes off log2 p0."""
+    return -math.log2(1.0 - 10.0 ** (-qv / 10.0))
+
+
+def odds_longest(qa, qb=None):
+    """About the most bases of alternating qualities qa, qb that keep p0 >= 2^-900 (the model has the last word)."""
+    per = (q_bits(qa) + q_bits(qa if qb is None else qb)) / 2
+    return int(-P0_MIN_LOG2 / per)
+
+
+def odds_bound(oracle):
+    """B: the largest model J over the uniform reads Q3 .. Q20, each at its longest length with p0 >= 2^-900, alpha 1e-5."""
+    if "B" not in _CACHE:
+        def longest_j(qv):
+            top = odds_longest(qv) + 2
+            lens = np.arange(top - 3, top + 1).astype(np.int32)         # the float estimate of the longest length, -1 .. +2
+            q = np.full((len(lens), 16 * ((top + 15) // 16)), qv, np.uint8)
+            q[np.arange(q.shape[1])[None, :] >= lens[:, None]] = 0
+            m = oracle.filter_batch_model(q, "odds", lens=lens, alpha=min(MODE_ALPHAS), threads=1)
+            ok = ~m.hand & (m.p0 >= 2.0 ** P0_MIN_LOG2)
+            assert ok[0] and not ok[-1], qv                               # the four lengths straddle the guard
+            return int(m.rows[ok].max())
+        with ThreadPoolExecutor(_threads(oracle)) as pool:
+            _CACHE["B"] = max(pool.map(longest_j, ODDS_LADDER_Q[::-1]))
+    return _CACHE["B"]
+
+
+def odds_unreachable(oracle):
+    """The main cells no read can fill under MPB_FLAG_ODDS: crossing row js needs J = js + 1 > B rows (odds_bound).
+    The mode keeps a read only while p0 = prod (1 - p_k) >= 2^-900, that is sum -ln(1 - p_k) <= 900 ln 2 = 623.8; with
+    -ln(1 - p) >= p the read's expected error count is sum p_k <= 623.8, its variance sum p_k (1 - p_k) is no larger, and J
+    grows with the mean: J <= about 624 + z sqrt(624) + (z^2 - 1) / 6 = 733 at z = Phi^-1(1 - 1e-5) = 4.26, the smallest alpha
+    the mode accepts.  Low error rates come closest (there -ln(1 - p) -> p and the variance -> the mean), and a read has at
+    most 65535 bases, so the ladder's Q20 read is about the best there is; B is measured, not taken from this estimate."""
+    B = odds_bound(oracle)
+    return [c for c in main_cells() if c[2] + 1 > B]
+
+
+def odds_cells(oracle):
+    bad = set(odds_unreachable(oracle))
+    return [c for c in main_cells() if c not in bad]
+
+
+def _long_specs(quals, stride, mean_lo, per_j=4):
+    """Reads of one quality (or two, alternating) up to the longest length the range guard lets through (and the stride), down
+    to the length at which the expected error count is mean_lo, about per_j lengths for every J."""
+    out = []
+    for qa, qb in quals:
+        pbar = (10.0 ** (-qa / 10.0) + 10.0 ** (-qb / 10.0)) / 2
+        hi = min(stride, odds_longest(qa, qb) + 2)
+        out.append((qa, qb, min(hi, int(mean_lo / pbar)), hi, max(1, int(1 / (per_j * pbar)))))
+    return out
+
+
+def _far_specs():
+    """The Q16 .. Q20 pool: sixteen lengths below each quality's longest, three for every J."""
+    out = []
+    for qv in (16, 17, 18, 20):
+        step = max(1, int(1 / (3 * 10.0 ** (-qv / 10.0))))
+        hi = odds_longest(qv)
+        out.append((qv, qv, hi - 15 * step, hi, step))
+    return out
+
+
+def mode_pools(mode):
+    """[(name, stride, specs, caps of the cells wanted from it)] of a mode's main-pass batches."""
+    short = [(qv, qv, 1, 960) for qv in range(1, 31)] + [(a, b, 1, 960) for a, b in [(1, 10), (3, 25), (2, 40)]]
+    if mode == "fma":              # the exact batches' pools
+        long_ = [(1, 1, 600, 1340), (2, 2, 780, 1700), (1, 2, 700, 1500), (1, 3, 800, 1640), (2, 3, 900, 1900),
+                 (1, 4, 800, 1800), (3, 3, 1000, 2040), (1, 5, 900, 1900)]
+        return [("main960", 960, short, (0, 512)), ("main2048", 2048, long_, (1024, 1024))]
+    return [("main960", 960, short, (0, 512)),
+            ("long2048", 2048, _long_specs([(3, 3), (4, 4), (5, 5), (6, 6), (3, 5), (4, 6)], 2048, 330, 2), (512, 1024)),
+            ("long8192", 8192, _long_specs([(8, 8), (9, 9), (10, 10), (11, 11), (8, 10)], 8192, 480, 2), (1024, 1024)),
+            ("long12288", 12288, _long_specs([(13, 13)], 12288, 560), (1024, 1024)),
+            ("far65536", 65536, _far_specs(), (1024, 1024))]
+
+
+def _generate_mode(oracle, mode):
+    rng = np.random.default_rng(SEED + 1 + MODES.index(mode))
+    cells = main_cells() if mode == "fma" else odds_cells(oracle)
+    batches = []
+    for name, stride, specs, (lo, hi) in mode_pools(mode):
+        want = {c for c in cells if lo <= c[1] <= hi}
+        batches += _main_like(oracle, "%s_%s" % (mode, name), "main", _uniform_pool(specs, stride), MODE_ALPHAS, want, rng, mode)
+    return batches
+
+
 _CACHE = {}
 
 
-def generate(oracle, fresh=False):
-    """The directed batches (main, wide, ovf kinds).  Cached per process; fresh=True generates again (determinism test)."""
+def generate(oracle, fresh=False, mode=None):
+    """The directed batches (main, wide, ovf kinds); with mode "fma" or "odds", the main-pass batches of that mode (kind main).
+    Cached per process; fresh=True generates again (determinism test)."""
+    make = (lambda: _generate(oracle)) if mode is None else (lambda: _generate_mode(oracle, mode))
     if fresh:
-        return _generate(oracle)
-    if "b" not in _CACHE:
-        _CACHE["b"] = _generate(oracle)
-    return _CACHE["b"]
+        return make()
+    key = "b" if mode is None else "b_" + mode
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+# ---- ODDS' range guard at its boundary, and the 1e-9 band around a read's limit ----------------------------------------------
+
+GUARD_CORES = {384: 1, 512: 3, 1024: 10}           # class -> the quality whose longest kept read crosses in that class
+GUARD_TRIM = (3, 6, 10, 13, 20, 30)                # coarse to fine: bases that bring log2 p0 to within 0.03 bit above -900
+GUARD_BAND = 0.05                                  # bits: every read of a ladder lies this close to 2^-900
+
+
+def range_guard_ladder(oracle, cap):
+    """(q, lens, kc): reads of class `cap` whose p0 steps across 2^-900.  A core of one low quality, a few trimming bases,
+    then k bases of Q40 -- each moves log2 p0 by 1.4e-4 -- for k around kc, the first k at which the float estimate of p0
+    falls below the guard (the model's p0, not this estimate, says on which side a read lies)."""
+    a, _ = oracle.lut()
+    bits = lambda qv: -math.log2(a[qv])
+    core = GUARD_CORES[cap]
+    quals = [core] * int((-P0_MIN_LOG2 - 1) / bits(core))
+    left = -P0_MIN_LOG2 - len(quals) * bits(core)
+    for qv in GUARD_TRIM:
+        k = max(0, int((left - 0.02) / bits(qv)))
+        quals += [qv] * k
+        left -= k * bits(qv)
+    assert 0.015 < left < 0.03, left
+    kc = int(left / bits(40)) + 1
+    span = int((GUARD_BAND - 0.01) / bits(40)) - kc
+    ks = sorted({0, kc - 64, kc - 8, kc - 3, kc - 2, kc - 1, kc, kc + 1, kc + 2, kc + 8, kc + 64, kc + span})
+    lens = np.array([len(quals) + k for k in ks], np.int32)
+    q = np.zeros((len(ks), 16 * ((int(lens.max()) + 15) // 16)), np.uint8)
+    q[:, :len(quals)] = np.array(quals, np.uint8)[None, :]
+    q[:, len(quals):] = 40
+    q[np.arange(q.shape[1])[None, :] >= lens[:, None]] = 0
+    return q, lens, kc
+
+
+def band_batch():
+    """(q, lens): 123 uniform and two-quality reads of 230 .. 330 bases at stride 336, of class 160 at alpha 0.005."""
+    return _uniform_pool([(3, 3, 230, 270), (4, 4, 290, 330), (2, 5, 240, 280)], 336)
+
+
+def band_picks(model, k=3):
+    """Reads whose model ee (ambigs ignore, no limit near) is far from an integer -- so that --round's own band stays out of
+    the way -- spread over the batch."""
+    e = model.ee_model
+    ok = np.flatnonzero(~model.hand & (np.abs(e - np.rint(e)) > 0.05) & (e > 100))
+    return [int(i) for i in ok[:: max(1, len(ok) // k)][:k]]
+
+
+BAND_FACTORS = ((0.5e-9, True), (2e-9, False))      # |limit / e - 1|, and whether the mode hands the read back there
+
+
+def model_ledger_mode(oracle, batches, mode, alpha=None):
+    """What a mode's batches fill under the predictor model's budgets and the mode model's rows: (main cells, thin cells)."""
+    main, thin = set(), set()
+    for b in batches:
+        if alpha is not None and b.alpha != alpha:
+            continue
+        m = oracle.filter_batch_model(b.q, mode, lens=b.lens, alpha=b.alpha, threads=_threads(oracle))
+        budgets = cap_of_rows(predicted_rows(b.q, b.lens, b.alpha))
+        main |= ledger_mode(m, budgets)
+        if b.stride <= 2048:
+            thin |= ledger_thin_mode(m, budgets)
+    return main, thin
 
 
 def model_ledger(oracle, batches):
