@@ -81,7 +81,7 @@ extern "C" {
                                     does not cross inside its class's rows; wide reads (more than 1024 rows); every read of a
                                     call that runs on a private table (scores above 254) or takes the one-read-per-wave path
                                     (mpb_filter_host: at most 4096 reads without MPB_FLAG_BATCHED_ONLY).  A call with the flag takes the sorted
-                                    pipeline, never the narrow pass.  The error grows like 1/alpha, as MPB_FLAG_FAST_FMA's does
+                                    pipeline, never the narrow pass (unless MPB_FLAG_ODDS_NARROW is set too).  The error grows like 1/alpha, as MPB_FLAG_FAST_FMA's does
                                     (worst relative difference of a numpy model over 1500 reads of 300 bases: 1.4e-12 at alpha
                                     1e-4, 1.3e-11 at 1e-5, 1.0e-10 at 1e-6; at most 5e-13 on the golden sets at alpha 0.005 ..
                                     0.5), so the flag is ACCEPTED ONLY FOR alpha >= 1e-5 (MPB_E_INVALID below), a factor of
@@ -118,6 +118,17 @@ extern "C" {
 #define MPB_FLAG_NARROW_SPLIT(c) (((uint32_t)(c) & 255u) << 12)   /* test / measurement hook, with MPB_FLAG_NARROW_ROWS(r >= 3) on a
                                     ragged batch: groups of the pass whose longest read has at most c 16-byte chunks run with r - 1
                                     rows ("mixed rows"; the library picks c from its sample by itself).  Results are identical. */
+
+#define MPB_FLAG_ODDS_NARROW (1u << 20)   /* opt-in, only together with MPB_FLAG_ODDS (alone: MPB_E_INVALID): mpb_filter_device may also
+                                    take the natural-order narrow pass, which then runs the one-FMA arithmetic (a lane keeps P0 and
+                                    w[1 .. R-1]; R operations per base instead of 3 R - 2).  Contract as MPB_FLAG_ODDS: ee within 1e-9
+                                    relative, ns / pass / NaN identical, decisions exact.  The pass hands a read back to the sorted
+                                    pipeline -- which runs it with MPB_FLAG_ODDS kept, so that n_overflow counts the ones the
+                                    three-rounding code recomputes -- when its CDF does not cross inside the R rows; when its P0 is
+                                    not >= 2^-900 (a lower-case 'n' makes it NaN); when its ee lies within 1e-9 * max(1, |ee|) of
+                                    its limit, or of an integer with MPB_FLAG_ROUND; and, in a ragged batch, when its length lies
+                                    outside its row.  No mixed rows in this form: MPB_FLAG_NARROW_SPLIT is ignored with the flag.
+                                    Everything that keeps a call out of the narrow pass still does.  Off by default. */
 
 /* kernel ids for mpb_kernel_time() */
 #define MPB_K_PREPASS   0   /* lambda/sigma/Ns estimate + row classing        */

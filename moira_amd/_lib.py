@@ -16,6 +16,7 @@ AMBIG = {"treat_as_errors": 0, "ignore": 1, "disallow": 2}
 FLAG_ROUND, FLAG_FAST_FMA, FLAG_TEST_UNDERPREDICT, FLAG_DECISION_ONLY, FLAG_BATCHED_ONLY, FLAG_COUNT_CELLS = 1, 2, 4, 8, 16, 32
 FLAG_NO_NARROW = 64
 FLAG_ODDS = 128                # MPB_FLAG_ODDS: one fma per DP cell in the sorted pipeline's main pass (ODDS_MODE.md)
+FLAG_ODDS_NARROW = 1 << 20     # MPB_FLAG_ODDS_NARROW: with FLAG_ODDS, the narrow pass may run too, in the one-fma form
 
 
 def FLAG_NARROW_ROWS(r):

@@ -21,6 +21,8 @@ LIB = os.path.join(HERE, "libmoira_pb.so")
 SOURCES = [os.path.join(CSRC, "mpb_kernels.hip"), os.path.join(CSRC, "mpb_api.cpp"), os.path.join(CSRC, "mpb_broker.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_host_internal.h"),
                   os.path.join(CSRC, "mpb_dp_tiles.inc"),
+                  os.path.join(CSRC, "mpb_narrow_ring.inc"), os.path.join(CSRC, "mpb_narrow_rs.inc"),
+                  os.path.join(CSRC, "mpb_narrow_rg.inc"),
                   os.path.join(CSRC, "libmoira_pb.map"),
                   os.path.join(ROOT, "include", "moira_pb.h"),
                   os.path.join(ROOT, "include", "mpb_synth.h")]

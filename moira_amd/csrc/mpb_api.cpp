@@ -617,6 +617,8 @@ static int check_params(const mpb_filter_params *p)
         return fail(MPB_E_INVALID, "MPB_FLAG_FAST_FMA needs alpha >= 1e-5 (its error bound does not hold below)");
     if ((p->flags & MPB_FLAG_ODDS) && (p->flags & MPB_FLAG_FAST_FMA))
         return fail(MPB_E_INVALID, "MPB_FLAG_ODDS and MPB_FLAG_FAST_FMA are two arithmetics for the same pass: set one");
+    if ((p->flags & MPB_FLAG_ODDS_NARROW) && !(p->flags & MPB_FLAG_ODDS))
+        return fail(MPB_E_INVALID, "MPB_FLAG_ODDS_NARROW needs MPB_FLAG_ODDS");
     if ((p->flags & MPB_FLAG_ODDS) && p->alpha < 1e-5)          // the same 1/alpha growth (include/moira_pb.h)
         return fail(MPB_E_INVALID, "MPB_FLAG_ODDS needs alpha >= 1e-5 (its error bound does not hold below)");
     const bool has_me = p->maxerrors == p->maxerrors;
@@ -766,12 +768,32 @@ static int ensure_narrow_workspace(mpb_ctx *c, int64_t n, bool ragged)
 // pipeline's cost x 1.05 + 1 -- since round 6 it runs through that pipeline where it lies (round 5 gathered it into a dense sub-batch:
 // x 1.3 + 3), so the pass wins up to about 40 % handed back (round 5: 20 %).  The pass must finish at least 55 % of the sample and
 // promise at least 5 %.
-static int narrow_rows_from_sample(const int32_t *hist, int n_sample)
+//
+// MPB_FLAG_ODDS_NARROW has constants of its own, in the same unit, fitted to the first of two runs of tools/odds_narrow_rate.py
+// (profiles/odds_narrow_rate_fit.txt; 10 M x 300, alternating options, 3 rounds x 20 steps; the second run, on another box 2-3 %
+// slower throughout, is profiles/odds_narrow_rate.json):
+//   the pass       forced R = 2 / 3 / 4 on the clean batch: 0.705 / 0.730 / 0.821 ms = 8.5 / 8.8 / 9.9 units; least squares 7.0 + 0.7 R
+//                  (a row is one operation here, and the pass is no longer bound by its arithmetic: ODDS_MODE.md)
+//   sorted + odds  the clean batch (every read in the class of cap 3): 1.638 ms = 19.7; BASELINE's reads: 28.8 per read from the slope
+//                  of the odds-alone step over the 5 / 20 / 40 % mixes (1.670 / 1.782 / 1.940 ms), config 2 as a whole 2.34 ms = 28.2
+//                  (ODDS_MODE.md); their mean cap is 9.6 by the exact constants (3.84 ms = 9 + 3.9 cap).  Two points: 15.7 + 1.34 cap
+//                  (k_dp_odds moves more than it computes on few-row classes: a larger intercept, a third of the slope)
+//   handed back    forced R = 2 on the mixes: the step less the pure pass is 0.194 / 0.553 / 1.032 ms for 0.50 / 2.00 / 4.00 M reads =
+//                  0.074 ms per call (0.9 units per read of the batch: the second pipeline's launches and its synchronisation) +
+//                  28.8 per read: the sorted cost itself, no factor
+// Flat Q30 and Q25-32 batches were not measured in this mode.  Checked on the second run: the model's R is the fastest forced option
+// on the clean batch, on every mix (R = 2 / 2 / 3 / 4 at 0 / 5 / 20 / 40 %) and on the ragged clean batch (R = 3), within 1 %.
+struct NarCostModel { double u0, u1, s0, s1, back_mul, back_add, back_call; };   // narrow u0 + u1 R; sorted s0 + s1 cap; a read handed
+                                                                                 // back: sorted x back_mul + back_add; any: back_call per read of the batch
+static const NarCostModel nar_cost_exact = {4.0, 3.0, 9.0, 3.9, 1.05, 1.0, 0.0};
+static const NarCostModel nar_cost_odds = {7.0, 0.7, 15.7, 1.34, 1.0, 0.0, 0.9};
+static int narrow_rows_from_sample(const int32_t *hist, int n_sample, bool odds = false)
 {
     if (n_sample <= 0) return 0;
-    auto sorted_cost = [](int r) {
+    const NarCostModel &m = odds ? nar_cost_odds : nar_cost_exact;
+    auto sorted_cost = [&m](int r) {
         const int cap = r == MPB_NAR_BUCKETS - 1 ? 30 : r <= 4 ? (r < 1 ? 2 : r + 1) : r;
-        return 9.0 + 3.9 * cap;
+        return m.s0 + m.s1 * cap;
     };
     const double lower_n_cost = sorted_cost(6);              // a read with a lower-case 'n' (handed back by the pass): a middling class
     double general = hist[0] * lower_n_cost;
@@ -782,8 +804,9 @@ static int narrow_rows_from_sample(const int32_t *hist, int n_sample)
         int64_t done = 0;
         for (int r = 1; r <= R; r++) done += hist[r];
         if ((double)done < 0.55 * n_sample) continue;
-        double cost = (double)n_sample * (4.0 + 3.0 * R) + hist[0] * (1.05 * lower_n_cost + 1.0);
-        for (int r = R + 1; r < MPB_NAR_BUCKETS; r++) cost += hist[r] * (1.05 * sorted_cost(r) + 1.0);
+        double cost = (double)n_sample * (m.u0 + m.u1 * R) + hist[0] * (m.back_mul * lower_n_cost + m.back_add);
+        for (int r = R + 1; r < MPB_NAR_BUCKETS; r++) cost += hist[r] * (m.back_mul * sorted_cost(r) + m.back_add);
+        if ((int64_t)n_sample > done) cost += (double)n_sample * m.back_call;
         if (cost < best_cost) { best = R; best_cost = cost; }
     }
     return best;
@@ -792,7 +815,8 @@ static int narrow_rows_from_sample(const int32_t *hist, int n_sample)
 // Fixed-length batches, and (round 6) ragged ones whose rows hold up to MPB_RG_MAX_STRIDE bytes (k_narrow_rg).
 static bool narrow_eligible(const mpb_ctx *c, int64_t n, int64_t row_stride, const int32_t *d_len, int32_t fixed_len, const mpb_filter_params *p)
 {
-    const uint32_t forbidden = MPB_FLAG_FAST_FMA | MPB_FLAG_ODDS | MPB_FLAG_TEST_UNDERPREDICT | MPB_FLAG_DECISION_ONLY | MPB_FLAG_COUNT_CELLS | MPB_FLAG_NO_NARROW;
+    uint32_t forbidden = MPB_FLAG_FAST_FMA | MPB_FLAG_ODDS | MPB_FLAG_TEST_UNDERPREDICT | MPB_FLAG_DECISION_ONLY | MPB_FLAG_COUNT_CELLS | MPB_FLAG_NO_NARROW;
+    if (p->flags & MPB_FLAG_ODDS_NARROW) forbidden &= ~MPB_FLAG_ODDS;      // the pass has a one-FMA form (check_params: the flag implies MPB_FLAG_ODDS)
     if (!(c->narrow_ok && n >= 1 && !(p->flags & forbidden) && c->ws.lut == c->d_lut)) return false;
     return d_len ? row_stride <= MPB_RG_MAX_STRIDE : fixed_len >= 1;
 }
@@ -824,7 +848,7 @@ static int narrow_choose(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t row_
     const int forced = (int)((params->flags >> 8) & 15u);
     if (forced) {
         *rows0 = forced < MPB_NAR_MIN_ROWS ? MPB_NAR_MIN_ROWS : forced > MPB_NAR_MAX_ROWS ? MPB_NAR_MAX_ROWS : forced;
-        *split = d_len ? (int)((params->flags >> 12) & 255u) : 0;          // MPB_FLAG_NARROW_SPLIT (test / measurement hook)
+        *split = d_len && !(params->flags & MPB_FLAG_ODDS_NARROW) ? (int)((params->flags >> 12) & 255u) : 0;   // MPB_FLAG_NARROW_SPLIT (test / measurement hook)
         return MPB_OK;
     }
     if (n < MPB_NAR_AUTO_MIN_READS) return MPB_OK;
@@ -841,8 +865,9 @@ static int narrow_choose(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t row_
     c->last_path.sampled = 1;
     int weight = 0;                                           // reads, or (ragged batches) their 16-byte chunks
     for (int k = 0; k < MPB_NAR_BUCKETS; k++) { c->last_path.sample_hist[k] = c->pin_words[16 + k]; weight += c->pin_words[16 + k]; }
-    *rows0 = narrow_rows_from_sample(c->pin_words + 16, weight);
-    if (d_len && *rows0 >= 3) {
+    const bool odds = (params->flags & MPB_FLAG_ODDS_NARROW) != 0;
+    *rows0 = narrow_rows_from_sample(c->pin_words + 16, weight, odds);
+    if (d_len && *rows0 >= 3 && !odds) {
         // mixed rows: the shortest sampled read that needs rows0 rows has `need` chunks; groups safely below it take a row less
         // (a sixteenth of margin and a chunk -- a cut that turns out too bold is dropped after the call that shows it, below; not
         // worth a second code path below four chunks)
@@ -872,7 +897,7 @@ static int filter_device_narrow(mpb_ctx *c, int rows0, int split, const uint8_t 
     if ((rc = ensure_narrow_workspace(c, n, d_len != nullptr))) return rc;
     { Span t(c, MPB_K_NARROW);
       mpb_launch_narrow(rows0, split, d_q, n, row_stride, fixed_len, d_len, prm, c->ws, d_ee, d_ns, d_pass, c->n_cu > 0 ? c->n_cu : 256,
-                        c->rg_per_cu, s); }
+                        c->rg_per_cu, s, (params->flags & MPB_FLAG_ODDS_NARROW) ? c->d_lut_odds : nullptr); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->pin_words, c->ws.nar_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -899,7 +924,8 @@ static int filter_device_narrow(mpb_ctx *c, int rows0, int split, const uint8_t 
             return filter_device_general(c, d_q, n, row_stride, d_len, fixed_len, prm.max_len, params, d_ee, d_ns, d_pass, counts);
         }
         mpb_filter_params sub = *params;
-        sub.flags = (sub.flags & ~((15u << 8) | (255u << 12))) | MPB_FLAG_NO_NARROW;
+        // (MPB_FLAG_ODDS stays: reads that only needed more rows get k_dp_odds, the ones the mode does not vouch for its overflow pass)
+        sub.flags = (sub.flags & ~((15u << 8) | (255u << 12) | MPB_FLAG_ODDS_NARROW)) | MPB_FLAG_NO_NARROW;
         if ((rc = filter_device_general(c, d_q, m, row_stride, d_len, fixed_len, prm.max_len, &sub, d_ee, d_ns, d_pass, nullptr, c->ws.nar_list, n))) return rc;
         HIPCHK(hipGetLastError());
     }

@@ -175,10 +175,7 @@
                 // MPB_FLAG_FAST_FMA and MPB_FLAG_ODDS keep the DECISIONS exact: an ee that lands within 1e-9 relative of
                 // the threshold (or, with --round, of an integer) is not trusted -- the read goes to the second
                 // pass, which always runs the three-rounding arithmetic
-                const double tol = 1e-9 * fmax(1.0, fabs(e));
-                bool unsure = fabs(e - mpb_limit(A.prm, li)) <= tol;
-                if (A.prm.flags & MPB_FLAG_ROUND) unsure = unsure || fabs(e - rint(e)) <= tol;
-                if (unsure) {
+                if (mode_unsure(A.prm, e, li)) {
                     if (A.final_pass == 0) { const int pos = atomicAdd(A.ovf_count, 1); A.ovf_list[pos] = idx; }
                     else A.pass[idx] = 2;
                     continue;

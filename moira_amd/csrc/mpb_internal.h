@@ -240,11 +240,14 @@ void mpb_launch_count(const uint8_t *pass, int64_t n, const MpbWorkspace &ws, hi
 // most that many 16-byte chunks run with rows0 - 1 rows).  Finished reads get ee / ns / pass; the others end up in ws.nar_list
 // (dense, in wave order; their number in ws.nar_count).  A persistent grid on n_cu CUs; rg_per_cu: the blocks per CU of the
 // MPB_NRG_FORMS ragged instantiations (mpb_narrow_rg_blocks_per_cu; only read for ragged batches).
+// lut_odds != nullptr (MPB_FLAG_ODDS | MPB_FLAG_ODDS_NARROW): the one-FMA twins (k_odds_nar, k_odds_nar_rs, k_odds_nar_rg) on that
+// {a, r = p / (1 - p)} table; no mixed rows then (split_chunks is ignored).
 #define MPB_RG_MAX_STRIDE 4096
-#define MPB_NRG_FORMS 5
+#define MPB_NRG_FORMS 8                   // k_narrow_rg's MPB_NRG_EXACT_FORMS instantiations, then k_odds_nar_rg<2..4>
+#define MPB_NRG_EXACT_FORMS 5
 void mpb_launch_narrow(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len,
                        const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int n_cu,
-                       const int *rg_per_cu, hipStream_t s);
+                       const int *rg_per_cu, hipStream_t s, const double2 *lut_odds = nullptr);
 void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS]);
 // predicted row budgets of `n_sample` reads spread over the batch -> ws.nar_sample (zeroed here)
 void mpb_launch_sample(const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len, const MpbDevParams &prm,

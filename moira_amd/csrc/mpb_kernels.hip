@@ -852,6 +852,16 @@ __device__ __forceinline__ bool read_result(const MpbDevParams &prm, bool crosse
     return mpb_round_and_keep(prm, e, has_n, li);
 }
 
+// MPB_FLAG_FAST_FMA and MPB_FLAG_ODDS keep the DECISIONS exact: an ee (after mpb_add_ns) that lands within 1e-9 relative of the read's
+// limit (or, with --round, of an integer) is not trusted -- the read goes to a pass that runs the three-rounding arithmetic.
+__device__ __forceinline__ bool mode_unsure(const MpbDevParams &prm, double e, int li)
+{
+    const double tol = 1e-9 * fmax(1.0, fabs(e));
+    bool unsure = fabs(e - mpb_limit(prm, li)) <= tol;
+    if (prm.flags & MPB_FLAG_ROUND) unsure = unsure || fabs(e - rint(e)) <= tol;
+    return unsure;
+}
+
 // Register budget of the DP kernel: 4 waves per SIMD = at most 128 VGPRs per lane.
 #define MPB_DP_WAVES_PER_EU 4
 
@@ -1753,6 +1763,46 @@ __device__ __forceinline__ void nar_run(double (&v)[R], uint32_t &nonzero, const
     }
 }
 
+// The same run in MPB_FLAG_ODDS_NARROW's form (ODDS_MODE.md "The narrow passes").  The table entry is {a, r = p / (1 - p)}; the
+// lane's registers are v[0] = p0 = prod a (the reference's row 0, in base order) and v[j] = w[j], the coefficients of
+// prod (1 + r x), j = 1 .. R-1; w[0] is the constant 1 and costs nothing.  Per base: p0 *= a, w[j] = fma(r, w[j-1], w[j]) from the
+// last row down (so every w[j-1] is the previous base's), w[1] += r: R operations where nar_run has 3 R - 2, in R chains that each
+// wait for their own value of the base before.  Within a base the chains are independent, and a chain's next link is R
+// instructions behind; the wave's other 3 chains and the SIMD's other waves fill the 8-9 cycles a dependent FP64 operation waits.
+// The chains are never split or re-associated: the bits are the CPU model's.  Same look-ahead (the table two dwords ahead) and
+// the same 'N' counting instruction as nar_run (at the head of the run); the fences keep the table reads where they are written.
+#define MPB_NAR_ODDS_FENCED 1
+template <int R, int ND>
+__device__ __forceinline__ void nar_run_odds(double (&v)[R], uint32_t &nonzero, const nar_entry_t *s_p, const uint32_t (&wd)[16])
+{
+    nar_entry_t P[ND + 2][4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) P[0][t] = NAR_LOOKUP(wd[0], t);
+    __builtin_amdgcn_sched_barrier(0);
+    // the run's 'N' count here, while the first entries are on their way and the look-ahead's registers are still free (inside the
+    // loop the count's temporary is one register more than the exact form's, whose products leave it one)
+#pragma unroll
+    for (int d = 0; d < ND; d++) nonzero = __builtin_amdgcn_msad_u8(wd[d] ^ 0x01010101u, wd[d], nonzero);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 4; t++) P[1][t] = NAR_LOOKUP(wd[1], t);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int d = 0; d < ND; d++) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const double a = NAR_A(P[d][t]), rr = NAR_P(P[d][t]);
+#pragma unroll
+            for (int r = R - 1; r >= 2; r--) v[r] = __builtin_fma(rr, v[r - 1], v[r]);
+            v[1] = v[1] + rr;                                   // fma(rr, 1, w[1]): the same bits
+            v[0] = v[0] * a;
+            if (MPB_NAR_ODDS_FENCED) __builtin_amdgcn_sched_barrier(0);
+            if (d < ND - 2) P[d + 2][t] = NAR_LOOKUP(wd[d + 2], t);
+            if (MPB_NAR_ODDS_FENCED) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
 // NC 16-byte chunks of the lane's read (chunk(c): where chunk c lies in LDS) into registers.  Chunks from `full` on (the first
 // `full` are complete in every lane: wave-uniform) are masked by the lane's own `nb` bases from the first chunk on: the bytes
 // past its end become zero -- the identity step, so a read's last bases take the same code as the others, and 'N' bases =
@@ -1774,18 +1824,25 @@ __device__ __forceinline__ void nar_load(uint32_t (&wd)[16], const Chunk &chunk,
 
 struct NarNothing { __device__ void operator()() const {} };
 
+template <int R, int ND, int AR>
+__device__ __forceinline__ void nar_run_ar(double (&v)[R], uint32_t &nonzero, const nar_entry_t *s_p, const uint32_t (&wd)[16])
+{
+    if constexpr (AR == MPB_AR_ODDS) nar_run_odds<R, ND>(v, nonzero, s_p, wd);
+    else nar_run<R, ND>(v, nonzero, s_p, wd);
+}
+
 // One run of nch chunks (1..4, wave-uniform) of the lane's read: nar_load, then `loaded()` (k_narrow: its ring slot is free
-// again), then nar_run<R, 4 nch>.
-template <int R, bool UNIFORM, typename Chunk, typename Loaded = NarNothing>
+// again), then nar_run<R, 4 nch> (AR == MPB_AR_ODDS: nar_run_odds).
+template <int R, bool UNIFORM, int AR = MPB_AR_EXACT, typename Chunk, typename Loaded = NarNothing>
 __device__ __forceinline__ void nar_chunks(double (&v)[R], uint32_t &nonzero, const nar_entry_t *s_p, const Chunk &chunk, int nch,
                                            int full, int nb, const Loaded &loaded = Loaded())
 {
     uint32_t wd[16];
     switch (nch) {
-    case 4: nar_load<4, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 16>(v, nonzero, s_p, wd); break;
-    case 3: nar_load<3, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 12>(v, nonzero, s_p, wd); break;
-    case 2: nar_load<2, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 8>(v, nonzero, s_p, wd); break;
-    default: nar_load<1, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run<R, 4>(v, nonzero, s_p, wd); break;
+    case 4: nar_load<4, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run_ar<R, 16, AR>(v, nonzero, s_p, wd); break;
+    case 3: nar_load<3, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run_ar<R, 12, AR>(v, nonzero, s_p, wd); break;
+    case 2: nar_load<2, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run_ar<R, 8, AR>(v, nonzero, s_p, wd); break;
+    default: nar_load<1, UNIFORM>(wd, chunk, full, nb); loaded(); nar_run_ar<R, 4, AR>(v, nonzero, s_p, wd); break;
     }
 }
 
@@ -1795,10 +1852,44 @@ __device__ __forceinline__ void nar_chunks(double (&v)[R], uint32_t &nonzero, co
 // never crosses) is appended to the wave's segment, in lane order.  The crossing is cdf_cross's loop written out, as k_narrow_rg
 // needs it (called there, cdf_cross spilled 3 more VGPRs inside the panel loop).
 struct NarRead { bool done, keep; int nsv; double e; };
+
+// The end of a read in MPB_FLAG_ODDS_NARROW's form: v[0] = p0, v[1 .. R-1] = w[1 .. R-1], w[0] = 1.  The sequential CDF of w against
+// thr / p0 (one division), cross_ee_odds, mpb_add_ns, mpb_round_and_keep: the expressions of the sorted pipeline's odds bodies
+// (mpb_dp_tiles.inc), so the bits are the same whichever pass finishes a read.  false: the pass hands the read back -- its CDF does not
+// cross inside the R rows, its p0 is not >= 2^-900 (a lower-case 'n': NaN), or its ee is one the mode does not vouch for
+// (mode_unsure).  With R <= 4 the range guard never finishes a read wrongly (w[<= 3] stays tiny); it is here so that the
+// hand-back rule is one rule on every path.
 template <int R>
+__device__ __forceinline__ bool nar_odds_result(const double (&v)[R], const MpbDevParams &prm, int nsv, int li, double &e, bool &keep)
+{
+    const double p0 = v[0], thr = prm.thr / p0;
+    double acc = 0.0, lo = 0.0, hi = 0.0;
+    int js = -1;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const double na = acc + (r == 0 ? 1.0 : v[r]);
+        const bool hit = (js < 0) && (na > thr);
+        lo = hit ? acc : lo;
+        hi = hit ? na : hi;
+        js = hit ? r : js;
+        acc = na;
+    }
+    if (!(js >= 0 && p0 >= 0x1p-900)) return false;
+    e = mpb_add_ns(prm, cross_ee_odds(true, js, prm.thr, p0, lo, hi), nsv);
+    if (mode_unsure(prm, e, li)) return false;
+    keep = mpb_round_and_keep(prm, e, nsv > 0, li);
+    return true;
+}
+
+template <int AR = MPB_AR_EXACT, int R>
 __device__ __forceinline__ NarRead nar_finish(double (&v)[R], uint32_t &nonzero, const MpbDevParams &prm, bool valid, bool good,
                                               int li, int64_t i, int32_t *my_seg, int &nlist, int lane)
 {
+    NarRead o;
+    if constexpr (AR == MPB_AR_ODDS) {
+        o.nsv = li - (int)nonzero;
+        o.done = good && nar_odds_result(v, prm, o.nsv, li, o.e, o.keep);
+    } else {
     double acc = 0.0, lo = 0.0, hi = 0.0;
     int js = -1;
 #pragma unroll
@@ -1810,10 +1901,10 @@ __device__ __forceinline__ NarRead nar_finish(double (&v)[R], uint32_t &nonzero,
         js = hit ? r : js;
         acc = na;
     }
-    NarRead o;
     o.done = good && js >= 0;
     o.nsv = li - (int)nonzero;                                       // 'N' bases (a read with an 'n' is never done)
     if (o.done) o.keep = read_result(prm, true, js, lo, hi, o.nsv, o.nsv > 0, li, o.e);
+    }
     const unsigned long long todo = __ballot(valid && !o.done);
     if (todo) {
         if (valid && !o.done) my_seg[nlist + __popcll(todo & ((1ull << lane) - 1ull))] = (int32_t)i;
@@ -1853,6 +1944,11 @@ __device__ __forceinline__ void nar_tile_fence()
 }
 
 
+// The three kernels' bodies are include files (mpb_narrow_ring.inc, mpb_narrow_rs.inc, mpb_narrow_rg.inc), compiled here with the
+// reference's arithmetic and, behind k_nar_compact, a second time as the one-FMA twins of MPB_FLAG_ODDS_NARROW.
+#define MPB_NAR_AR MPB_AR_EXACT
+#define MPB_NAR_RLO RLO
+
 // (Rows whose stride is a multiple of 64 bytes take k_narrow_rs below since the second session of round 5; a form of this
 // kernel that fetched the line a row pair shares only once -- tail buffers beside the ring, -DMPB_NAR_TAILS -- is in the
 // history: 4.03 -> 3.49 GB read, 6 % slower.)
@@ -1861,121 +1957,7 @@ __global__ __launch_bounds__(256) void k_narrow(const uint8_t *__restrict__ q, i
                                                 MpbDevParams prm, const double2 *__restrict__ lut_g,
                                                 double *__restrict__ ee, int32_t *__restrict__ ns, uint8_t *__restrict__ pass,
                                                 int32_t *__restrict__ seg, int32_t *__restrict__ wave_count)
-{
-    // seg / wave_count: the reads this pass cannot finish.  A wave appends them to a segment of its own -- wave gw owns the
-    // slots of the row blocks it walks, which start at 64 * (blocks owned by the waves before it) -- and leaves its count in
-    // wave_count[gw]: no atomic (a returned atomic would drain the prefetch stream: vmcnt counts everything), and a list whose
-    // order does not depend on timing.  k_nar_compact then makes the dense list.
-    static_assert(D >= 2 && D <= 4, "ring depth");
-    __shared__ nar_entry_t s_p[256];
-    // one array per ring slot: a read of slot k is then provably independent of a DMA into slot k + 1 (the compiler orders
-    // LDS reads behind LDS-DMA by what may alias)
-    __shared__ __attribute__((aligned(16))) uint8_t s_ring0[4][MPB_NAR_PANEL];
-    __shared__ __attribute__((aligned(16))) uint8_t s_ring1[4][MPB_NAR_PANEL];
-    __shared__ __attribute__((aligned(16))) uint8_t s_ring2[D > 2 ? 4 : 1][D > 2 ? MPB_NAR_PANEL : 16];
-    __shared__ __attribute__((aligned(16))) uint8_t s_ring3[D > 3 ? 4 : 1][D > 3 ? MPB_NAR_PANEL : 16];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    nar_stage_table(s_p, lut_g, tid);
-    const int64_t nblk = (n + 63) >> 6;                       // row blocks of 64 reads
-    const int ncq = (li + 63) >> 6;                           // 64-byte panels per row block (li >= 1)
-    const int64_t gw = (int64_t)blockIdx.x * 4 + w, W = (int64_t)gridDim.x * 4;
-    if (gw >= nblk) {
-        if (lane == 0) wave_count[gw] = 0;
-        return;
-    }
-    const int64_t total = ((nblk - gw + W - 1) / W) * ncq;    // panels this wave walks
-    int32_t *const my_seg = seg + 64 * (gw * (nblk / W) + min(gw, nblk % W));
-    int nlist = 0;                                            // wave-uniform
-    const int r16 = lane & 15, cl = lane >> 4;
-    const int row_chunks = __builtin_amdgcn_readfirstlane((int)(stride >> 4));
-    uint32_t voff[4];
-#pragma unroll
-    for (int rg = 0; rg < 4; rg++) voff[rg] = (uint32_t)((rg * 16 + r16) * (int)stride + cl * 16);
-    uint8_t *const ring[4] = {s_ring0[w], s_ring1[w], s_ring2[D > 2 ? w : 0], s_ring3[D > 3 ? w : 0]};
-    const uint32_t ring_lds[4] = {lds_offset(s_ring0[w]), lds_offset(s_ring1[w]), lds_offset(s_ring2[D > 2 ? w : 0]),
-                                  lds_offset(s_ring3[D > 3 ? w : 0])};
-
-    // one panel = four DMA instructions, always four (the waits below count them)
-    auto issue = [&](const int64_t b, const int c, const uint32_t slot) {
-        const uint8_t *base = q + b * 64 * stride + c * 64;                        // wave-uniform
-        const bool edge = (b * 64 + 64 > n) || (c * 4 + 4 > row_chunks);          // wave-uniform
-        if (!edge) {
-#pragma unroll
-            for (int rg = 0; rg < 4; rg++) nar_dma16(base, voff[rg], slot + rg * 1024);
-        } else {
-            // last row block of the batch / last chunk column of a row whose stride is not a multiple of 64: rows and chunks
-            // clamped into the matrix (what they deliver is never looked at)
-            const int last_row = (int)(n - 1 - b * 64);                            // >= 0: the block holds at least one read
-            const int ch = min(cl, row_chunks - 1 - c * 4);                        // >= 0: the panel starts inside the row
-#pragma unroll
-            for (int rg = 0; rg < 4; rg++)
-                nar_dma16(base, (uint32_t)(min(rg * 16 + r16, last_row) * (int)stride + ch * 16), slot + rg * 1024);
-        }
-    };
-
-    int64_t pf_b = gw, cur_b = gw;            // row block of the next panel to request / being computed
-    int pf_c = 0, cur_c = 0;
-    int64_t pf = 0;                           // panels requested so far
-    auto request = [&](const uint32_t slot) {
-        if (pf < total) {
-            issue(pf_b, pf_c, slot);
-            pf++;
-            if (++pf_c == ncq) { pf_c = 0; pf_b += W; }
-        }
-    };
-#pragma unroll
-    for (int k = 0; k < D - 1; k++) request(ring_lds[k]);
-    // A panel's slot is free as soon as its 64 bytes per lane are in registers -- at the START of its step, not at the end: the
-    // request that refills it is made right behind those reads, so D panels are in flight while one is computed on, not D - 1
-    // (what a CU can have in flight is what bounds the stream, and LDS capacity is what bounds that: profiles/r05_narrow_variants.txt).
-    request(ring_lds[D - 1]);
-
-    double v[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-    const uint32_t tl = (uint32_t)((lane >> 4) * 1024 + (lane & 15) * 16);      // this lane's row inside a panel
-    uint32_t nonzero = 0;
-
-    auto step = [&](const int S, const int64_t s) {
-        (void)s;
-        // the panel of this step has landed when at most the requests made after it are still out
-        const int64_t younger = pf - (s + 1);               // 0 .. D-1 panels (wave-uniform)
-        {
-        if (younger >= 3) nar_wait<12>();
-        else if (younger == 2) nar_wait<8>();
-        else if (younger == 1) nar_wait<4>();
-        else nar_wait<0>();
-        }
-        // The lane's chunks of the panel -- all four, or (the last panel of a row whose length is no multiple of 64) those the read
-        // reaches, the bytes past its end masked -- in registers; the slot is free then, and refilled before the run starts.
-        const uint8_t *mine = ring[S] + tl;
-        const int nbases = min(64, li - cur_c * 64);        // wave-uniform
-        nar_chunks<R, true>(v, nonzero, s_p, [&](const int c) { return mine + c * 256; }, (nbases + 15) >> 4, nbases >> 4, nbases, [&] {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            request(ring_lds[S]);
-        });
-        if (++cur_c == ncq) {
-            const int64_t i = cur_b * 64 + lane;
-            const bool valid = i < n;
-            const NarRead r = nar_finish(v, nonzero, prm, valid, valid, li, i, my_seg, nlist, lane);
-            if (r.done) {
-                ee[i] = r.e;
-                ns[i] = r.nsv;
-                pass[i] = (uint8_t)(r.keep ? 1 : 0);
-            }
-            cur_c = 0;
-            cur_b += W;
-        }
-    };
-    for (int64_t s = 0; s < total; s += D) {
-        step(0, s);
-        if (D > 1 && s + 1 < total) step(1 % D, s + 1);
-        if (D > 2 && s + 2 < total) step(2 % D, s + 2);
-        if (D > 3 && s + 3 < total) step(3 % D, s + 3);
-    }
-    if (lane == 0) wave_count[gw] = nlist;
-}
+#include "mpb_narrow_ring.inc"
 
 // ------------------------------------------------------------------------------------------
 // k_narrow_rs<R>: the narrow pass with the panel stream staged in REGISTERS and every request a whole, aligned 128-byte line
@@ -2000,137 +1982,7 @@ __global__ __launch_bounds__(256) void k_narrow_rs(const uint8_t *__restrict__ q
                                                    MpbDevParams prm, const double2 *__restrict__ lut_g,
                                                    double *__restrict__ ee, int32_t *__restrict__ ns, uint8_t *__restrict__ pass,
                                                    int32_t *__restrict__ seg, int32_t *__restrict__ wave_count)
-{
-    __shared__ nar_entry_t s_p[256];
-    __shared__ __attribute__((aligned(128))) uint8_t s_tile[4][MPB_NRS_TILE];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    nar_stage_table(s_p, lut_g, tid);
-    const int64_t rows_sb = 64 * (int64_t)k;                  // reads of a stream block: 64 lanes x k reads each
-    const int64_t nsb = (n + rows_sb - 1) / rows_sb;
-    const int KB = __builtin_amdgcn_readfirstlane((int)(k * stride));      // bytes of a lane's stream: a multiple of 128
-    const int NP = KB >> 7;                                   // its panels
-    const int istride = __builtin_amdgcn_readfirstlane((int)stride);
-    const int64_t gw = (int64_t)blockIdx.x * 4 + w, W = (int64_t)gridDim.x * 4;
-    if (gw >= nsb) {
-        if (lane == 0) wave_count[gw] = 0;
-        return;
-    }
-    const int64_t total = ((nsb - gw + W - 1) / W) * NP;      // panels this wave walks
-    int32_t *const my_seg = seg + rows_sb * (gw * (nsb / W) + min(gw, nsb % W));
-    int nlist = 0;                                            // wave-uniform
-    uint8_t *const tile = s_tile[w];
-    const int r8 = lane >> 3, c8 = lane & 7;                  // stream 8 j + r8 of load instruction j: the lane's slot c8 of panel bytes
-    const int voff = r8 * KB + c8 * 16;
-    int wr_even, wr_odd, x0;
-    nar_tile_lane(lane, wr_even, wr_odd, x0);
-
-    u32x4 pre[8];
-    auto load_panel = [&](const int64_t sb, const int pk) {
-        const uint64_t base = (uint64_t)(uintptr_t)q + (uint64_t)(sb * rows_sb) * (uint64_t)stride;
-        const int64_t rows_here = (n - sb * rows_sb) < rows_sb ? (n - sb * rows_sb) : rows_sb;
-        const uint32_t b_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-        const uint32_t b_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
-        const uint32_t b_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(rows_here * stride));
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(uintptr_t)(((uint64_t)b_hi << 32) | b_lo), 0, (int)b_n, 0x00020000);
-#pragma unroll
-        for (int j = 0; j < 8; j++) pre[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, j * 8 * KB + pk * 128, 0);
-    };
-    int64_t pf_sb = gw, cur_sb = gw;
-    int pf_pk = 0, cur_pk = 0;
-    load_panel(pf_sb, pf_pk);
-    if (++pf_pk == NP) { pf_pk = 0; pf_sb += W; }
-
-    double v[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-    uint32_t nonzero = 0;
-    int u = 0, sread = 0;                                      // position in the stream: byte u of its read number sread (wave-uniform)
-
-    // ---- a read is done: nar_finish.  Two reads per lane: result arrays aligned for a lane's pair (R <= 3 only: with four rows the
-    // held results do not fit the 128 registers of four waves per SIMD)
-    const bool pair_stores = R <= 3 && k == 2 && (((uintptr_t)ee & 15) | ((uintptr_t)ns & 7) | ((uintptr_t)pass & 1)) == 0;
-    double held_e = 0.0;
-    int held_ns = 0;
-    uint8_t held_ps = 0;
-    bool held_ok = false;
-    auto finish = [&](const int64_t sb, const int sr) {
-        const int64_t i = sb * rows_sb + (int64_t)lane * k + sr;
-        const NarRead r = nar_finish(v, nonzero, prm, i < n, i < n, li, i, my_seg, nlist, lane);
-        if (r.done) {
-            const double e = r.e;
-            const int nsv = r.nsv;
-            const uint8_t ps = (uint8_t)(r.keep ? 1 : 0);
-            if (pair_stores && sr == 0) {
-                // two reads per lane: the first one's results wait in registers for the second's, and go out together -- 16 + 8 + 2
-                // contiguous bytes per lane instead of two half-used sectors a panel and a half apart (writes 0.26 -> 0.13 GB)
-                held_e = e; held_ns = nsv; held_ps = ps;
-            } else if (pair_stores && held_ok) {
-                *reinterpret_cast<double2 *>(ee + i - 1) = make_double2(held_e, e);
-                *reinterpret_cast<int2 *>(ns + i - 1) = make_int2(held_ns, nsv);
-                *reinterpret_cast<uint16_t *>(pass + i - 1) = (uint16_t)(held_ps | ((uint16_t)ps << 8));
-            } else {
-                ee[i] = e;
-                ns[i] = nsv;
-                pass[i] = ps;
-            }
-        }
-        if (pair_stores) {
-            if (sr == 0) held_ok = r.done;
-            else if (held_ok && !r.done) { ee[i - 1] = held_e; ns[i - 1] = held_ns; pass[i - 1] = held_ps; }   // the second one is handed back (or past the end)
-        }
-    };
-    for (int64_t t = 0; t < total; t++) {
-        // the panel requested one panel ago -> tile (the tile's last reads were issued before: LDS runs a wave's operations in order)
-        nar_tile_write(tile, wr_even, wr_odd, pre);
-        nar_tile_fence();
-        if (t + 1 < total) {                                    // in flight while this panel is computed on
-            load_panel(pf_sb, pf_pk);
-            if (++pf_pk == NP) { pf_pk = 0; pf_sb += W; }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- the panel's two 64-byte halves, four 16-byte chunks each.  The chunks of a half that belong to ONE read go through
-        // one run (nar_chunks), so a 300-base read's last 44 bases take the same code as the others, as 48.  A read may end -- and the
-        // next one begin -- anywhere a chunk does (strides that are no multiple of 64): then the half is several runs; row
-        // padding is skipped by whole chunks.  All of it wave-uniform.
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            if (ALIGNED) {
-                // rows of a multiple of 64 bytes: a read starts with a half, so a half holds chunks of ONE read -- one run, every
-                // address a constant (the form measured in profiles/r05_narrow_variants.txt; the loop below costs it 2-3 %)
-                const int nb = li - u;                          // bases of the current read from this half on
-                if (nb > 0) {
-                    nar_chunks<R, true>(v, nonzero, s_p, [&](const int c) { return tile + (x0 ^ ((h * 4 + c) << 4)); }, nb >= 64 ? 4 : (nb + 15) >> 4, nb >> 4, nb);
-                    if (nb <= 64) finish(cur_sb, sread);
-                }
-                u += 64;
-                if (u == istride) { u = 0; sread++; }
-                continue;
-            }
-            int p = 0;                                          // chunk of this half
-            while (p < 4) {
-                const int nb = li - u;                          // bases of the current read from here on
-                if (nb <= 0) {                                  // its padding: on to the next read, or to the end of the half
-                    const int skip = min((istride - u) >> 4, 4 - p);
-                    p += skip;
-                    u += 16 * skip;
-                } else {
-                    const int nch = min((nb + 15) >> 4, 4 - p); // chunks of this read in what is left of the half
-                    const int c0 = h * 4 + p;
-                    nar_chunks<R, true>(v, nonzero, s_p, [&](const int c) { return tile + (x0 ^ ((c0 + c) << 4)); }, nch, nb >> 4, nb);
-                    p += nch;
-                    u += 16 * nch;
-                    if (16 * nch >= nb) finish(cur_sb, sread);  // the read is done (u may stand in its padding now)
-                }
-                if (u >= istride) { u = 0; sread++; }
-            }
-        }
-        if (++cur_pk == NP) { cur_pk = 0; cur_sb += W; sread = 0; }
-        nar_tile_fence();                                       // the tile is overwritten by the next panel
-    }
-    if (lane == 0) wave_count[gw] = nlist;
-}
+#include "mpb_narrow_rs.inc"
 
 // ------------------------------------------------------------------------------------------
 // k_narrow_rg<R>: the narrow pass for RAGGED batches (round 6: one padded matrix + int32 len[], e.g. the contigs the
@@ -2354,150 +2206,7 @@ __global__ __launch_bounds__(256, 4) void k_narrow_rg(const uint8_t *__restrict_
                                                    MpbDevParams prm, const double2 *__restrict__ lut_g,
                                                    double *__restrict__ ee, int32_t *__restrict__ ns, uint8_t *__restrict__ pass,
                                                    int32_t *__restrict__ seg, int32_t *__restrict__ wave_count)
-{
-    __shared__ nar_entry_t s_p[256];
-    __shared__ __attribute__((aligned(128))) uint8_t s_tile[4][MPB_NRS_TILE];
-    __shared__ uint32_t s_row[4][64];                         // byte offsets of the rows of the group being loaded, from its window's base
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    nar_stage_table(s_p, lut_g, tid);
-    const int gw = blockIdx.x * 4 + w;
-    const int ngroups = (int)((n + 63) >> 6), nwin = (int)((n + MPB_RG_WIN - 1) / MPB_RG_WIN), nwaves = (int)gridDim.x * 4;
-    const int g0 = __builtin_amdgcn_readfirstlane(rg_first_group(wpre, gpre, nwin, ngroups, gw, nwaves, lane));
-    const int g1 = __builtin_amdgcn_readfirstlane(rg_first_group(wpre, gpre, nwin, ngroups, gw + 1, nwaves, lane));
-    if (lane == 0) gstart[gw] = g0;                           // (where the wave's list segment starts: k_nar_compact)
-    if (g0 >= g1) {
-        if (lane == 0) wave_count[gw] = 0;
-        return;
-    }
-    int32_t *const my_seg = seg + 64 * (int64_t)g0;
-    int nlist = 0;                                            // wave-uniform
-    uint8_t *const tile = s_tile[w];
-    const int istride = __builtin_amdgcn_readfirstlane((int)stride);
-    const int r8 = lane >> 3, c8 = lane & 7;                  // stream 8 j + r8 of load instruction j: the lane's row
-    int wr_even, wr_odd, x0;
-    nar_tile_lane(lane, wr_even, wr_odd, x0);
-
-    // a group's order entries {read, length}: -1 / -1 past the batch or past the wave's range; length -1: outside 0..max_len
-    auto fetch = [&](const int g, int &idx, int &ln) {
-        const int64_t p = (int64_t)g * 64 + lane;
-        unsigned long long e = ~0ull;                           // {-1, -1}
-        if (g < g1 && p < n) e = gload(reinterpret_cast<const unsigned long long *>(ord) + p);
-        idx = (int)(uint32_t)e; ln = (int)(uint32_t)(e >> 32);
-    };
-    int cur_idx, cur_len, nx_idx, nx_len, nn_idx, nn_len;
-    fetch(g0, cur_idx, cur_len);
-    fetch(g0 + 1, nx_idx, nx_len);
-    fetch(g0 + 2, nn_idx, nn_len);
-
-    // arming a group for loading: per-lane row offsets from the window's base, the group's chunks (longest read) and the
-    // chunks complete in every lane (shortest)
-    uint32_t *const rows = s_row[w];
-    const uint8_t *wbase = q;
-    int ld_maxc = 0, ld_full = 0;
-    auto arm = [&](const int g, const int idx, const int ln) {
-        const int64_t wrow = ((int64_t)g * 64) & ~(int64_t)(MPB_RG_WIN - 1);          // first row of the group's window
-        wbase = q + wrow * stride;
-        const bool good = idx >= 0 && ln >= 0;
-        const int rowoff = idx >= 0 ? (int)(idx - wrow) * istride : 0;                // (rows past the batch: the window's first)
-        int mx = good ? (ln + 15) >> 4 : 0, mn = good ? ln >> 4 : 0x7fffffff;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { mx = max(mx, __shfl_xor(mx, off)); mn = min(mn, __shfl_xor(mn, off)); }
-        ld_maxc = __builtin_amdgcn_readfirstlane(mx);
-        ld_full = __builtin_amdgcn_readfirstlane(mn);
-        rows[lane] = (uint32_t)rowoff;                          // (the loads of the group before this one have all been issued)
-    };
-    u32x4 pre[8];
-    auto load_panel = [&](const int pk) {
-        const uint8_t *pb = wbase + pk * 128;                   // wave-uniform
-        uint32_t voff[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) voff[j] = rows[8 * j + r8] + (uint32_t)(c8 * 16);
-        if (8 * pk + c8 < ld_maxc) {                            // (the group's last panel: only the chunks its longest read has)
-#pragma unroll
-            for (int j = 0; j < 8; j++) pre[j] = *(const __attribute__((address_space(1))) u32x4 *)(pb + voff[j]);
-        }
-    };
-    arm(g0, cur_idx, cur_len);
-    int cur_maxc = ld_maxc, cur_full = ld_full;
-    load_panel(0);
-
-    double v[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-    uint32_t nonzero = 0;
-
-    for (int g = g0; g < g1; g++) {
-        const int np = __builtin_amdgcn_readfirstlane(max(1, (cur_maxc + 7) >> 3));      // panels of this group
-        for (int pk = 0; pk < np; pk++) {
-            nar_tile_write(tile, wr_even, wr_odd, pre);
-            nar_tile_fence();
-            {
-                int next_pk = pk + 1;
-                const bool next_group = next_pk == np && g + 1 < g1;
-                if (next_group) { arm(g + 1, nx_idx, nx_len); next_pk = 0; }
-                if (next_pk < np || next_group) load_panel(next_pk);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int cb = 8 * pk + 4 * h;                   // first chunk of this half
-                const int rem = cur_maxc - cb;                   // chunks of the group's longest read from here on
-                if (rem <= 0) continue;
-                const int fullc = cur_full - cb;                 // ... that are complete in every lane
-                const int nbl = cur_len - 16 * cb;               // this lane's bases from here on (may be <= 0)
-                const auto chunk = [&](const int c) { return tile + (x0 ^ ((h * 4 + c) << 4)); };
-                if (RLO < R && cur_maxc <= split) {               // a short group: rows 0 .. RLO-1 only (v[RLO ..] stay zero)
-                    double (&vl)[RLO] = *reinterpret_cast<double (*)[RLO]>(&v[0]);
-                    nar_chunks<RLO, false>(vl, nonzero, s_p, chunk, rem >= 4 ? 4 : rem, fullc, nbl);
-                } else {
-                    nar_chunks<R, false>(v, nonzero, s_p, chunk, rem >= 4 ? 4 : rem, fullc, nbl);
-                }
-            }
-            nar_tile_fence();                                   // the tile is overwritten by the next panel
-        }
-        // ---- the group is done: nar_finish written out, with the lane's own length (and a length outside 0..max_len is handed back).
-        // This kernel sits at its register cap: through the helper it needs a VGPR more at R = 2 and 4 more bytes of spill at R = 3, 4.
-        {
-            const int64_t i = cur_idx;
-            const int li = cur_len;
-            const bool valid = cur_idx >= 0, good = valid && li >= 0;
-            double acc = 0.0, lo = 0.0, hi = 0.0;
-            int js = -1;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const double na = acc + v[r];
-                const bool hit = (js < 0) && (na > prm.thr);
-                lo = hit ? acc : lo;
-                hi = hit ? na : hi;
-                js = hit ? r : js;
-                acc = na;
-            }
-            const bool done = good && js >= 0;
-            if (done) {
-                const int nsv = li - (int)nonzero;                           // 'N' bases (a read with an 'n' never gets here)
-                double e;
-                const bool keep = read_result(prm, true, js, lo, hi, nsv, nsv > 0, li, e);
-                ee[i] = e;
-                ns[i] = nsv;
-                pass[i] = (uint8_t)(keep ? 1 : 0);
-            }
-            const unsigned long long todo = __ballot(valid && !done);
-            if (todo) {
-                if (valid && !done) my_seg[nlist + __popcll(todo & ((1ull << lane) - 1ull))] = (int32_t)i;
-                nlist += __popcll(todo);
-            }
-#pragma unroll
-            for (int r = 0; r < R; r++) v[r] = r == 0 ? 1.0 : 0.0;
-            nonzero = 0;
-        }
-        cur_idx = nx_idx; cur_len = nx_len;
-        nx_idx = nn_idx; nx_len = nn_len;
-        cur_maxc = __builtin_amdgcn_readfirstlane(ld_maxc); cur_full = __builtin_amdgcn_readfirstlane(ld_full);
-        fetch(g + 3, nn_idx, nn_len);
-    }
-    if (lane == 0) wave_count[gw] = nlist;
-}
+#include "mpb_narrow_rg.inc"
 
 // The waves' list segments -> the dense list, in wave order: block g sums the counts of the waves before it (at most 8192 ints,
 // from L2), copies its wave's segment behind them, and the last block leaves the total in *count.  One launch; no atomics, so the
@@ -2523,6 +2232,41 @@ __global__ __launch_bounds__(256) void k_nar_compact(const int32_t *__restrict__
     for (int k = tid; k < cnt; k += 256) dst[k] = src[k];
     if (g == nwaves - 1 && tid == 0) *count = off0 + cnt;
 }
+
+// ------------------------------------------------------------------------------------------
+// The one-FMA twins (MPB_FLAG_ODDS | MPB_FLAG_ODDS_NARROW; ODDS_MODE.md "The narrow passes"): the three bodies above with
+// nar_run_odds and the odds end of a read; lut_g is the {a, r} table.  Kernels of their own names -- the exact kernels hold no
+// fused operation, and are compiled from the same text as before.  No mixed rows in this form: a row costs one operation of
+// R + 1, so a cut saves little (`split` is unused, k_rag_sort is launched without one).
+// ------------------------------------------------------------------------------------------
+#undef MPB_NAR_AR
+#undef MPB_NAR_RLO
+#define MPB_NAR_AR MPB_AR_ODDS
+#define MPB_NAR_RLO R
+template <int R, int D>
+__global__ __launch_bounds__(256) void k_odds_nar(const uint8_t *__restrict__ q, int64_t n, int64_t stride, int32_t li,
+                                                  MpbDevParams prm, const double2 *__restrict__ lut_g,
+                                                  double *__restrict__ ee, int32_t *__restrict__ ns, uint8_t *__restrict__ pass,
+                                                  int32_t *__restrict__ seg, int32_t *__restrict__ wave_count)
+#include "mpb_narrow_ring.inc"
+
+template <int R, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_odds_nar_rs(const uint8_t *__restrict__ q, int64_t n, int64_t stride, int32_t li, int32_t k,
+                                                     MpbDevParams prm, const double2 *__restrict__ lut_g,
+                                                     double *__restrict__ ee, int32_t *__restrict__ ns, uint8_t *__restrict__ pass,
+                                                     int32_t *__restrict__ seg, int32_t *__restrict__ wave_count)
+#include "mpb_narrow_rs.inc"
+
+template <int R>
+__global__ __launch_bounds__(256, 4) void k_odds_nar_rg(const uint8_t *__restrict__ q, int64_t n, int64_t stride,
+                                                   const int2 *__restrict__ ord, const unsigned long long *__restrict__ wpre,
+                                                   const int32_t *__restrict__ gpre, int32_t *__restrict__ gstart, int32_t split,
+                                                   MpbDevParams prm, const double2 *__restrict__ lut_g,
+                                                   double *__restrict__ ee, int32_t *__restrict__ ns, uint8_t *__restrict__ pass,
+                                                   int32_t *__restrict__ seg, int32_t *__restrict__ wave_count)
+#include "mpb_narrow_rg.inc"
+#undef MPB_NAR_RLO
+#undef MPB_NAR_AR
 
 // ------------------------------------------------------------------------------------------
 // k_sample: which pass does this batch take?  `n_sample` reads spread evenly (with a hashed offset inside each stride) over
@@ -2854,14 +2598,18 @@ static int mpb_narrow_rg_key_shift(int64_t stride)
 }
 
 // k_narrow_rg<R, RLO> by form: [0..2] R = 2..4 rows everywhere, [3..4] R = 3, 4 with mixed rows (RLO = R - 1)
-static decltype(&k_narrow_rg<2, 2>) const nar_rg_forms[MPB_NRG_FORMS] = {k_narrow_rg<2, 2>, k_narrow_rg<3, 3>, k_narrow_rg<4, 4>,
-                                                                          k_narrow_rg<3, 2>, k_narrow_rg<4, 3>};
+static decltype(&k_narrow_rg<2, 2>) const nar_rg_forms[MPB_NRG_EXACT_FORMS] = {k_narrow_rg<2, 2>, k_narrow_rg<3, 3>, k_narrow_rg<4, 4>,
+                                                                                k_narrow_rg<3, 2>, k_narrow_rg<4, 3>};
+// ... and [5..7] of rg_per_cu: the one-FMA twins k_odds_nar_rg<R>, R = 2..4
+static decltype(&k_odds_nar_rg<2>) const nar_rg_odds_forms[MPB_NRG_FORMS - MPB_NRG_EXACT_FORMS] = {k_odds_nar_rg<2>, k_odds_nar_rg<3>,
+                                                                                                     k_odds_nar_rg<4>};
 
 void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS])
 {
     for (int f = 0; f < MPB_NRG_FORMS; f++) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)nar_rg_forms[f], 256, 0) != hipSuccess || nb < 1) {
+        const void *const form = f < MPB_NRG_EXACT_FORMS ? (const void *)nar_rg_forms[f] : (const void *)nar_rg_odds_forms[f - MPB_NRG_EXACT_FORMS];
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, form, 256, 0) != hipSuccess || nb < 1) {
             (void)hipGetLastError();
             nb = 1;
         }
@@ -2869,10 +2617,53 @@ void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS])
     }
 }
 
+// The pass in its one-FMA form (MPB_FLAG_ODDS | MPB_FLAG_ODDS_NARROW): the twins on the {a, r} table `lut`; the grid is sized as in
+// mpb_launch_narrow below; no mixed rows (k_rag_sort without a cut).
+static void launch_narrow_odds(int rows0, const double2 *lut, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len,
+                               const int32_t *len, const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass,
+                               int n_cu, const int *rg_per_cu, hipStream_t s)
+{
+    const int ri = rows0 <= 2 ? 0 : rows0 == 3 ? 1 : 2;
+    const int rg = MPB_NRG_EXACT_FORMS + ri;
+    const int rs_k = len ? 0 : nar_rs_reads_per_lane(stride, rows0);
+    const int lds = len || rs_k ? 256 * (int)sizeof(nar_entry_t) + 4 * MPB_NRS_TILE
+                                : 256 * (int)sizeof(nar_entry_t) + MPB_NAR_DEPTH * 4 * MPB_NAR_PANEL + 32;
+    int per_cu = (160 * 1024) / lds;
+    if (len && rg_per_cu[rg] < per_cu) per_cu = rg_per_cu[rg];
+    const int per_blk = 64 * (rs_k ? rs_k : 1);
+    const int64_t nblk = (n + per_blk - 1) / per_blk;
+    int64_t blocks = (nblk + 3) / 4;
+    if (blocks > (int64_t)n_cu * per_cu) blocks = (int64_t)n_cu * per_cu;
+    if (blocks > MPB_NAR_MAX_WAVES / 4) blocks = MPB_NAR_MAX_WAVES / 4;
+    if (blocks < 1) blocks = 1;
+    const int nwaves = (int)blocks * 4;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (len) {
+        const int64_t nwin = (n + MPB_RG_WIN - 1) / MPB_RG_WIN;
+        hipLaunchKernelGGL(k_rag_sort, dim3((unsigned)nwin), dim3(256), 0, s, len, n, prm.max_len, mpb_narrow_rg_key_shift(stride),
+                           -1, 100, ws.rg_ord, ws.rg_gpre, ws.rg_wsum);
+        hipLaunchKernelGGL(k_rag_scan, dim3(1), dim3(1024), 0, s, ws.rg_wsum, (int)nwin, ws.rg_wpre);
+        hipLaunchKernelGGL(nar_rg_odds_forms[ri], grid, block, 0, s, q, n, stride, ws.rg_ord, ws.rg_wpre, ws.rg_gpre, ws.rg_gstart,
+                           -1, prm, lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count);
+    } else if (rs_k) {
+        static decltype(&k_odds_nar_rs<2, true>) const forms[4] = {k_odds_nar_rs<2, true>, k_odds_nar_rs<3, true>, k_odds_nar_rs<4, true>,
+                                                                   k_odds_nar_rs<2, false>};   // (rows of no multiple of 64: two rows only)
+        hipLaunchKernelGGL(forms[stride % 64 != 0 ? 3 : ri], grid, block, 0, s, q, n, stride, fixed_len, rs_k, prm, lut, ee, ns, pass,
+                           ws.nar_seg, ws.nar_wave_count);
+    } else {
+        static decltype(&k_odds_nar<2, MPB_NAR_DEPTH>) const forms[3] = {k_odds_nar<2, MPB_NAR_DEPTH>, k_odds_nar<3, MPB_NAR_DEPTH>,
+                                                                         k_odds_nar<4, MPB_NAR_DEPTH>};
+        hipLaunchKernelGGL(forms[ri], grid, block, 0, s, q, n, stride, fixed_len, prm, lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count);
+    }
+    hipLaunchKernelGGL(k_nar_compact, dim3((unsigned)nwaves), dim3(256), 0, s, ws.nar_seg, ws.nar_wave_count, nblk, nwaves, per_blk,
+                       len ? (const int32_t *)ws.rg_gstart : nullptr, ws.nar_list, ws.nar_count);
+}
+
 void mpb_launch_narrow(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len,
                        const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int n_cu,
-                       const int *rg_per_cu, hipStream_t s)
+                       const int *rg_per_cu, hipStream_t s, const double2 *lut_odds)
 {
+    if (lut_odds) return launch_narrow_odds(rows0, lut_odds, q, n, stride, fixed_len, len, prm, ws, ee, ns, pass, n_cu, rg_per_cu, s);
     const int ri = rows0 <= 2 ? 0 : rows0 == 3 ? 1 : 2;
     const bool mixed = len && split_chunks > 0 && rows0 >= 3;          // short groups with a row less (k_narrow_rg<R, R - 1>)
     const int rg = mixed ? ri + 2 : ri;

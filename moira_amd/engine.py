@@ -124,16 +124,19 @@ class Engine:
     @staticmethod
     def params(alpha=0.005, uncert=0.01, maxerrors=None, ambigs="treat_as_errors", round_=False,
                fast_fma=False, test_underpredict=False, decision_only=False, batched_only=False, count_cells=False,
-               no_narrow=False, narrow_rows=0, narrow_split=0, odds=False):
+               no_narrow=False, narrow_rows=0, narrow_split=0, odds=False, odds_narrow=False):
         if ambigs not in L.AMBIG:
             raise ValueError("ambigs must be one of %s" % sorted(L.AMBIG))
         if odds and fast_fma:
             raise ValueError("odds and fast_fma are two arithmetics for the same pass: set one")
+        if odds_narrow and not odds:
+            raise ValueError("odds_narrow needs odds=True (MPB_FLAG_ODDS_NARROW needs MPB_FLAG_ODDS)")
         flags = (L.FLAG_ROUND if round_ else 0) | (L.FLAG_FAST_FMA if fast_fma else 0) | \
                 (L.FLAG_TEST_UNDERPREDICT if test_underpredict else 0) | \
                 (L.FLAG_DECISION_ONLY if decision_only else 0) | \
                 (L.FLAG_BATCHED_ONLY if batched_only else 0) | (L.FLAG_COUNT_CELLS if count_cells else 0) | \
-                (L.FLAG_NO_NARROW if no_narrow else 0) | (L.FLAG_ODDS if odds else 0) | L.FLAG_NARROW_ROWS(narrow_rows) | ((int(narrow_split) & 255) << 12)
+                (L.FLAG_NO_NARROW if no_narrow else 0) | (L.FLAG_ODDS if odds else 0) | \
+                (L.FLAG_ODDS_NARROW if odds_narrow else 0) | L.FLAG_NARROW_ROWS(narrow_rows) | ((int(narrow_split) & 255) << 12)
         return L.FilterParams(float(alpha), float(uncert),
                               math.nan if maxerrors is None else float(maxerrors),
                               L.AMBIG[ambigs], flags)

@@ -38,7 +38,26 @@ VARIANTS = {
     # section 10: within 1.5 % of the planned cut either way -- a SIMD's four waves share its FP64 pipe, so a wave that ends early
     # gives its cycles to the others and the 9 % spread of the waves' ranges never shows.  One atomic claim per group instead: 1.10 ms,
     # a single address takes about 70 M atomics a second.)
-    "rg_striped_claims": "patches/rg_striped_claims.diff",
+    # (The one-FMA ragged twin k_odds_nar_rg keeps the planned cut this variant removes: its launch is taken out of the copy.)
+    "rg_striped_claims": ("patches/rg_striped_claims.diff", [
+        ("        hipLaunchKernelGGL(k_rag_sort, dim3((unsigned)nwin), dim3(256), 0, s, len, n, prm.max_len, mpb_narrow_rg_key_shift(stride),\n"
+         "                           -1, 100, ws.rg_ord, ws.rg_gpre, ws.rg_wsum);\n"
+         "        hipLaunchKernelGGL(k_rag_scan, dim3(1), dim3(1024), 0, s, ws.rg_wsum, (int)nwin, ws.rg_wpre);\n"
+         "        hipLaunchKernelGGL(nar_rg_odds_forms[ri], grid, block, 0, s, q, n, stride, ws.rg_ord, ws.rg_wpre, ws.rg_gpre, ws.rg_gstart,\n"
+         "                           -1, prm, lut, ee, ns, pass, ws.nar_seg, ws.nar_wave_count);\n",
+         "        (void)nwin; (void)grid; (void)block; (void)nar_rg_odds_forms;      // EXPERIMENT: the ragged twin is not launched\n"),
+        ("template <int R>\n"
+         "__global__ __launch_bounds__(256, 4) void k_odds_nar_rg(const uint8_t *__restrict__ q, int64_t n, int64_t stride,\n"
+         "                                                   const int2 *__restrict__ ord, const unsigned long long *__restrict__ wpre,\n"
+         "                                                   const int32_t *__restrict__ gpre, int32_t *__restrict__ gstart, int32_t split,\n"
+         "                                                   MpbDevParams prm, const double2 *__restrict__ lut_g,\n"
+         "                                                   double *__restrict__ ee, int32_t *__restrict__ ns, uint8_t *__restrict__ pass,\n"
+         "                                                   int32_t *__restrict__ seg, int32_t *__restrict__ wave_count)\n"
+         "#include \"%s\"\n" % os.path.join(ROOT, "moira_amd", "csrc", "mpb_narrow_rg.inc"), ""),
+        ("static decltype(&k_odds_nar_rg<2>) const nar_rg_odds_forms[MPB_NRG_FORMS - MPB_NRG_EXACT_FORMS] = {k_odds_nar_rg<2>, k_odds_nar_rg<3>,\n"
+         "                                                                                                     k_odds_nar_rg<4>};",
+         "static const void *const nar_rg_odds_forms[MPB_NRG_FORMS - MPB_NRG_EXACT_FORMS] = {nullptr, nullptr, nullptr};"),
+    ]),
     # k_narrow_rg: when a group is armed, every lane asks for one dword of line c8 (c8 >= 1) of each of the eight rows its load
     # instructions cover -- the rows' later lines are requested from DRAM together with their first, and wait in the L2 / the
     # Infinity Cache for the panel that needs them.  Results unchanged (the dwords are never looked at).
@@ -107,8 +126,23 @@ def main():
     name, out = sys.argv[1], sys.argv[2]
     src = sys.argv[3] if len(sys.argv) > 3 else SRC        # another copy of the kernel file (an A/B baseline kept aside); "none": no patch
     s = open(src).read()
+    # The narrow kernels' bodies are include files shared with their one-FMA twins (k_odds_nar*).  The variants are experiments on
+    # the EXACT kernels: their include (the first of each pair) is expanded in place, with the arithmetic selector written out as
+    # its default, so that a patch sees the body as text of this file; the twins keep including the unpatched body.
+    csrc = os.path.join(ROOT, "moira_amd", "csrc")
+    for inc in ("mpb_narrow_ring.inc", "mpb_narrow_rs.inc", "mpb_narrow_rg.inc"):
+        line = '#include "%s"\n' % inc
+        if line in s:
+            body = open(os.path.join(csrc, inc)).read()
+            body = body.replace(", MPB_NAR_AR>", ">").replace("nar_finish<MPB_NAR_AR>(", "nar_finish(").replace("MPB_NAR_RLO", "RLO")
+            body = body.replace("MPB_NAR_AR", "MPB_AR_EXACT")
+            s = s.replace(line, body, 1)
+            s = s.replace(line, '#include "%s"\n' % os.path.join(csrc, inc))
     for part in ([] if name == "none" else name.split("+")):     # A+B: both, in that order
         v = VARIANTS[part]
+        after = []
+        if isinstance(v, tuple):                               # a unified diff, then text patches
+            v, after = v
         if isinstance(v, str):                                 # a unified diff next to this script
             import subprocess
             import tempfile
@@ -121,7 +155,7 @@ def main():
                     sys.stderr.write("variant %s: %s does not apply:\n%s%s\n" % (part, v, r.stdout, r.stderr))
                     return 1
                 s = open(b).read()
-            continue
+            v = after
         for item in v:
             old, new, times = item if len(item) == 3 else (item[0], item[1], 1)
             if s.count(old) != times:

@@ -186,6 +186,31 @@ with Engine(0) as eng:
                 bad += 1
                 print("RAGGED-NARROW MISMATCH round %d: n=%d stride=%d rows0=%d split=%d kind=%d kw=%s path=%s"
                       % (it, n, stride, rows0, split, kind, kw, path), flush=True)
+        if extra.get("odds") and not extra.get("test_underpredict") and not too.any() and rng.random() < 0.7 and \
+                ((fixed and int(lens[0]) >= 1) or (not fixed and stride <= 4096)):
+            # MPB_FLAG_ODDS_NARROW: the same batch resident in HBM through the one-FMA form of the narrow pass, forced with 2 / 3 / 4
+            # rows, by the counting form; the pass finishes exactly the reads the model says cross within those rows (F)
+            n_mode["odds_narrow"] = n_mode.get("odds_narrow", 0) + 1
+            rows0 = int(rng.integers(2, 5))
+            bufs = [eng.alloc(n * stride).upload(q), eng.alloc(n * 8), eng.alloc(n * 4), eng.alloc(n), eng.alloc(n * 4).upload(lens)]
+            c = eng.filter_device(bufs[0], n, stride, d_len=None if fixed else bufs[4], fixed_len=int(lens[0]) if fixed else 0,
+                                  d_ee=bufs[1], d_ns=bufs[2], d_pass=bufs[3],
+                                  params=eng.params(narrow_rows=rows0, odds=True, odds_narrow=True, **kw))
+            path = eng.last_path()
+            g_ee, g_ns, g_ps = bufs[1].download(np.float64, n), bufs[2].download(np.int32, n), bufs[3].download(np.uint8, n).astype(bool)
+            for b in bufs:
+                b.free()
+            amb_n = ((q == 255) & (np.arange(stride)[None, :] < lens[:, None])).any(1)
+            F = ~m.hand & ~amb_n & (m.rows <= rows0)
+            eq_model = same(g_ee, m.ee) & (g_ps == m.passed)
+            eq_exact = same(g_ee, ee) & (g_ps == ps.astype(bool))
+            oko = (path["narrow_rows"] == rows0 and path["n_fallback"] == n - int(F.sum()) and np.array_equal(g_ns, ns)
+                   and eq_model[F].all() and (eq_model | eq_exact).all() and eq_exact[m.hand].all()
+                   and int((~eq_model).sum()) <= c.n_overflow + int((lens + 1 > 1024).sum()) and c.n_pass == int(ps.sum()))
+            if not oko:
+                bad += 1
+                print("ODDS-NARROW MISMATCH round %d: n=%d stride=%d fixed=%s rows0=%d kind=%d kw=%s path=%s"
+                      % (it, n, stride, fixed, rows0, kind, kw, path), flush=True)
         if (it + 1) % 100 == 0:
             print("fuzz: %d rounds done, %d mismatching, %.0f s" % (it + 1, bad, time.time() - t0), flush=True)
         if not ok:
@@ -193,6 +218,6 @@ with Engine(0) as eng:
             d = np.nonzero(~((r.ee == ee) | (np.isnan(r.ee) & np.isnan(ee))))[0]
             print("MISMATCH round %d: n=%d stride=%d fixed=%s kind=%d kw=%s extra=%s batched_only=%s first diffs %s rows %s"
                   % (it, n, stride, fixed, kind, kw, extra, eng.batched_only, d[:5], rows[d[:5]]), flush=True)
-print("fuzz: %d rounds, %d mismatching rounds, %.1f s (oracle threads %d; %d FAST_FMA and %d ODDS rounds)"
-      % (rounds, bad, time.time() - t0, threads, n_mode["fast_fma"], n_mode["odds"]))
+print("fuzz: %d rounds, %d mismatching rounds, %.1f s (oracle threads %d; %d FAST_FMA and %d ODDS rounds, %d of them also ODDS_NARROW)"
+      % (rounds, bad, time.time() - t0, threads, n_mode["fast_fma"], n_mode["odds"], n_mode.get("odds_narrow", 0)))
 sys.exit(1 if bad else 0)
