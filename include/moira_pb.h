@@ -130,6 +130,14 @@ extern "C" {
                                     outside its row.  No mixed rows in this form: MPB_FLAG_NARROW_SPLIT is ignored with the flag.
                                     Everything that keeps a call out of the narrow pass still does.  Off by default. */
 
+#define MPB_FLAG_POISSON_DEVICE_TAIL (1u << 21)   /* opt-in, read by the Poisson HOST entries only (mpb_filter_poisson_host,
+                                    mpb_filter_host_multi with poisson != 0; every other entry ignores the bit): the CDF tail of each
+                                    chunk runs on the device behind k_lambda (k_poisson_tail, in place in the chunk's ee array), and
+                                    the host tail runs only on the reads the kernel hands back.  Contract and hand-back rule: "the
+                                    device tail" below, next to mpb_poisson_finish_device.  n_overflow = the reads the host
+                                    finished, summed over the chunks.  alpha < 1e-5 with the flag is MPB_E_INVALID.  Off by default:
+                                    without it the entries keep the reference's libm bits. */
+
 /* kernel ids for mpb_kernel_time() */
 #define MPB_K_PREPASS   0   /* lambda/sigma/Ns estimate + row classing        */
 #define MPB_K_SCAN      1   /* class histogram scan / tile table              */
@@ -141,7 +149,8 @@ extern "C" {
 #define MPB_K_NARROW    7   /* natural-order narrow pass: one read per lane, 2..4 DP rows, the matrix read once */
 #define MPB_K_FALLBACK  8   /* (rounds 5: the gather of the unfinished reads and the scatter of their results; unused since round 6: they run where they lie) */
 #define MPB_K_SAMPLE    9   /* ... the batch sample that picks the pass */
-#define MPB_K_COUNT     10
+#define MPB_K_POISSON_TAIL 10 /* Poisson approximation: the CDF tail on the device (percentile, +Ns / floor, predicate) */
+#define MPB_K_COUNT     11
 
 typedef struct mpb_ctx mpb_ctx;
 
@@ -477,6 +486,59 @@ int mpb_poisson_finish_host(const double *lambda, const int32_t *ns, const int32
 int mpb_filter_poisson_host(mpb_ctx *ctx, const uint8_t *q, int64_t n, int64_t row_stride,
                             const int32_t *len, int32_t fixed_len, const mpb_filter_params *params,
                             double *ee, int32_t *ns, uint8_t *pass, mpb_filter_counts *counts);
+
+/*
+ * The device tail.  mpb_poisson_finish_host is the reference's loop with the HOST's libm (exp, and one pow per CDF term); no
+ * device code can have those bits -- glibc's exp / pow are not correctly rounded and differ between its own FMA and non-FMA
+ * variants.  The two entries below (and MPB_FLAG_POISSON_DEVICE_TAIL) therefore carry the contract of MPB_FLAG_FAST_FMA /
+ * MPB_FLAG_ODDS, with mpb_poisson_finish_host as the exact side:
+ *   - ee within 1e-9 relative; an ee of 0 on either side is 0 on both;
+ *   - ns, every pass / fail flag and every NaN identical;
+ *   - every read the device arithmetic cannot vouch for is finished by the host tail and counted in n_overflow.
+ * Device arithmetic (k_poisson_tail, one read per lane): em = exp(-lambda), one call per read and no pow; the terms by
+ * recurrence t_0 = em, t_j = (t_{j-1} * lambda) / j; the CDF summed sequentially until it exceeds 1 - alpha (j <= 170, as the
+ * reference's factorial); the reference's interpolation (j - 1) + (thr - acc_prev) / (acc - acc_prev), negative -> 0; then +Ns /
+ * floor / predicate by the code the host tail uses.
+ * Hand-back rule -- a read goes to the host tail when
+ *   (a) !(lambda >= 0 && lambda <= 64): NaN, negative, infinite, and every lambda for which the reference can raise OverflowError
+ *       (lambda <= 64: lambda ** j <= 2^1020 for every j <= 170, and with alpha >= 1e-5 the CDF crosses long before term 170).
+ *       Every read that can be NaN is computed by the code that defines it;
+ *   (b) its CDF crosses in term 0 or 1 and |(1 - alpha) - em| < 2^-17: in term 1 the ee is the fraction (thr - em) / t_1 alone, so
+ *       a last-bit difference in em is a large relative error once thr - em is tiny; in term 0 the two sides could disagree
+ *       between 0 and a tiny positive value.  The window was fixed on a numpy model of this arithmetic with em moved by -1 / 0 / +1
+ *       ulp against mpb_poisson_finish_host (tests/test_poisson_device_model.py).  Worst relative error of the model outside the
+ *       window, per alpha -- over 100 k lambda uniform in [0, 64]: 1e-5: 1.1e-11, 1e-4: 1.2e-12, 0.005: 2.5e-13, 0.05: 5.7e-13,
+ *       0.5: 9.0e-14, 0.9: 4.2e-13; over every input family of the tests (planted neighbours of the cancellation point, one-base
+ *       reads): 1e-5: 1.8e-11, 1e-4: 7.3e-12, 0.005: 9.4e-12, 0.05: 7.7e-12 -- at least 50 x inside the contract; the crossing
+ *       term and the ee == 0 reads agree everywhere outside the window;
+ *   (c) its ee (after +Ns) lies within 1e-9 * max(1, |ee|) of its limit or, with MPB_FLAG_ROUND, of an integer -- the test of
+ *       MPB_FLAG_FAST_FMA / MPB_FLAG_ODDS.  Not asked of a read that crosses in term 0 outside the window of (b): its ee is 0 (+Ns)
+ *       exactly on both sides.
+ * alpha < 1e-5 is MPB_E_INVALID (the floor of the other tolerance modes; the exact entries -- mpb_poisson_finish_host,
+ * mpb_filter_poisson_host without the flag -- take any alpha).
+ * BOTH ENTRIES SYNCHRONISE before they return: they fetch the 4-byte count of handed-back reads (with `counts` also the 8-byte
+ * count of kept reads, and mpb_filter_poisson_device the 4-byte count of reads with a byte 255, as mpb_poisson_lambda_device
+ * does).  When the count is zero nothing else crosses the link.  Otherwise the host fetches the handed-back reads' lambda / ns /
+ * length -- up to 65536 reads as one block of 24-byte records the kernel wrote, more than that as the whole arrays; never a copy
+ * per read --, runs the host tail on them and writes their ee / pass back before returning.
+ * counts (may be NULL): n_reads, n_pass, n_fail over the final flags; n_overflow = the reads the host finished.
+ *
+ * mpb_poisson_finish_device: the device twin of mpb_poisson_finish_host -- lambda / ns / len on the device, results on the device.
+ * d_ee may be the same array as d_lambda (each lane reads its lambda before it writes its ee).  d_ns is not written.
+ */
+int mpb_poisson_finish_device(mpb_ctx *ctx, const double *d_lambda, const int32_t *d_ns,
+                              const int32_t *d_len, int32_t fixed_len, int64_t n,
+                              const mpb_filter_params *params,
+                              double *d_ee, uint8_t *d_pass, mpb_filter_counts *counts);
+/* The resident Poisson filter: k_lambda + the device tail, the twin of mpb_filter_device for --error_calc poisson.  Arguments as
+ * mpb_poisson_lambda_device checks them (shape, alignment, row_stride <= 2^24; a byte 255 fails the call with MPB_E_INVALID).
+ * d_lambda may be NULL (lambda then lives in d_ee until the tail overwrites it); when given it receives
+ * mpb_poisson_lambda_device's values. */
+int mpb_filter_poisson_device(mpb_ctx *ctx, const uint8_t *d_q, int64_t n, int64_t row_stride,
+                              const int32_t *d_len, int32_t fixed_len,
+                              const mpb_filter_params *params,
+                              double *d_ee, int32_t *d_ns, uint8_t *d_pass, double *d_lambda,
+                              mpb_filter_counts *counts);
 
 /*
  * One read, the signature-level twin of moira.py's

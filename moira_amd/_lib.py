@@ -17,6 +17,7 @@ FLAG_ROUND, FLAG_FAST_FMA, FLAG_TEST_UNDERPREDICT, FLAG_DECISION_ONLY, FLAG_BATC
 FLAG_NO_NARROW = 64
 FLAG_ODDS = 128                # MPB_FLAG_ODDS: one fma per DP cell in the sorted pipeline's main pass (ODDS_MODE.md)
 FLAG_ODDS_NARROW = 1 << 20     # MPB_FLAG_ODDS_NARROW: with FLAG_ODDS, the narrow pass may run too, in the one-fma form
+FLAG_POISSON_DEVICE_TAIL = 1 << 21     # MPB_FLAG_POISSON_DEVICE_TAIL: the Poisson host entries run the CDF tail on the device
 
 
 def FLAG_NARROW_ROWS(r):
@@ -25,8 +26,9 @@ def FLAG_NARROW_ROWS(r):
 
 
 K_PREPASS, K_SCAN, K_SCATTER, K_DP, K_OVERFLOW, K_LAMBDA, K_WIDE, K_NARROW, K_FALLBACK, K_SAMPLE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+K_POISSON_TAIL = 10
 KERNEL_NAMES = {K_PREPASS: "prepass", K_SCAN: "scan", K_SCATTER: "scatter", K_DP: "dp", K_OVERFLOW: "overflow", K_LAMBDA: "lambda",
-                K_WIDE: "wide", K_NARROW: "narrow", K_FALLBACK: "fallback", K_SAMPLE: "sample"}
+                K_WIDE: "wide", K_NARROW: "narrow", K_FALLBACK: "fallback", K_SAMPLE: "sample", K_POISSON_TAIL: "poisson_tail"}
 
 
 class MoiraPBError(RuntimeError):
@@ -105,6 +107,10 @@ PROTOTYPES = {
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mpb_poisson_lambda_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, _VP, _VP]),
     "mpb_poisson_finish_host": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int64, C.POINTER(FilterParams), _VP, _VP]),
+    "mpb_poisson_finish_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int64, C.POINTER(FilterParams), _VP, _VP,
+                                            C.POINTER(FilterCounts)]),
+    "mpb_filter_poisson_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.POINTER(FilterParams),
+                                            _VP, _VP, _VP, _VP, C.POINTER(FilterCounts)]),
     "mpb_filter_poisson_host": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32,
                                           C.POINTER(FilterParams), _VP, _VP, _VP, C.POINTER(FilterCounts)]),
     "mpb_synth_fill_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, C.c_int32,

@@ -104,8 +104,10 @@ struct mpb_ctx {
     void *ws_nar = nullptr;              // wave segments + dense list + per-wave counts
     int64_t ws_nar_cap = 0;
     void *ws_rg = nullptr; int64_t ws_rg_cap = 0;   // the ragged pass' order entries, group costs, wave ranges (first ragged call)
+    void *pt_rec = nullptr; int64_t pt_rec_cap = 0;  // MPB_PT_REC_CAP records of reads k_poisson_tail handed back (first device-tail call)
     int rg_per_cu[MPB_NRG_FORMS] = {0};  // blocks per CU of the ragged pass' instantiations (the first ragged call)
-    // pinned host words: [0] list count, [2..3] passes, [4] overflow re-runs, [5] bad lengths, [16..34) the sample histogram
+    // pinned host words: [0] list count, [2..3] passes, [4] overflow re-runs, [5] bad lengths, [16..34) the sample histogram,
+    // [40] reads the Poisson device tail handed back, [42..43] the reads it kept, [44] reads with a byte 255
     int32_t *pin_words = nullptr;
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)
         bool valid = false; int64_t n = 0, stride = 0; int32_t fixed_len = 0; double alpha = 0; uint32_t flags = 0;
@@ -305,6 +307,7 @@ int mpb_destroy(mpb_ctx *c)
     if (c->pin_words) (void)hipHostFree(c->pin_words);
     if (c->ws_nar) (void)hipFree(c->ws_nar);
     if (c->ws_rg) (void)hipFree(c->ws_rg);
+    if (c->pt_rec) (void)hipFree(c->pt_rec);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_lut_odds) (void)hipFree(c->d_lut_odds);
     if (c->d_lut_private) (void)hipFree(c->d_lut_private);
@@ -480,6 +483,7 @@ static int ensure_workspace(mpb_ctx *c, int64_t n)
         c->ws.alg_cells = (unsigned long long *)(p + 2 * align_up(sizeof(MpbTables), 256) + 448);
         c->ws.nar_count = (int32_t *)(p + 2 * align_up(sizeof(MpbTables), 256) + 512);
         c->ws.nar_sample = (int32_t *)(p + 2 * align_up(sizeof(MpbTables), 256) + 576);      // MPB_NAR_BUCKETS ints
+        c->ws.pt_count = (int32_t *)(p + 2 * align_up(sizeof(MpbTables), 256) + 768);
         c->ws.lut = c->d_lut;
     }
     if (n <= c->ws_cap) return MPB_OK;
@@ -1262,12 +1266,16 @@ static void drain_pipeline(mpb_ctx *c)
 // what a pipeline run computes: the Poisson-binomial pass, or the Poisson approximation (lambda on the device, the
 // scalar tail on the host when a chunk is retired -- i.e. beside the GPU work of the chunks after it)
 struct PipeJob {
-    int poisson;
+    int poisson;           // 0: Poisson-binomial; 1: lambda + the host tail; 2: lambda + k_poisson_tail (MPB_FLAG_POISSON_DEVICE_TAIL)
     const mpb_filter_params *params;
     const int32_t *len;
     int32_t fixed_len;
     double *ee; int32_t *ns; uint8_t *pass;
+    int64_t *n_host_tail;  // poisson == 2: += the reads the host tail finished
 };
+
+static int poisson_finish_marked(const mpb_filter_params *p, const int32_t *ns, const int32_t *len, int32_t fixed_len, int64_t n,
+                                 double *ee, uint8_t *pass, int64_t *n_marked);
 
 // wait for the chunk parked in `sl` and hand its results to the caller's arrays
 static int retire_slot(mpb_ctx *c, HostSlot &sl, int64_t cap_reads, int64_t row_stride, const PipeJob &job, int64_t *n_pass)
@@ -1278,7 +1286,18 @@ static int retire_slot(mpb_ctx *c, HostSlot &sl, int64_t cap_reads, int64_t row_
     const char *h = (const char *)sl.pin_out;
     memcpy(job.ns + sl.off, h + L.ee, (size_t)(sl.m * 4));
     const uint8_t *hp;
-    if (job.poisson) {
+    if (job.poisson == 2) {
+        // the device tail ran in place: ee / pass as for the Poisson-binomial job, then the host tail on the reads it handed back
+        // (pass byte 2, lambda left in the ee slot)
+        memcpy(job.ee + sl.off, h, (size_t)(sl.m * 8));
+        memcpy(job.pass + sl.off, h + L.ee + L.ns, (size_t)sl.m);
+        int64_t marked = 0;
+        int rc = poisson_finish_marked(job.params, job.ns + sl.off, job.len ? job.len + sl.off : nullptr, job.fixed_len, sl.m,
+                                       job.ee + sl.off, job.pass + sl.off, &marked);
+        if (rc) return rc;
+        *job.n_host_tail += marked;
+        hp = job.pass + sl.off;
+    } else if (job.poisson) {
         // the block's first array holds lambda; ee / pass come from the reference's scalar loop (moira.py:1666-1679)
         int rc = mpb_poisson_finish_host((const double *)h, job.ns + sl.off, job.len ? job.len + sl.off : nullptr, job.fixed_len,
                                          sl.m, job.params, job.ee + sl.off, job.pass + sl.off);
@@ -1300,7 +1319,9 @@ static int filter_host_pipeline(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t
                                 int32_t fixed_len, const mpb_filter_params *params, double *ee, int32_t *ns,
                                 uint8_t *pass, mpb_filter_counts *counts, int poisson)
 {
-    const PipeJob job = {poisson, params, len, fixed_len, ee, ns, pass};
+    int64_t n_host_tail = 0;
+    const PipeJob job = {poisson, params, len, fixed_len, ee, ns, pass, &n_host_tail};
+    const MpbDevParams tail_prm = make_dev_params(params, fixed_len, 1);         // poisson == 2: what k_poisson_tail reads
     // chunk: at most MPB_HOST_CHUNK_BYTES of qualities, and at least four chunks per batch where the batch
     // is large enough for a chunk to be worth a launch sequence (overlap needs more than one chunk)
     int64_t chunk = (int64_t)MPB_HOST_CHUNK_BYTES / row_stride;
@@ -1338,6 +1359,10 @@ static int filter_host_pipeline(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t
     // fetched its counts must not fail this one
     HIPCHK(hipMemsetAsync(c->ws.bad_len, 0, sizeof(int32_t), c->stream));
     if (poisson) HIPCHK(hipMemsetAsync(c->ws.ovf_count, 0, sizeof(int32_t), c->stream));     // reads with a byte 255, summed over the chunks
+    if (poisson == 2) {    // the device tail's counters (neither is fetched here: the host sees every pass byte anyway)
+        HIPCHK(hipMemsetAsync(c->ws.pt_count, 0, sizeof(int32_t), c->stream));
+        HIPCHK(hipMemsetAsync(c->ws.pass_count, 0, sizeof(unsigned long long), c->stream));
+    }
     int64_t n_pass = 0;
     int64_t k = 0;
     for (int64_t off = 0; off < n; off += chunk, k++) {
@@ -1372,7 +1397,14 @@ static int filter_host_pipeline(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t
             Span t(c, MPB_K_LAMBDA);
             mpb_launch_lambda(d_q, m, row_stride, len ? d_len : nullptr, fixed_len, c->ws.lut, d_ee, d_ns, c->ws.ovf_count, c->stream);
             rc = hipGetLastError() == hipSuccess ? MPB_OK : fail(MPB_E_HIP, "k_lambda launch failed");
-        } else {
+        }
+        if (poisson == 2 && rc == MPB_OK) {
+            Span t(c, MPB_K_POISSON_TAIL);           // in place: lambda sits in the chunk's ee array
+            mpb_launch_poisson_tail(d_ee, d_ns, len ? d_len : nullptr, m, tail_prm, d_ee, d_pass, c->ws.pt_count, nullptr, 0,
+                                    c->ws.pass_count, c->stream);
+            rc = hipGetLastError() == hipSuccess ? MPB_OK : fail(MPB_E_HIP, "k_poisson_tail launch failed");
+        }
+        if (!poisson) {
             // (the chunks always take the sorted pipeline: the narrow pass synchronises on its count of handed-back reads, which would
             // stall the three-stream overlap of a path that is bound by the link anyway)
             mpb_filter_params chunk_prm = *params;
@@ -1411,7 +1443,7 @@ static int filter_host_pipeline(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t
     HIPCHK(hipStreamSynchronize(c->stream));
     if (bad255) return fail(MPB_E_INVALID, "%d read(s) contain byte 255 ('n'): the Poisson path follows the Python reference, "
                             "which scores lower-case n as a normal base -- pack it as one", bad255);
-    if (poisson) ovf = 0;
+    if (poisson) ovf = n_host_tail;                  // (0 without MPB_FLAG_POISSON_DEVICE_TAIL)
     if (bad) {
         HIPCHK(hipMemsetAsync(c->ws.bad_len, 0, sizeof(int32_t), c->stream));
         return fail(MPB_E_INVALID, "%d read length(s) outside 0..%d", bad, MPB_MAX_LEN);
@@ -1966,12 +1998,166 @@ int mpb_poisson_finish_host(const double *lambda, const int32_t *ns, const int32
     return MPB_OK;
 }
 
+// The reads of a batch in HOST arrays that k_poisson_tail handed back (pass byte 2, lambda in the ee slot): the host tail on exactly
+// those, through mpb_poisson_finish_host on a dense copy (so a batch that is handed back as a whole is split over the CPUs).
+static int poisson_finish_marked(const mpb_filter_params *p, const int32_t *ns, const int32_t *len, int32_t fixed_len, int64_t n,
+                                 double *ee, uint8_t *pass, int64_t *n_marked)
+{
+    *n_marked = 0;
+    const uint8_t *first = (const uint8_t *)memchr(pass, 2, (size_t)n);
+    if (!first) return MPB_OK;
+    try {
+        std::vector<int64_t> idx;
+        for (int64_t i = first - pass; i < n; i++) if (pass[i] == 2) idx.push_back(i);
+        const size_t m = idx.size();
+        std::vector<double> lam(m), e(m);
+        std::vector<int32_t> nsv(m), lv(m);
+        std::vector<uint8_t> ps(m);
+        for (size_t k = 0; k < m; k++) { lam[k] = ee[idx[k]]; nsv[k] = ns[idx[k]]; lv[k] = len ? len[idx[k]] : fixed_len; }
+        int rc = mpb_poisson_finish_host(lam.data(), nsv.data(), lv.data(), 0, (int64_t)m, p, e.data(), ps.data());
+        if (rc) return rc;
+        for (size_t k = 0; k < m; k++) { ee[idx[k]] = e[k]; pass[idx[k]] = ps[k]; }
+        *n_marked = (int64_t)m;
+    } catch (const std::bad_alloc &) {
+        return fail(MPB_E_NOMEM, "out of host memory for the reads handed back to the host tail");
+    }
+    return MPB_OK;
+}
+
+#define MPB_PT_REC_CAP 65536          // more handed-back reads than this: the arrays are fetched whole
+
+static int check_device_tail_params(const mpb_filter_params *p, const char *who)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (p->alpha < 1e-5)
+        return fail(MPB_E_INVALID, "%s needs alpha >= 1e-5 (the device tail's error bound does not hold below); the exact entries -- "
+                    "mpb_poisson_finish_host, mpb_filter_poisson_host without MPB_FLAG_POISSON_DEVICE_TAIL -- take any alpha", who);
+    return MPB_OK;
+}
+
+// k_poisson_tail on a resident batch (queued behind whatever produced d_lambda on the context's stream), the counts fetched, the
+// handed-back reads finished by the host tail and written back.  with_bad255: k_lambda ran just before; its count decides first.
+static int poisson_tail_resident(mpb_ctx *c, const double *d_lambda, const int32_t *d_ns, const int32_t *d_len, int32_t fixed_len,
+                                 int64_t n, const mpb_filter_params *p, double *d_ee, uint8_t *d_pass, bool with_bad255,
+                                 mpb_filter_counts *counts)
+{
+    hipStream_t s = c->stream;
+    int rc = grow_block(&c->pt_rec, &c->pt_rec_cap, (int64_t)MPB_PT_REC_CAP * (int64_t)sizeof(MpbPoissonRec), false);
+    if (rc) return rc;
+    int32_t *handed = c->pin_words + 40, *bad = c->pin_words + 44;
+    unsigned long long *kept = reinterpret_cast<unsigned long long *>(c->pin_words + 42);
+    *handed = 0; *bad = 0; *kept = 0;
+    HIPCHK(hipMemsetAsync(c->ws.pt_count, 0, sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(c->ws.pass_count, 0, sizeof(unsigned long long), s));
+    const MpbDevParams prm = make_dev_params(p, fixed_len, 1);
+    { Span t(c, MPB_K_POISSON_TAIL);
+      mpb_launch_poisson_tail(d_lambda, d_ns, d_len, n, prm, d_ee, d_pass, c->ws.pt_count, (MpbPoissonRec *)c->pt_rec, MPB_PT_REC_CAP,
+                              c->ws.pass_count, s); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(handed, c->ws.pt_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (counts) HIPCHK(hipMemcpyAsync(kept, c->ws.pass_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (with_bad255) HIPCHK(hipMemcpyAsync(bad, c->ws.ovf_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (*bad) return fail(MPB_E_INVALID, "%d read(s) contain byte 255 ('n'): the Poisson path follows the Python reference, "
+                          "which scores lower-case n as a normal base -- pack it as one", *bad);
+    const int64_t h = *handed;
+    int64_t host_pass = 0;
+    if (h > 0) {
+        try {
+            if (h <= MPB_PT_REC_CAP) {
+                // few: their records in one copy, the host tail, their results in one copy and a scatter
+                std::vector<MpbPoissonRec> rec((size_t)h);
+                HIPCHK(hipMemcpyAsync(rec.data(), c->pt_rec, (size_t)h * sizeof(MpbPoissonRec), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                std::vector<double> lam((size_t)h), e((size_t)h);
+                std::vector<int32_t> nsv((size_t)h), lv((size_t)h);
+                std::vector<uint8_t> ps((size_t)h);
+                for (int64_t k = 0; k < h; k++) { lam[k] = rec[k].lambda; nsv[k] = rec[k].ns; lv[k] = rec[k].len; }
+                if ((rc = mpb_poisson_finish_host(lam.data(), nsv.data(), lv.data(), 0, h, p, e.data(), ps.data()))) return rc;
+                std::vector<MpbPoissonFix> fix((size_t)h);
+                for (int64_t k = 0; k < h; k++) { fix[k].ee = e[k]; fix[k].idx = rec[k].idx; fix[k].pass = ps[k]; host_pass += ps[k]; }
+                HIPCHK(hipMemcpyAsync(c->pt_rec, fix.data(), (size_t)h * sizeof(MpbPoissonFix), hipMemcpyHostToDevice, s));
+                mpb_launch_poisson_patch((const MpbPoissonFix *)c->pt_rec, (int32_t)h, d_ee, d_pass, s);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(s));
+            } else {
+                // a large share of the batch: the arrays whole, both ways (never a copy per read)
+                std::vector<double> e((size_t)n);
+                std::vector<int32_t> nsv((size_t)n), lv(d_len ? (size_t)n : 0);
+                std::vector<uint8_t> ps((size_t)n);
+                HIPCHK(hipMemcpyAsync(e.data(), d_ee, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipMemcpyAsync(nsv.data(), d_ns, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipMemcpyAsync(ps.data(), d_pass, (size_t)n, hipMemcpyDeviceToHost, s));
+                if (d_len) HIPCHK(hipMemcpyAsync(lv.data(), d_len, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                std::vector<uint8_t> was(ps);
+                int64_t marked = 0;
+                if ((rc = poisson_finish_marked(p, nsv.data(), d_len ? lv.data() : nullptr, fixed_len, n, e.data(), ps.data(), &marked))) return rc;
+                if (marked != h) return fail(MPB_E_HIP, "k_poisson_tail counted %lld handed-back reads, %lld are marked", (long long)h, (long long)marked);
+                for (int64_t i = 0; i < n; i++) if (was[i] == 2) host_pass += ps[i];
+                HIPCHK(hipMemcpyAsync(d_ee, e.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+                HIPCHK(hipMemcpyAsync(d_pass, ps.data(), (size_t)n, hipMemcpyHostToDevice, s));
+                HIPCHK(hipStreamSynchronize(s));
+            }
+        } catch (const std::bad_alloc &) {
+            return fail(MPB_E_NOMEM, "out of host memory for the reads handed back to the host tail");
+        }
+    }
+    if (counts) {
+        counts->n_reads = n; counts->n_pass = (int64_t)*kept + host_pass; counts->n_fail = n - counts->n_pass; counts->n_overflow = h;
+    }
+    return MPB_OK;
+}
+
+int mpb_poisson_finish_device(mpb_ctx *c, const double *d_lambda, const int32_t *d_ns, const int32_t *d_len, int32_t fixed_len,
+                              int64_t n, const mpb_filter_params *params, double *d_ee, uint8_t *d_pass, mpb_filter_counts *counts)
+{
+    CTXCHK(c);
+    int rc = check_device_tail_params(params, "mpb_poisson_finish_device");
+    if (rc) return rc;
+    if (n < 0) return fail(MPB_E_INVALID, "n < 0");
+    if (n > 0x7fffffffll - 4096) return fail(MPB_E_INVALID, "batch of %lld reads exceeds 2^31; split it", (long long)n);
+    if (!d_len && fixed_len < 0) return fail(MPB_E_INVALID, "fixed_len < 0");
+    if (counts) { counts->n_reads = n; counts->n_pass = 0; counts->n_fail = 0; counts->n_overflow = 0; }
+    if (n == 0) return MPB_OK;
+    if (!d_lambda || !d_ns || !d_ee || !d_pass) return fail(MPB_E_INVALID, "NULL device buffer");
+    if ((rc = ensure_workspace(c, 1))) return rc;
+    return poisson_tail_resident(c, d_lambda, d_ns, d_len, fixed_len, n, params, d_ee, d_pass, false, counts);
+}
+
+int mpb_filter_poisson_device(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t row_stride, const int32_t *d_len, int32_t fixed_len,
+                              const mpb_filter_params *params, double *d_ee, int32_t *d_ns, uint8_t *d_pass, double *d_lambda,
+                              mpb_filter_counts *counts)
+{
+    CTXCHK(c);
+    int rc = check_device_tail_params(params, "mpb_filter_poisson_device");
+    if (rc) return rc;
+    // (the argument checks of mpb_poisson_lambda_device)
+    if (n < 0 || row_stride <= 0 || row_stride % 16 != 0) return fail(MPB_E_INVALID, "bad matrix shape");
+    if (n > 0x7fffffffll - 4096) return fail(MPB_E_INVALID, "batch of %lld reads exceeds 2^31; split it", (long long)n);
+    if (row_stride > MPB_LAMBDA_MAX_STRIDE) return fail(MPB_E_INVALID, "row_stride %lld exceeds %d", (long long)row_stride, MPB_LAMBDA_MAX_STRIDE);
+    if (((uintptr_t)d_q & 15) != 0) return fail(MPB_E_INVALID, "quality matrix must be 16-byte aligned");
+    if (!d_len && (fixed_len < 0 || fixed_len > row_stride)) return fail(MPB_E_INVALID, "fixed_len does not fit row_stride");
+    if (counts) { counts->n_reads = n; counts->n_pass = 0; counts->n_fail = 0; counts->n_overflow = 0; }
+    if (n == 0) return MPB_OK;
+    if (!d_q || !d_ee || !d_ns || !d_pass) return fail(MPB_E_INVALID, "NULL device buffer");
+    if ((rc = ensure_workspace(c, 1))) return rc;
+    double *lam = d_lambda ? d_lambda : d_ee;        // without d_lambda, lambda lives in d_ee until the tail overwrites it
+    HIPCHK(hipMemsetAsync(c->ws.ovf_count, 0, sizeof(int32_t), c->stream));
+    { Span t(c, MPB_K_LAMBDA);
+      mpb_launch_lambda(d_q, n, row_stride, d_len, fixed_len, c->ws.lut, lam, d_ns, c->ws.ovf_count, c->stream); }
+    HIPCHK(hipGetLastError());
+    return poisson_tail_resident(c, lam, d_ns, d_len, fixed_len, n, params, d_ee, d_pass, true, counts);
+}
+
 int mpb_filter_poisson_host(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t row_stride, const int32_t *len,
                             int32_t fixed_len, const mpb_filter_params *params, double *ee, int32_t *ns,
                             uint8_t *pass, mpb_filter_counts *counts)
 {
     CTXCHK(c);
-    int rc = check_params(params);
+    int rc = (params && (params->flags & MPB_FLAG_POISSON_DEVICE_TAIL)) ? check_device_tail_params(params, "MPB_FLAG_POISSON_DEVICE_TAIL")
+                                                                        : check_params(params);
     if (rc) return rc;
     if (n < 0 || row_stride <= 0 || row_stride % 16 != 0) return fail(MPB_E_INVALID, "bad matrix shape");
     if (row_stride > MPB_LAMBDA_MAX_STRIDE) return fail(MPB_E_INVALID, "row_stride %lld exceeds %d", (long long)row_stride, MPB_LAMBDA_MAX_STRIDE);
@@ -1985,7 +2171,9 @@ int mpb_filter_poisson_host(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t row
     if (n == 0) return MPB_OK;
     // the same four-slot pipeline as mpb_filter_host: H2D of chunk k+1 | k_lambda of chunk k | D2H of chunk k-1, and the
     // scalar tail of a chunk runs on the host while the GPU is busy with the chunks after it
-    return filter_host_pipeline(c, q, n, row_stride, len, fixed_len, params, ee, ns, pass, counts, 1);
+    // MPB_FLAG_POISSON_DEVICE_TAIL: k_poisson_tail runs on each chunk behind k_lambda, the host tail only on the reads it hands back
+    return filter_host_pipeline(c, q, n, row_stride, len, fixed_len, params, ee, ns, pass, counts,
+                                (params->flags & MPB_FLAG_POISSON_DEVICE_TAIL) ? 2 : 1);
 }
 
 // One read, the twin of moira.py's calculate_errors_poisson(sequence, quals, alpha) -> (expected_errors, Ns)

@@ -151,6 +151,7 @@ struct MpbWorkspace {
     int32_t  *rg_gpre;     // [n / 64 + 2] cost of each group of 64 entries (from its longest read), summed up inside its window
     unsigned long long *rg_wsum, *rg_wpre;   // [n / 4096 + 2] cost of each window; exclusive prefix ([nwin] = the total)
     int32_t  *rg_gstart;   // [MPB_NAR_MAX_WAVES + 1] first group of each wave of the persistent grid (written by the pass itself)
+    int32_t  *pt_count;    // [1] reads k_poisson_tail handed back to the host tail
 };
 
 // ---- natural-order narrow pass (round 5) -------------------------------------------------------
@@ -231,6 +232,20 @@ void mpb_launch_wide(const uint8_t *q, int64_t stride, const int32_t *len, const
                      const MpbWorkspace &ws, const int32_t *ns, double *ee, uint8_t *pass, hipStream_t s);
 void mpb_launch_lambda(const uint8_t *q, int64_t n, int64_t stride, const int32_t *len, int32_t fixed_len,
                        const double2 *lut_ap, double *lambda, int32_t *ns, int32_t *bad, hipStream_t s);
+// The device tail of --error_calc poisson (k_poisson_tail, MPB_FLAG_POISSON_DEVICE_TAIL / mpb_poisson_finish_device): lambda -> ee / pass,
+// one read per lane; ee may be the array lambda lies in.  A read the kernel does not vouch for (include/moira_pb.h: lambda outside
+// 0..MPB_PT_LAMBDA_MAX, a crossing in term 0 or 1 with |thr - exp(-lambda)| < MPB_PT_WINDOW, an ee next to a decision) keeps its lambda
+// in ee, gets pass = 2, is counted in *handed and -- rec != nullptr -- is recorded in rec[slot] while slot < rec_cap (in no
+// particular order).  *n_pass += the reads it kept.  Both counters are zeroed by the caller.
+#define MPB_PT_LAMBDA_MAX 64.0            // lambda ** j <= 2^1020 for every j <= 170: the reference's OverflowError cannot occur
+#define MPB_PT_WINDOW 0x1p-17             // fixed on the numpy model (tests/helpers/poisson_tail_model.py), not on the kernel
+struct MpbPoissonRec { double lambda; int32_t idx, ns, len, pad_; };     // a handed-back read, as the host tail needs it
+struct MpbPoissonFix { double ee; int32_t idx, pass; };                   // ... and its result on the way back
+void mpb_launch_poisson_tail(const double *lambda, const int32_t *ns, const int32_t *len, int64_t n, const MpbDevParams &prm,
+                             double *ee, uint8_t *pass, int32_t *handed, MpbPoissonRec *rec, int32_t rec_cap,
+                             unsigned long long *n_pass, hipStream_t s);
+// ee[fix[k].idx] / pass[...] = the host tail's results of m handed-back reads
+void mpb_launch_poisson_patch(const MpbPoissonFix *fix, int32_t m, double *ee, uint8_t *pass, hipStream_t s);
 void mpb_launch_decode(const uint8_t *seq, const uint8_t *qual, int64_t n, int64_t stride, const int32_t *len,
                        int32_t fixed_len, int32_t offset, uint8_t *out, int32_t *err, hipStream_t s);
 void mpb_launch_count(const uint8_t *pass, int64_t n, const MpbWorkspace &ws, hipStream_t s);

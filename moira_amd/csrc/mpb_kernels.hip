@@ -1584,6 +1584,88 @@ __global__ __launch_bounds__(256) void k_lambda(const uint8_t *__restrict__ q, i
 }
 
 // ------------------------------------------------------------------------------------------
+// k_poisson_tail: the CDF tail of --error_calc poisson on the device (moira/moira.py:1666-1679), one read per lane.
+// NOT the reference's libm bits (no device code can have them: glibc's exp / pow are not correctly rounded), so the contract is
+// the one of MPB_FLAG_FAST_FMA / MPB_FLAG_ODDS: ee within 1e-9 relative, ns / pass / NaN identical, and every read this arithmetic
+// cannot vouch for goes back to the host tail (pass = 2, lambda left in its ee slot, counted).
+//   em = exp(-lambda), ONE call per read; the terms by recurrence t_0 = em, t_j = (t_{j-1} * lambda) / j (no pow, no factorial
+//   table); the CDF summed sequentially as the reference sums it; its interpolation and clamp; then mpb_add_ns / mode_unsure /
+//   mpb_round_and_keep exactly as the host tail calls them (has_n = ns > 0).
+// Handed back: (a) !(0 <= lambda <= 64) -- NaN, negative, infinite, and every lambda for which the reference can overflow (so the
+// kernel never has to reproduce a NaN); (b) a crossing in term 0 or 1 with |thr - em| < 2^-17: in term 1 the ee is the fraction
+// (thr - em) / t_1 alone, where a last-bit difference in em is a large relative error once thr - em is tiny, and in term 0 the two
+// sides could disagree between 0 and a tiny positive value; (c) mode_unsure: an ee within 1e-9 relative of the read's limit or,
+// with --round, of an integer.  A crossing in term 0 outside the window of (b) is ee = 0 (+ Ns) EXACTLY on both sides -- the host's em
+// lies within an ulp of this one and the window is 2^35 ulps wide -- so (c) is not asked there: with --round it would send every
+// perfect read (0 is an integer) to the host for a value that cannot differ.
+// A lane reads its lambda before it writes its ee: the two may be one array (no __restrict__ on them).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_poisson_tail(const double *lambda, const int32_t *ns, const int32_t *len, int64_t n,
+                                                      MpbDevParams prm, double *ee, uint8_t *pass, int32_t *handed,
+                                                      MpbPoissonRec *rec, int32_t rec_cap, unsigned long long *n_pass)
+{
+    unsigned int kept = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double lam = lambda[i];
+        const int nsv = ns[i];
+        const int li = len ? len[i] : prm.fixed_len;
+        double e = 0.0;
+        bool keep = false;
+        bool back = !(lam >= 0.0 && lam <= MPB_PT_LAMBDA_MAX);                       // (a)
+        if (!back) {
+            const double em = exp(-lam);
+            double t = em, acc_prev = 0.0, acc = em;                                 // term 0: 0 + em == em
+            int j = 0;
+            while (!(acc > prm.thr) && j < 170) {                                    // the reference's factorial ends at 170
+                j++;
+                t = (t * lam) / (double)j;
+                acc_prev = acc;
+                acc = acc_prev + t;
+            }
+            if (!(acc > prm.thr)) {
+                back = true;                                                         // (never for lambda <= 64, alpha >= 1e-5)
+            } else if (j <= 1 && fabs(prm.thr - em) < MPB_PT_WINDOW) {
+                back = true;                                                         // (b)
+            } else {
+                e = (double)(j - 1) + (prm.thr - acc_prev) / (acc - acc_prev);
+                if (e < 0) e = 0;
+                e = mpb_add_ns(prm, e, nsv);
+                if (j > 0 && mode_unsure(prm, e, li)) back = true;                   // (c)
+                else keep = mpb_round_and_keep(prm, e, nsv > 0, li);
+            }
+        }
+        if (back) {
+            const int slot = atomicAdd(handed, 1);
+            if (rec && slot < rec_cap) {
+                MpbPoissonRec r;
+                r.lambda = lam; r.idx = (int32_t)i; r.ns = nsv; r.len = li; r.pad_ = 0;
+                rec[slot] = r;
+            }
+            ee[i] = lam;
+            pass[i] = 2;
+        } else {
+            ee[i] = e;
+            pass[i] = keep ? 1 : 0;
+            kept += keep ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) kept += __shfl_xor(kept, off);
+    if ((threadIdx.x & 63) == 0 && kept) atomicAdd(n_pass, (unsigned long long)kept);
+}
+
+__global__ __launch_bounds__(256) void k_poisson_patch(const MpbPoissonFix *__restrict__ fix, int32_t m, double *__restrict__ ee,
+                                                       uint8_t *__restrict__ pass)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < m) {
+        const MpbPoissonFix f = fix[k];
+        ee[f.idx] = f.ee;
+        pass[f.idx] = (uint8_t)f.pass;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // k_decode_ascii: FASTQ quality bytes + base letters -> packed qscores, 16 bytes per lane
 // (ref: moira/moira.py:1177 `ord(x) - offset`, bernoullimodule.c:104-107 Q0->1, :196 N / n)
 // ------------------------------------------------------------------------------------------
@@ -2523,6 +2605,23 @@ void mpb_launch_lambda(const uint8_t *q, int64_t n, int64_t stride, const int32_
     else
         hipLaunchKernelGGL((k_lambda<false>), dim3((unsigned)blocks), dim3(256), 0, s, q, n, stride, len,
                            fixed_len, lut_ap, lambda, ns, bad);
+}
+
+void mpb_launch_poisson_tail(const double *lambda, const int32_t *ns, const int32_t *len, int64_t n, const MpbDevParams &prm,
+                             double *ee, uint8_t *pass, int32_t *handed, MpbPoissonRec *rec, int32_t rec_cap,
+                             unsigned long long *n_pass, hipStream_t s)
+{
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;                    // 8 workgroups per CU; the read loop is grid-strided
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_poisson_tail, dim3((unsigned)blocks), dim3(256), 0, s, lambda, ns, len, n, prm, ee, pass, handed, rec,
+                       rec_cap, n_pass);
+}
+
+void mpb_launch_poisson_patch(const MpbPoissonFix *fix, int32_t m, double *ee, uint8_t *pass, hipStream_t s)
+{
+    if (m <= 0) return;
+    hipLaunchKernelGGL(k_poisson_patch, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, fix, m, ee, pass);
 }
 
 void mpb_launch_decode(const uint8_t *seq, const uint8_t *qual, int64_t n, int64_t stride, const int32_t *len,

@@ -124,7 +124,7 @@ class Engine:
     @staticmethod
     def params(alpha=0.005, uncert=0.01, maxerrors=None, ambigs="treat_as_errors", round_=False,
                fast_fma=False, test_underpredict=False, decision_only=False, batched_only=False, count_cells=False,
-               no_narrow=False, narrow_rows=0, narrow_split=0, odds=False, odds_narrow=False):
+               no_narrow=False, narrow_rows=0, narrow_split=0, odds=False, odds_narrow=False, poisson_device_tail=False):
         if ambigs not in L.AMBIG:
             raise ValueError("ambigs must be one of %s" % sorted(L.AMBIG))
         if odds and fast_fma:
@@ -136,7 +136,8 @@ class Engine:
                 (L.FLAG_DECISION_ONLY if decision_only else 0) | \
                 (L.FLAG_BATCHED_ONLY if batched_only else 0) | (L.FLAG_COUNT_CELLS if count_cells else 0) | \
                 (L.FLAG_NO_NARROW if no_narrow else 0) | (L.FLAG_ODDS if odds else 0) | \
-                (L.FLAG_ODDS_NARROW if odds_narrow else 0) | L.FLAG_NARROW_ROWS(narrow_rows) | ((int(narrow_split) & 255) << 12)
+                (L.FLAG_ODDS_NARROW if odds_narrow else 0) | (L.FLAG_POISSON_DEVICE_TAIL if poisson_device_tail else 0) | \
+                L.FLAG_NARROW_ROWS(narrow_rows) | ((int(narrow_split) & 255) << 12)
         return L.FilterParams(float(alpha), float(uncert),
                               math.nan if maxerrors is None else float(maxerrors),
                               L.AMBIG[ambigs], flags)
@@ -297,7 +298,9 @@ class Engine:
 
     def filter_poisson(self, q, lens=None, fixed_len=None, out=None, **kw):
         """--error_calc poisson (moira/moira.py:1637-1679): lambda summed on the GPU in base order,
-        scalar CDF tail on the host with the reference's libm calls.  Returns FilterResult."""
+        scalar CDF tail on the host with the reference's libm calls.  Returns FilterResult.
+        poisson_device_tail=True (MPB_FLAG_POISSON_DEVICE_TAIL): the tail runs on the GPU too -- ee within 1e-9 relative, ns /
+        pass / NaN identical; n_overflow = the reads the host tail finished."""
         params = kw.pop("params", None) or self.params(**kw)
         q, n, stride, lens, (ee, ns, ps) = check_host_batch(q, lens, fixed_len, out, limit=None)
         counts = L.FilterCounts()
@@ -305,7 +308,32 @@ class Engine:
                                                  lens.ctypes.data if lens is not None else None,
                                                  0 if lens is not None else int(fixed_len), C.byref(params),
                                                  ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, C.byref(counts)))
-        return FilterResult(ee, ns, ps.view(bool), counts.n_pass, 0)
+        return FilterResult(ee, ns, ps.view(bool), counts.n_pass, counts.n_overflow)     # (0 without poisson_device_tail)
+
+    def poisson_finish_device(self, d_lambda, d_ns, n, d_len=None, fixed_len=0, d_ee=None, d_pass=None, params=None,
+                              want_counts=True):
+        """The device twin of mpb_poisson_finish_host: lambda / ns (/ len) resident in HBM -> ee / pass there.  d_ee may be
+        d_lambda.  Synchronises (include/moira_pb.h, "the device tail")."""
+        params = params or self.params()
+        ptr = lambda b: (b.ptr if isinstance(b, DeviceBuffer) else b)
+        counts = L.FilterCounts()
+        L.check(self.lib.mpb_poisson_finish_device(self.ctx, ptr(d_lambda), ptr(d_ns), ptr(d_len) if d_len is not None else None,
+                                                   int(fixed_len), n, C.byref(params), ptr(d_ee), ptr(d_pass),
+                                                   C.byref(counts) if want_counts else None))
+        return counts if want_counts else None
+
+    def filter_poisson_device(self, d_q, n, stride, d_len=None, fixed_len=0, d_ee=None, d_ns=None, d_pass=None, d_lambda=None,
+                              params=None, want_counts=True):
+        """--error_calc poisson on a batch already resident in HBM (k_lambda + the device tail); results stay there.
+        d_lambda (optional) receives lambda.  Synchronises."""
+        params = params or self.params()
+        ptr = lambda b: (b.ptr if isinstance(b, DeviceBuffer) else b)
+        counts = L.FilterCounts()
+        L.check(self.lib.mpb_filter_poisson_device(self.ctx, ptr(d_q), n, stride, ptr(d_len) if d_len is not None else None,
+                                                   int(fixed_len), C.byref(params), ptr(d_ee), ptr(d_ns), ptr(d_pass),
+                                                   ptr(d_lambda) if d_lambda is not None else None,
+                                                   C.byref(counts) if want_counts else None))
+        return counts if want_counts else None
 
     def calculate_errors_PB(self, contig, contig_quals, alpha):
         """Exact twin of bernoulli.calculate_errors_PB -> (expected_errors, Ns).

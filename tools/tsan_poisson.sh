@@ -27,6 +27,8 @@ void mpb_launch_narrow(int, int, const uint8_t *, int64_t, int64_t, int32_t, con
 void mpb_narrow_rg_blocks_per_cu(int *) STUB
 void mpb_launch_sample(const uint8_t *, int64_t, int64_t, int32_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, int, hipStream_t) STUB
 void mpb_launch_serve(const MpbServeBox &, const double2 *, uint32_t, uint32_t, hipStream_t) STUB
+void mpb_launch_poisson_tail(const double *, const int32_t *, const int32_t *, int64_t, const MpbDevParams &, double *, uint8_t *, int32_t *, MpbPoissonRec *, int32_t, unsigned long long *, hipStream_t) STUB
+void mpb_launch_poisson_patch(const MpbPoissonFix *, int32_t, double *, uint8_t *, hipStream_t) STUB
 CPP
 cat > $D/main.cpp <<'CPP'
 #include "moira_pb.h"
