@@ -18,8 +18,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmoira_pb.so")
-SOURCES = [os.path.join(CSRC, "mpb_kernels.hip"), os.path.join(CSRC, "mpb_api.cpp"), os.path.join(CSRC, "mpb_broker.cpp")]
+# the host side of the library: the C ABI layer, unit by unit (mpb_hostonly.cpp includes no HIP header), and the broker
+HOST_SOURCES = [os.path.join(CSRC, name) for name in ("mpb_hostonly.cpp", "mpb_context.cpp", "mpb_resident.cpp", "mpb_hostfed.cpp",
+                                                      "mpb_perread.cpp", "mpb_poisson.cpp", "mpb_broker.cpp")]
+SOURCES = [os.path.join(CSRC, "mpb_kernels.hip")] + HOST_SOURCES
 DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_host_internal.h"),
+                  os.path.join(CSRC, "mpb_shared.h"), os.path.join(CSRC, "mpb_hostonly.h"), os.path.join(CSRC, "mpb_ctx.h"),
                   os.path.join(CSRC, "mpb_dp_tiles.inc"),
                   os.path.join(CSRC, "mpb_narrow_ring.inc"), os.path.join(CSRC, "mpb_narrow_rs.inc"),
                   os.path.join(CSRC, "mpb_narrow_rg.inc"),
@@ -141,6 +145,9 @@ def build(force=False, verbose=False, extra=()):
 
 
 if __name__ == "__main__":
+    if "--host-sources" in sys.argv:     # for scripts that build variants of the library (tools/experiments)
+        print(" ".join(os.path.relpath(p, ROOT) for p in HOST_SOURCES))
+        sys.exit(0)
     build(force="--force" in sys.argv, verbose=True)
     build_contig(force="--force" in sys.argv, verbose=True)
     build_io(force="--force" in sys.argv, verbose=True)

@@ -1,0 +1,232 @@
+// mpb_ctx.h -- the context of the C ABI (struct mpb_ctx) and what the GPU-facing host units share: the error macros, the owner of
+// a growable block (Buf), the carver that lays a block out (Carver), the timing span, and the few functions that cross units
+// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp).  Not installed.
+#ifndef MPB_CTX_H
+#define MPB_CTX_H
+
+#include "../../include/moira_pb.h"
+#include "mpb_internal.h"
+#include "mpb_host_internal.h"
+#include "mpb_hostonly.h"
+
+#include <vector>
+
+static_assert(sizeof(MpbPair) == sizeof(double2) && offsetof(MpbPair, y) == sizeof(double), "MpbPair is double2's layout");
+
+static inline int hip_fail(const char *what, hipError_t e)
+{
+    return fail(e == hipErrorOutOfMemory ? MPB_E_NOMEM : MPB_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
+#define HIPCHK(expr)                                        \
+    do {                                                    \
+        hipError_t e_ = (expr);                             \
+        if (e_ != hipSuccess) return hip_fail(#expr, e_);   \
+    } while (0)
+// ... of calls whose results were kept until a synchronisation had been made: the first that failed
+#define HIPCHK_KEPT(what, e)                                \
+    do {                                                    \
+        if ((e) != hipSuccess) return hip_fail(what, e);    \
+    } while (0)
+
+#define CTXCHK(c)                                                     \
+    do {                                                              \
+        if (!(c)) return fail(MPB_E_INVALID, "%s: ctx is NULL", __func__); \
+        HIPCHK(hipSetDevice((c)->device));                            \
+    } while (0)
+
+// ---- one owner for a block of device or pinned memory --------------------------------------------------------------------
+// grow() is the ONLY place that frees a block to make a larger one: the runtime waits for the whole device in a free, so the
+// context's stream is synchronised and the per-read entry's resident kernel is asked to leave (serve_quiesce) first.
+enum BufKind { BUF_DEVICE, BUF_PINNED, BUF_MAPPED };     // hipMalloc; hipHostMalloc; hipHostMalloc, mapped into the device
+struct Buf {
+    BufKind kind;
+    void *p = nullptr;
+    int64_t cap = 0;                                     // bytes
+    explicit Buf(BufKind k = BUF_DEVICE) : kind(k) {}
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
+    hipError_t alloc(int64_t bytes);                     // an empty block only: no wait, no free (context and server set-up)
+    // at least `bytes`; a block that has to be replaced is made `alloc_bytes` large (0: bytes).  Fails with p == nullptr, cap == 0.
+    int grow(mpb_ctx *c, int64_t bytes, int64_t alloc_bytes = 0);
+    void release();
+};
+
+// The layout of a block: one statement list (a function of a Carver) walked twice.  Without a base it nulls the pointers and sums
+// the sizes; with the block's base it hands out the pointers, each 256-byte aligned.  Size and offsets cannot disagree.
+struct Carver {
+    char *base;
+    int64_t off = 0;
+    explicit Carver(void *b = nullptr) : base((char *)b) {}
+    template <typename T> void take(T *&ptr, int64_t count)
+    {
+        ptr = base ? (T *)(base + off) : nullptr;
+        off += align_up(count * (int64_t)sizeof(T), 256);
+    }
+    int64_t bytes() const { return off; }
+};
+// block `b` laid out by `layout`, grown as needed (a block that is replaced gets `headroom` times the bytes).  When it cannot be
+// had, every pointer of the layout is left null.
+template <typename Layout>
+static int carve(mpb_ctx *c, Buf &b, Layout &&layout, int headroom = 1)
+{
+    Carver size;
+    layout(size);
+    int rc = b.grow(c, size.bytes(), size.bytes() * headroom);
+    if (rc) return rc;
+    Carver place(b.p);
+    layout(place);
+    return MPB_OK;
+}
+
+// The small device block: the two class tables and the counters, each counter on a 64-byte line of its own (different kernels
+// write them).  c->ws points at its members.
+struct MpbSmallBlock {
+    alignas(256) MpbTables tables;                       // main pass
+    alignas(256) MpbTables tables2;                      // overflow pass
+    alignas(64) int32_t ovf_count;
+    alignas(64) int32_t bad_len;
+    alignas(64) unsigned long long pass_count;
+    alignas(64) long long ovf_total;                     // overflow re-runs summed over the chunks of one host-pipeline call
+    alignas(64) int32_t wide_count;
+    alignas(64) unsigned long long alg_cells;
+    alignas(64) int32_t nar_count;
+    alignas(64) int32_t nar_sample[MPB_NAR_BUCKETS + 2];
+    alignas(64) int32_t pt_count;
+};
+
+// The pinned words the counts of a call land in (several copies, one synchronisation; nothing of it lies on a frame).
+struct PinWords {
+    int32_t nar_count;                                   // reads the narrow pass handed back
+    int32_t n_overflow;                                  // overflow re-runs
+    unsigned long long n_pass;
+    int32_t bad_len;                                     // lengths outside 0..max_len
+    int32_t bad255;                                      // Poisson paths: reads with a byte 255
+    int32_t sample[MPB_NAR_BUCKETS + 2];                 // the sample histogram (k_sample)
+    int32_t pt_handed;                                   // reads the Poisson device tail handed back
+    unsigned long long pt_kept;                          // ... and the reads it kept
+    long long ovf_total;                                 // host pipeline: overflow re-runs of all chunks
+};
+
+struct TimedSpan { int kid; hipEvent_t a, b; };
+
+// the chunk arrays of the host-fed paths, as one block holds them: inputs (q | len), then outputs (ee | ns | pass)
+struct ChunkArrays {
+    uint8_t *q; int32_t *len; double *ee; int32_t *ns; uint8_t *pass;
+    void in(Carver &k, int64_t m, int64_t row_stride) { k.take(q, m * row_stride); k.take(len, m); }
+    void out(Carver &k, int64_t m) { k.take(ee, m); k.take(ns, m); k.take(pass, m); }
+};
+
+// One of the MPB_HOST_SLOTS chunk buffers of the host pipeline (mpb_filter_host): a device block
+// (q | len | ee | ns | pass), a pinned staging block for inputs that arrive in pageable memory, a pinned
+// block the outputs land in, and the three events that hand the chunk from stream to stream.
+#define MPB_HOST_SLOTS 4
+struct HostSlot {
+    Buf dev{BUF_DEVICE}, pin_in{BUF_PINNED}, pin_out{BUF_PINNED};
+    ChunkArrays d{}, hin{}, hout{};          // the chunk arrays in dev (all five), pin_in (q, len) and pin_out (ee, ns, pass)
+    hipEvent_t h2d_done = nullptr, k_done = nullptr, d2h_done = nullptr;
+    int64_t off = -1, m = 0;  // chunk in flight (off < 0: none)
+};
+
+struct mpb_ctx {
+    int device = -1;
+    hipStream_t stream = nullptr;        // kernels (and every call that is not the host pipeline)
+    hipStream_t copy_stream = nullptr;   // host pipeline: H2D of the next chunk
+    hipStream_t out_stream = nullptr;    // host pipeline: D2H of the previous chunk
+    HostSlot slot[MPB_HOST_SLOTS];
+    int copy_threads = 1;
+    Buf luts{BUF_DEVICE};                // the three tables below
+    double2 *d_lut = nullptr;
+    double2 *d_lut_odds = nullptr;       // {1-p, p / (1-p)}: the table of MPB_FLAG_ODDS' main pass (k_dp_odds)
+    double2 *d_lut_private = nullptr;    // one call's table when a read carries qualities above 254 (mpb_calculate_errors_PB)
+    // workspace, grown on demand
+    MpbWorkspace ws{};
+    Buf ws_small{BUF_DEVICE};            // MpbSmallBlock
+    Buf ws_block{BUF_DEVICE};            // the sorted pipeline's arrays
+    int64_t ws_cap = 0;                  // ... sized for this many reads
+    // what the last classify-at-source call produced (consumed by mpb_filter_device_classified; any other call that
+    // rebuilds the workspace invalidates it)
+    struct Classified {
+        bool valid = false; const uint8_t *q = nullptr; int64_t n = 0, stride = 0; const int32_t *len = nullptr;
+        int32_t fixed_len = 0; mpb_filter_params params{}; double *ee = nullptr; int32_t *ns = nullptr; uint8_t *pass = nullptr;
+    } classified;
+    Buf ws_wide{BUF_DEVICE};             // wide-read list + predicted rows, only for batches whose rows hold > 1023 bases
+    int64_t ws_wide_cap = 0;
+    // timing
+    bool timing = false;
+    std::vector<TimedSpan> spans;
+    std::vector<hipEvent_t> event_pool;
+    double acc_ms[MPB_K_COUNT] = {0};
+    int64_t acc_n[MPB_K_COUNT] = {0};
+    // the small-batch path: device staging, and pinned host scratch (inputs and outputs of one call, back to back)
+    Buf stage{BUF_DEVICE};
+    Buf pin_host{BUF_MAPPED};
+    uint32_t small_token = 0;            // completion token of the last zero-copy k_small launch (never 0)
+    // ---- natural-order narrow pass (round 5) ----
+    int n_cu = 0;                        // compute units of the device (the persistent grid of k_narrow)
+    bool narrow_ok = false;              // the default table satisfies a == 1 - b for every score (checked by mpb_create)
+    Buf ws_nar{BUF_DEVICE};              // wave segments + dense list + per-wave counts
+    int64_t ws_nar_cap = 0;
+    Buf ws_rg{BUF_DEVICE}; int64_t ws_rg_cap = 0;    // the ragged pass' order entries, group costs, wave ranges (first ragged call)
+    Buf pt_rec{BUF_DEVICE};              // MPB_PT_REC_CAP records of reads k_poisson_tail handed back (first device-tail call)
+    int rg_per_cu[MPB_NRG_FORMS] = {0};  // blocks per CU of the ragged pass' instantiations (the first ragged call)
+    Buf pin_mem{BUF_PINNED};
+    PinWords *pin = nullptr;             // (in pin_mem)
+    struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)
+        bool valid = false; int64_t n = 0, stride = 0; int32_t fixed_len = 0; double alpha = 0; uint32_t flags = 0;
+        int rows0 = 0; int split = 0; int calls = 0;
+        double expect_back = 0;          // share of the sample (by weight) that needs more rows than rows0 or holds an 'n'
+    } nar_choice;
+    mpb_path_info last_path{};
+    // the class workspace (cls, tables) describes the last filtered batch as a whole: mpb_last_class_histogram, mpb_last_read_budgets
+    bool classes_whole = true;
+    // ---- the per-read entry's resident server (round 5; k_serve with ONE mailbox entry, see serve_one) ----
+    struct CtxServe {
+        bool tried = false, ok = false, running = false;
+        hipStream_t stream = nullptr;
+        Buf pin{BUF_MAPPED}, dev{BUF_DEVICE};
+        MpbServeBox box{};
+        uint32_t generation = 0, tok = 0;
+        double cached_alpha = -1.0;
+        MpbDevParams cached_prm;
+    } serve;
+};
+
+struct Span {
+    mpb_ctx *c; int kid; hipEvent_t a = nullptr, b = nullptr;
+    Span(mpb_ctx *c_, int kid_) : c(c_), kid(kid_) { if (c->timing) start(); }
+    void start();                        // (mpb_context.cpp, next to the event pool)
+    ~Span()
+    {
+        if (c->timing) { (void)hipEventRecord(b, c->stream); c->spans.push_back({kid, a, b}); }
+    }
+};
+
+// The kernels of one call run on a private copy of the table; the context's own is back in place when the call returns.
+struct PrivateTable {
+    mpb_ctx *c;
+    bool on = false;
+    explicit PrivateTable(mpb_ctx *ctx) : c(ctx) {}
+    int install(const double2 *h);
+    ~PrivateTable() { if (on) c->ws.lut = c->d_lut; }
+};
+
+// mpb_context.cpp
+// one copy between a frame (or a vector) and the device, and the wait for it: nothing can return between the two
+int copy_sync(mpb_ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+int ensure_workspace(mpb_ctx *c, int64_t n);
+int ensure_wide_workspace(mpb_ctx *c, int64_t n);
+int ensure_narrow_workspace(mpb_ctx *c, int64_t n, bool ragged);
+// mpb_resident.cpp
+MpbDevParams make_dev_params(const mpb_filter_params *p, int32_t fixed_len, int32_t max_len);
+// mpb_hostfed.cpp
+void drain_pipeline(mpb_ctx *c);
+int filter_host_pipeline(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t row_stride, const int32_t *len, int32_t fixed_len,
+                         const mpb_filter_params *params, double *ee, int32_t *ns, uint8_t *pass, mpb_filter_counts *counts,
+                         int poisson);
+// mpb_perread.cpp: the per-read entry's resident kernel leaves (before anything is freed: the runtime waits for the whole
+// device there); ... and its stream and blocks go
+void serve_quiesce(mpb_ctx *c);
+void serve_free(mpb_ctx *c);
+
+#endif

@@ -1,5 +1,5 @@
 // mpb_host_internal.h -- what the broker's translation unit (mpb_broker.cpp) needs from the C-ABI layer
-// (mpb_api.cpp).  Not installed; none of these symbols is exported (the version script keeps `mpb_*` only).
+// (mpb_perread.cpp, mpb_hostfed.cpp).  Not installed; none of these symbols is exported (the version script keeps `mpb_*` only).
 #ifndef MPB_HOST_INTERNAL_H
 #define MPB_HOST_INTERNAL_H
 
@@ -9,7 +9,7 @@
 struct mpb_ctx;
 struct MpbSmallHost;
 
-extern "C" {      // (defined inside mpb_api.cpp's extern "C" block; hidden: the version script exports `mpb_*` only)
+extern "C" {      // (defined in mpb_perread.cpp, mpbi_wait_flags in mpb_hostfed.cpp; hidden: the version script exports `mpb_*` only)
 
 int mpbi_fail(int code, const char *msg);                // sets mpb_last_error() of the calling thread, returns code
 int mpbi_ctx_device(const mpb_ctx *c);

@@ -1,0 +1,44 @@
+// mpb_hostonly.h -- the part of the C-ABI layer that needs no GPU (mpb_hostonly.cpp): error state, the table arithmetic, the
+// packers, argument checks, the narrow pass' cost model, the host Poisson tail, the NUMA parser.  Includes no HIP header: the
+// unit builds with a plain C++ compiler (tools/asan_api.sh, tools/tsan_poisson.sh run it under the host sanitizers).  C++
+// linkage throughout, so the version script, which exports `mpb_*` only, keeps all of it inside the library.
+#ifndef MPB_HOSTONLY_H
+#define MPB_HOSTONLY_H
+
+#include <sched.h>
+#include <stddef.h>
+#include "mpb_shared.h"
+
+#define MPB_ERR_LEN 512                   // bytes of a thread's last error text (mpb_last_error)
+
+// sets mpb_last_error() of the calling thread, returns code
+int fail(int code, const char *fmt, ...);
+
+static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+struct MpbPair { double x, y; };          // one table entry; the layout of HIP's double2 (checked in mpb_ctx.h)
+void lut_entry(int q, MpbPair *e, MpbPair *odds = nullptr);
+void build_lut(MpbPair *lut, MpbPair *odds = nullptr);
+int pack_one_read(const char *contig, const int32_t *quals, int32_t len, bool poisson, uint8_t *row, int32_t row_bytes,
+                  MpbPair *h, bool *priv);
+
+int check_params(const mpb_filter_params *p);
+double inv_norm_cdf(double p);
+// the parameters of a per-read call (bernoulli's calculate_errors_PB / calculate_errors_poisson): alpha, the rest moira's defaults
+static inline mpb_filter_params per_read_params(double alpha)
+{
+    mpb_filter_params p;
+    p.alpha = alpha; p.uncert = 1.0; p.maxerrors = NAN; p.ambig_mode = MPB_AMBIG_IGNORE; p.flags = 0;
+    return p;
+}
+
+int narrow_rows_from_sample(const int32_t *hist, int n_sample, bool odds = false);
+int64_t pipeline_chunk_reads(int64_t n, int64_t row_stride);
+int poisson_finish_marked(const mpb_filter_params *p, const int32_t *ns, const int32_t *len, int32_t fixed_len, int64_t n,
+                          double *ee, uint8_t *pass, int64_t *n_marked);
+
+bool parse_cpulist(const char *s, cpu_set_t *set, int *count);
+int staging_threads();
+void parallel_copy(void *dst, const void *src, size_t bytes, int threads);
+
+#endif

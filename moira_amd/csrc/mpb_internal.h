@@ -1,40 +1,10 @@
-// mpb_internal.h -- shared between the C-ABI layer (mpb_api.cpp) and the gfx950 kernels
-// (mpb_kernels.hip).  Not installed; the public surface is include/moira_pb.h.
+// mpb_internal.h -- shared between the GPU-facing units of the C-ABI layer (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp,
+// mpb_perread.cpp, mpb_poisson.cpp) and the gfx950 kernels (mpb_kernels.hip).  Not installed; the public surface is include/moira_pb.h.
 #ifndef MPB_INTERNAL_H
 #define MPB_INTERNAL_H
 
 #include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include "../../include/moira_pb.h"     // MPB_FLAG_*, MPB_AMBIG_*
-
-// ---- the reference's verdict on one read (moira.py:827-831, 911, 925-926, 949-950) -------------------------------------------
-// Shared by every kernel that finishes a read and by the host Poisson tail.  P is MpbDevParams or mpb_filter_params (the fields
-// maxerrors, uncert, ambig_mode, flags).  Between mpb_add_ns and mpb_round_and_keep a caller may look at the ee (MPB_FLAG_FAST_FMA's
-// "unsure" test); the helpers write no memory.
-// the read's limit: --maxerrors if set, else len x --uncert (moira.py:925-926, 949-950)
-template <typename P>
-__host__ __device__ __forceinline__ double mpb_limit(const P &p, int li)
-{
-    return (p.maxerrors == p.maxerrors) ? p.maxerrors : (double)li * p.uncert;
-}
-// --ambigs treat_as_errors: the ambiguous bases (N and n) count as errors (moira.py:827-828)
-template <typename P>
-__host__ __device__ __forceinline__ double mpb_add_ns(const P &p, double e, int nsv)
-{
-    return p.ambig_mode == MPB_AMBIG_TREAT_AS_ERRORS ? e + (double)nsv : e;
-}
-// Rounds e IN PLACE -- --round floors the reported ee (moira.py:830-831) -- and returns whether the read is kept: e <= its limit,
-// unless --ambigs disallow finds an upper-case 'N' in it (moira.py:911: 'n' does not count there, so has_n is the caller's,
-// apart from the ambiguity count).  (The limit is computed here, after the disallow test: taking it precomputed as an argument
-// costs k_serve four spilled registers.)
-template <typename P>
-__host__ __device__ __forceinline__ bool mpb_round_and_keep(const P &p, double &e, bool has_n, int li)
-{
-    if (p.flags & MPB_FLAG_ROUND) e = floor(e);
-    if (p.ambig_mode == MPB_AMBIG_DISALLOW && has_n) return false;
-    return e <= mpb_limit(p, li);
-}
+#include "mpb_shared.h"                  // the verdict on one read, MPB_MAX_LEN, MPB_NAR_MIN_ROWS / _MAX_ROWS / _BUCKETS (HIP-free)
 
 // ---- DP row-budget classes -------------------------------------------------------------
 // A read predicted to need J rows of the DP table goes to the smallest class with
@@ -51,7 +21,6 @@ __host__ __device__ __forceinline__ bool mpb_round_and_keep(const P &p, double &
 #define MPB_TILE_MAX_ROWS 1024
 #define MPB_WIDE_WAVES 16
 #define MPB_MAX_ROWS (MPB_TILE_MAX_ROWS * MPB_WIDE_WAVES)
-#define MPB_MAX_LEN 65535                 // longest read (perm_ns and the prepass' marker counts are 16 bits wide)
 #define MPB_MAX_STRIDE 65536              // widest quality-matrix row (bytes)
 #define MPB_SMALL_MAX_STRIDE 16384        // widest row of the one-read-per-wave kernel (a lane peels at most 256 bytes of markers)
 
@@ -164,9 +133,6 @@ struct MpbWorkspace {
 // Three kernels, one arithmetic (nar_run) and one end of a read (nar_finish): k_narrow_rs (a lane walks one or more rows as one
 // stream of whole 128-byte lines, panels staged in registers), k_narrow (any stride: 64-byte panels through an LDS-DMA ring) and
 // k_narrow_rg (ragged batches, groups of 64 reads of nearly one length).
-#define MPB_NAR_MIN_ROWS 2
-#define MPB_NAR_MAX_ROWS 4
-#define MPB_NAR_BUCKETS 16                // k_sample: [0] reads with a lower-case 'n', [r] reads that need r rows (r = 1..14), [15] more
 #define MPB_NAR_MAX_WAVES 8192            // waves of the persistent k_narrow grid (256 CUs x 3 workgroups x 4 waves = 3072 on MI355X)
 #define MPB_NAR_AUTO_MIN_READS (1 << 18)  // below this a batch always takes the ordinary pipeline (unless the path is forced)
 

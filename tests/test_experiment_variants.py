@@ -21,9 +21,10 @@ def variants():
 def test_the_shipped_kernels_have_no_conditional_compilation():
     src = open(os.path.join(ROOT, "moira_amd", "csrc", "mpb_kernels.hip")).read().splitlines()
     assert [l for l in src if l.startswith(("#if", "#ifdef", "#ifndef", "#elif"))] == []
-    for name in ("mpb_api.cpp", "mpb_broker.cpp"):
-        body = open(os.path.join(ROOT, "moira_amd", "csrc", name)).read()
-        assert "MPB_TUNING_KNOBS" not in body
+    from moira_amd.build import HOST_SOURCES
+    assert len(HOST_SOURCES) >= 7 and all(os.path.dirname(p) == os.path.join(ROOT, "moira_amd", "csrc") for p in HOST_SOURCES)
+    for path in HOST_SOURCES:            # every host unit of the library, the broker among them
+        assert "MPB_TUNING_KNOBS" not in open(path).read(), path
     assert len(variants()) >= 4
 
 

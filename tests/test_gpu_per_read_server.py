@@ -1,5 +1,5 @@
 """The per-read entry without a launch per call (round 5): while mpb_calculate_errors_PB is called from a process of its own,
-the context keeps k_serve resident with one mailbox entry (moira_amd/csrc/mpb_api.cpp serve_one; the broker's form:
+the context keeps k_serve resident with one mailbox entry (moira_amd/csrc/mpb_perread.cpp serve_one; the broker's form:
 tests/test_gpu_broker.py).  Same results as the launch per call, whatever happens in between: pauses longer than the kernel's
 lifetime, batch calls that grow (free and re-allocate) the workspace, reads the server does not take."""
 import os

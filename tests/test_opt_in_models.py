@@ -23,7 +23,7 @@ def fma(x, y, z):
 
 
 def py_tables():
-    """{a, b, r} per byte code as the library evaluates them (mpb_api.cpp lut_entry); 0 and 255: the identity {1, 0}."""
+    """{a, b, r} per byte code as the library evaluates them (mpb_hostonly.cpp lut_entry); 0 and 255: the identity {1, 0}."""
     A, B, R = [1.0] * 256, [0.0] * 256, [0.0] * 256
     for c in range(1, 255):
         p = math.pow(10, c / -10.0)

@@ -1,11 +1,10 @@
 #!/bin/bash
-# CPU-only AddressSanitizer + UBSan run of the HOST-side code of the C ABI layer (mpb_api.cpp): packers, the Poisson
-# tail (threaded), argument validation.  The kernels are not involved (GPU sanitizers are not available on this
-# pool): the launch wrappers are stubbed as in tools/tsan_poisson.sh.
+# CPU-only AddressSanitizer + UBSan run of the HOST-side code of the C ABI layer: packers, the Poisson tail (threaded),
+# argument validation.  The kernels are not involved (GPU sanitizers are not available on this pool): all of it lives in
+# the HIP-free unit (mpb_hostonly.cpp), which is all this builds -- no HIP header, no HIP library, no stub.
 set -e
 cd "$(dirname "$0")/.."
 D=${TMPDIR:-/tmp}/mpb_asan; mkdir -p $D
-sed -n '/^cat > \$D\/stubs.cpp/,/^CPP$/p' tools/tsan_poisson.sh | sed '1d;$d' > $D/stubs.cpp
 cat > $D/main.cpp <<'CPP'
 #include "moira_pb.h"
 #include <cmath>
@@ -85,7 +84,6 @@ int main()
     return bad != 0;
 }
 CPP
-g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -pthread -D__HIP_PLATFORM_AMD__ \
-    -I/opt/rocm/include -Iinclude -Imoira_amd/csrc moira_amd/csrc/mpb_api.cpp $D/stubs.cpp $D/main.cpp \
-    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o $D/asan_api
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -pthread -Iinclude \
+    moira_amd/csrc/mpb_hostonly.cpp $D/main.cpp -o $D/asan_api
 ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $D/asan_api

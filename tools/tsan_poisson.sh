@@ -1,35 +1,11 @@
 #!/bin/bash
 # CPU-only ThreadSanitizer run of the Poisson host tail (mpb_poisson_finish_host): two threads reach
 # factorial_table() for the first time concurrently, as two contexts on two threads can.  The HIP kernels are
-# not involved (GPU sanitizers are not available on this pool): mpb_api.cpp is built with g++ against the HIP
-# headers, the launch wrappers are stubbed, and only the host function is called.
+# not involved (GPU sanitizers are not available on this pool): the function lives in the HIP-free unit of the C ABI
+# layer (mpb_hostonly.cpp), which is all this builds -- no HIP header, no HIP library, no stub.
 set -e
 cd "$(dirname "$0")/.."
 D=${TMPDIR:-/tmp}/mpb_tsan; mkdir -p $D
-cat > $D/stubs.cpp <<'CPP'
-#include "mpb_internal.h"
-#include <cstdlib>
-#define STUB { abort(); }
-void mpb_launch_prepass(const uint8_t *, int64_t, int64_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, int32_t *, double *, uint8_t *, hipStream_t, const int32_t *) STUB
-void mpb_launch_small(const uint8_t *, int64_t, int64_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, int32_t *, double *, uint8_t *, hipStream_t, const MpbSmallHost *) STUB
-void mpb_launch_scan(int64_t, const int32_t *, const MpbWorkspace &, hipStream_t) STUB
-void mpb_launch_scatter(int64_t, const int32_t *, const int32_t *, const MpbDevParams &, const MpbWorkspace &, hipStream_t, const int32_t *) STUB
-void mpb_launch_dp(const uint8_t *, int64_t, int64_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, const int32_t *, double *, uint8_t *, hipStream_t) STUB
-void mpb_launch_overflow(const uint8_t *, int64_t, int64_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, const int32_t *, double *, uint8_t *, hipStream_t) STUB
-void mpb_launch_lambda(const uint8_t *, int64_t, int64_t, const int32_t *, int32_t, const double2 *, double *, int32_t *, int32_t *, hipStream_t) STUB
-void mpb_launch_decode(const uint8_t *, const uint8_t *, int64_t, int64_t, const int32_t *, int32_t, int32_t, uint8_t *, int32_t *, hipStream_t) STUB
-void mpb_launch_wide(const uint8_t *, int64_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, const int32_t *, double *, uint8_t *, hipStream_t) STUB
-void mpb_launch_decode_classify(const uint8_t *, const uint8_t *, int32_t, uint8_t *, int32_t *, int64_t, int64_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, int32_t *, double *, uint8_t *, hipStream_t) STUB
-void mpb_launch_encode(const uint8_t *, int64_t, int64_t, int32_t, uint8_t *, uint8_t *, hipStream_t) STUB
-void mpb_launch_count(const uint8_t *, int64_t, const MpbWorkspace &, hipStream_t) STUB
-void mpb_launch_synth(uint8_t *, int64_t, int64_t, int32_t, int32_t, int32_t, int32_t *, uint64_t, int64_t, hipStream_t, int) STUB
-void mpb_launch_narrow(int, int, const uint8_t *, int64_t, int64_t, int32_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, double *, int32_t *, uint8_t *, int, const int *, hipStream_t) STUB
-void mpb_narrow_rg_blocks_per_cu(int *) STUB
-void mpb_launch_sample(const uint8_t *, int64_t, int64_t, int32_t, const int32_t *, const MpbDevParams &, const MpbWorkspace &, int, hipStream_t) STUB
-void mpb_launch_serve(const MpbServeBox &, const double2 *, uint32_t, uint32_t, hipStream_t) STUB
-void mpb_launch_poisson_tail(const double *, const int32_t *, const int32_t *, int64_t, const MpbDevParams &, double *, uint8_t *, int32_t *, MpbPoissonRec *, int32_t, unsigned long long *, hipStream_t) STUB
-void mpb_launch_poisson_patch(const MpbPoissonFix *, int32_t, double *, uint8_t *, hipStream_t) STUB
-CPP
 cat > $D/main.cpp <<'CPP'
 #include "moira_pb.h"
 #include <cmath>
@@ -54,6 +30,5 @@ int main()
     return (rc1 || rc2 || !same) ? 1 : 0;
 }
 CPP
-g++ -std=c++17 -O1 -g -fsanitize=thread -ffp-contract=off -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Imoira_amd/csrc \
-    moira_amd/csrc/mpb_api.cpp $D/stubs.cpp $D/main.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o $D/tsan_poisson
+g++ -std=c++17 -O1 -g -fsanitize=thread -ffp-contract=off -pthread -Iinclude moira_amd/csrc/mpb_hostonly.cpp $D/main.cpp -o $D/tsan_poisson
 TSAN_OPTIONS="halt_on_error=1" $D/tsan_poisson
