@@ -120,7 +120,9 @@ __device__ __forceinline__ bool settled_by_chernoff(const MpbDevParams &prm, flo
 // row longer than 960 bytes is walked in panels of 60 chunk columns, peeled one by one).  Chunks that
 // are complete in every lane of the wave take a path without any masking; the ragged tail fills the
 // bytes past the read's end with Q254 (p = 4e-26).  The four lanes of a read are then combined in a
-// fixed order (deterministic).
+// fixed order (deterministic).  The counts are exact, the sum under an 'n' marker is not (65536 leaves a
+// float 7 fraction bits): a lane that finds an 'n' sums its bytes again without it, so that a read's
+// budget does not depend on its ambiguous bases (tests/test_gpu_front_end.py).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ uint32_t mask_dword(uint32_t w, int nvalid_bytes)
@@ -222,6 +224,25 @@ __device__ __forceinline__ uint4 decode16(const uint4 sq, const uint4 ql, int po
     }
     return make_uint4(decode4(sq.x, ql.x, nv, offset, off4, bad), decode4(sq.y, ql.y, nv - 4, offset, off4, bad),
                       decode4(sq.z, ql.z, nv - 8, offset, off4, bad), decode4(sq.w, ql.w, nv - 12, offset, off4, bad));
+}
+
+// every byte 0xFF ('n') of w as 0xFE (Q254, p = 4e-26: nothing to any sum)
+__device__ __forceinline__ uint32_t lower_as_q254(uint32_t w)
+{
+    return w ^ (zero_bytes(~w) >> 7);
+}
+
+// pre_chunk for one dword whose 'n' bytes count as Q254, byte by byte in pre_chunk's order: the rare second look of a lane that
+// found an 'n' (rolled: it should cost the kernels around it as few registers as can be)
+__device__ __forceinline__ void pre_dword_again(const float2 *tab, uint32_t w, f32x2 &a01, float &s3)
+{
+    w = lower_as_q254(w);
+#pragma unroll 1
+    for (int t = 0; t < 4; t++) {
+        const float2 e = tab[(w >> (8 * t)) & 0xffu];
+        a01 += (f32x2){e.x, e.y};
+        s3 = __builtin_fmaf(e.x, e.y, s3);
+    }
 }
 
 // where the classified-at-source pass (k_classify_linear<., DECODE>) takes its bytes from, and where it leaves the packed matrix
@@ -376,7 +397,25 @@ __global__ __launch_bounds__(256) void k_prepass(const uint8_t *__restrict__ q, 
         }
         // second component = sum p(1-p) (<= 64) + 128 per 'N' + 65536 per 'n': peel the markers
         const float n255 = floorf(a01.y * (1.0f / MPB_MARK_LOWER));
-        const float rem = a01.y - MPB_MARK_LOWER * n255;
+        if (n255 > 0.0f) {
+            // Rare: an 'n' among this lane's bytes of the panel.  The count is exact, but from 65536 on a float steps by 2^-7 and
+            // the p(1-p) of a good base is 1e-3: whatever was summed on top of the marker lost its low bits, and the row budget
+            // with them.  Sum the lane's bytes once more, in the same order, with every 'n' as Q254.  Rare in sequencer output,
+            // where a lower-case 'n' hardly occurs; a batch with 'n' in most reads pays for it (the wave waits for the lanes that
+            // look twice, byte by byte): with 0.3 % of the bytes 'n' the pass takes 2.7 x as long on rows of 320 bytes and
+            // 4 x on rows of 2048, and as long as before on input without 'n' at every shape (tools/front_end_rate.py).
+            a01 = (f32x2){0.f, 0.f};
+            s3 = 0.f;
+#pragma unroll 1
+            for (int c0 = pb; c0 < pend; c0 += 4) {
+                const int nv = li - (c0 + cl) * 16;
+                if (nv <= 0) break;                        // (bytes past the read's end: Q254 in the sums above, nothing here)
+#pragma unroll 1
+                for (int d = 0; d < 4; d++)
+                    pre_dword_again(s_tab, fill_dword(*reinterpret_cast<const uint32_t *>(src + c0 * 16 + d * 4), nv - 4 * d), a01, s3);
+            }
+        }
+        const float rem = a01.y;                                          // (no 'n' marker in it by now)
         const float nzero = floorf(rem * (1.0f / MPB_MARK_UPPER));
         const float pvar = rem - MPB_MARK_UPPER * nzero;
         mu += a01.x;
@@ -506,7 +545,13 @@ __global__ __launch_bounds__(256) void k_classify_linear(const uint8_t *__restri
                 float s3 = 0.f;
                 pre_chunk(s_tab, y, a01, s3);
                 const float n255 = floorf(a01.y * (1.0f / MPB_MARK_LOWER));
-                const float rem = a01.y - MPB_MARK_LOWER * n255;
+                if (n255 > 0.0f) {                                        // rare: an 'n' in the chunk; as in k_prepass, the sums without its marker
+                    a01 = (f32x2){0.f, 0.f};
+                    s3 = 0.f;
+                    pre_dword_again(s_tab, y.x, a01, s3); pre_dword_again(s_tab, y.y, a01, s3);
+                    pre_dword_again(s_tab, y.z, a01, s3); pre_dword_again(s_tab, y.w, a01, s3);
+                }
+                const float rem = a01.y;                                  // (no 'n' marker in it by now)
                 const float nzero = floorf(rem * (1.0f / MPB_MARK_UPPER));
                 const float pvar = rem - MPB_MARK_UPPER * nzero;
                 part = make_float4(a01.x, pvar, pvar - 2.0f * s3, __uint_as_float((uint32_t)nzero + ((uint32_t)n255 << 16)));
@@ -1167,6 +1212,8 @@ __device__ __forceinline__ bool small_one_read(const DpArgs &args, const DpArgs 
             pre_chunk(s_tab, y, a01, s3);
         }
     }
+    // (Unlike k_prepass, no second look for a read that holds an 'n': under its marker the sum steps by 2^-7, so such a read's budget
+    // here may differ from the one k_prepass gives it.  The budget only chooses the body; a miss is re-run, the result is the same.)
     const float n255 = floorf(a01.y * (1.0f / MPB_MARK_LOWER));
     const float rem = a01.y - MPB_MARK_LOWER * n255;
     const float nzero_f = floorf(rem * (1.0f / MPB_MARK_UPPER));
@@ -2406,6 +2453,7 @@ __global__ __launch_bounds__(256) void k_sample(const uint8_t *__restrict__ q, i
                     lp0 += e.x; t1 += e.y; t2 += e.z; t3 += e.w;
                 }
         }
+        // (no second look under an 'n' marker, unlike k_prepass: the sample only counts such a read as handed back, its rows do not matter)
         const float n255 = floorf(a01.y * (1.0f / MPB_MARK_LOWER));
         const float rem = a01.y - MPB_MARK_LOWER * n255;
         const float nzero = floorf(rem * (1.0f / MPB_MARK_UPPER));

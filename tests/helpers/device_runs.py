@@ -65,20 +65,34 @@ class Resident:
             b.free()
 
 
-def classified_pair(eng, q, lens, fixed_len=None, **kw):
+def classified_pair(eng, q, lens, fixed_len=None, front_end=False, **kw):
     """The batch as FASTQ text in HBM (mpb_encode_ascii_device) through mpb_decode_classify_device +
-    mpb_filter_device_classified -> (ee, ns, pass, counts)."""
+    mpb_filter_device_classified -> (ee, ns, pass, counts); with front_end=True the result arrays lie between guard elements
+    (two in front, one behind, as Resident's) and the tuple goes on with the budgets and the class histogram the library reports
+    after the pair, the packed matrix the decode pass wrote, and whether every guard still holds its sentinel."""
     n, stride = q.shape
+    g = 2 if front_end else 0                         # guard elements in front of the results (one behind)
+    m = n + (3 if front_end else 0)
     d_q, d_seq, d_qual, d_out = (eng.alloc(max(1, n * stride)) for _ in range(4))
     d_len = eng.alloc(max(1, n) * 4).upload(np.ascontiguousarray(lens, np.int32)) if fixed_len is None else None
-    d_ee, d_ns, d_pass = eng.alloc(n * 8), eng.alloc(n * 4), eng.alloc(n)
+    d_ee, d_ns, d_pass = eng.alloc(m * 8), eng.alloc(m * 4), eng.alloc(m)
     try:
         d_q.upload(np.ascontiguousarray(q))
         eng.encode_ascii_device(d_q, n, stride, d_seq, d_qual)
-        d_ee.upload(np.full(n, SENT_EE))
+        d_ee.upload(np.full(m, SENT_EE))
+        if front_end:
+            d_ns.upload(np.full(m, SENT_NS, np.int32))
+            d_pass.upload(np.full(m, SENT_PS, np.uint8))
         c = eng.filter_ascii_device(d_seq, d_qual, n, stride, d_out, d_len=d_len, fixed_len=0 if fixed_len is None else fixed_len,
-                                    d_ee=d_ee, d_ns=d_ns, d_pass=d_pass, params=eng.params(**kw))
-        return d_ee.download(np.float64, n), d_ns.download(np.int32, n), d_pass.download(np.uint8, n), c
+                                    d_ee=d_ee.ptr + 8 * g, d_ns=d_ns.ptr + 4 * g, d_pass=d_pass.ptr + g, params=eng.params(**kw))
+        ee, ns, ps = d_ee.download(np.float64, m), d_ns.download(np.int32, m), d_pass.download(np.uint8, m)
+        out = ee[g:g + n], ns[g:g + n], ps[g:g + n], c
+        if front_end:
+            outside = np.ones(m, bool)
+            outside[g:g + n] = False
+            intact = (ee[outside] == SENT_EE).all() and (ns[outside] == SENT_NS).all() and (ps[outside] == SENT_PS).all()
+            out += (eng.read_budgets(n), eng.class_histogram(), d_out.download(np.uint8, n * stride).reshape(n, stride), bool(intact))
+        return out
     finally:
         for b in (d_q, d_seq, d_qual, d_out, d_len, d_ee, d_ns, d_pass):
             if b is not None:
