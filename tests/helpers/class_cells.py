@@ -13,8 +13,9 @@ The places of a body that have code of their own are rows, so a test aims at (cl
             class with G > 1: a row of lane 0, both sides of the lane 0 / 1 boundary, both sides of the boundary at
             g = G / 2, the first row of the last lane -- where a read can reach it (see overflow_unreachable)
   wide      the tile / wide boundary (budget 1024 with J = 1024; a wide read with J <= 1024) and k_wide's wave boundaries
-            (js = 1023, 1024, 2047, 2048)
-  thin      the ten one-read-per-wave bodies (MPB_THIN_CLASSES: cap = the next power of two >= the predicted rows):
+            (js = 1023, 1024, 2047, 2048); every wave boundary of all four k_wide instances, both passes and the list loop:
+            helpers/wide_cells.py
+  thin     the ten one-read-per-wave bodies (MPB_THIN_CLASSES: cap = the next power of two >= the predicted rows):
             first reachable row (cap / 2; 0 for cap 2), last row, and one lane boundary (g = 3 G / 4) where R > 1
   modes     MPB_FLAG_FAST_FMA and MPB_FLAG_ODDS compile every class body once more, so the main cells are required again per
             mode, by the crossing row of the mode's CPU model (generate(mode=...), ledger_mode); ODDS keeps a read only while
