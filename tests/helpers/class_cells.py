@@ -16,7 +16,10 @@ The places of a body that have code of their own are rows, so a test aims at (cl
             (js = 1023, 1024, 2047, 2048); every wave boundary of all four k_wide instances, both passes and the list loop:
             helpers/wide_cells.py
   thin     the ten one-read-per-wave bodies (MPB_THIN_CLASSES: cap = the next power of two >= the predicted rows):
-            first reachable row (cap / 2; 0 for cap 2), last row, and one lane boundary (g = 3 G / 4) where R > 1
+            first reachable row (cap / 2; 0 for cap 2), last row, and one lane boundary (g = 3 G / 4) where R > 1.  These are the
+            bodies of k_small (a launch per batch of at most 4096 reads, or per call with MPB_SERVE=0).  The resident kernel
+            k_serve, which answers a per-read call, runs them only for a read of more than 1024 bases or more than 64 predicted
+            rows; any other read runs its register-resident body, whose cells are helpers/serve_cells.py's
   modes     MPB_FLAG_FAST_FMA and MPB_FLAG_ODDS compile every class body once more, so the main cells are required again per
             mode, by the crossing row of the mode's CPU model (generate(mode=...), ledger_mode); ODDS keeps a read only while
             p0 >= 2^-900, which puts the far rows of class 1024 out of every read's reach (odds_unreachable)

@@ -173,8 +173,13 @@ def test_classified_at_source_pair(eng, batches, want):
 
 
 def test_per_read_entry_on_the_thin_and_wide_boundary_reads(eng, oracle, batches, want, device_runs):
-    """bernoulli.calculate_errors_PB's twin, read by read (the resident one-read kernel): up to two reads per thin cell and per
-    wide cell, and every read of the stride-4096 batches."""
+    """bernoulli.calculate_errors_PB's twin, read by read (the resident one-read kernel, k_serve): up to two reads per thin cell
+    and per wide cell of the ledger, and every read of the stride-4096 batches.  The thin ledger names the body k_small runs
+    (test_small_path).  Under k_serve a read of at most 1024 bases and at most 64 predicted rows runs the register-resident body
+    instead, so of the reads picked here only those of more than 1024 bases or of caps 128 .. 1024 run the thin body the ledger
+    names, a read of more than 2047 bases takes the host path, and the wide cells are handed back by the kernel and answered by
+    the host.  The register body's own cells, and the thin bodies of cap <= 64 as k_serve runs them (reads of 1025 .. 2047
+    bases), are tests/test_gpu_serve_edges.py's."""
     todo = []
     seen = {}
     for b in batches:
