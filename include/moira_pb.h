@@ -150,7 +150,8 @@ extern "C" {
 #define MPB_K_FALLBACK  8   /* (rounds 5: the gather of the unfinished reads and the scatter of their results; unused since round 6: they run where they lie) */
 #define MPB_K_SAMPLE    9   /* ... the batch sample that picks the pass */
 #define MPB_K_POISSON_TAIL 10 /* Poisson approximation: the CDF tail on the device (percentile, +Ns / floor, predicate) */
-#define MPB_K_COUNT     11
+#define MPB_K_PACK_TEXT 11   /* FASTQ text + record index -> the packed ragged matrix (k_pack_text) */
+#define MPB_K_COUNT     12
 
 typedef struct mpb_ctx mpb_ctx;
 
@@ -258,6 +259,56 @@ int mpb_decode_ascii_device(mpb_ctx *ctx, const uint8_t *d_seq, const uint8_t *d
 int mpb_encode_ascii_device(mpb_ctx *ctx, const uint8_t *d_q, int64_t n, int64_t row_stride, int32_t fastq_offset,
                             uint8_t *d_seq_out, uint8_t *d_qual_out);
 
+/*
+ * Packing on the device from the text AS IT LIES IN THE FILE (one step further): a chunk of FASTQ text plus
+ * its record index -- what include/moira_io.h's mio_fastq_index yields, and the shape mct_contigs_from_fastq gives its contigs
+ * (include/moira_contig.h: out_buf + out_idx) -- becomes the packed, zero-padded ragged matrix, the lengths and the has-'N'
+ * flags, with no host pack.  The bytes are those of moira_io.h's mio_pack, bit for bit.
+ *
+ * The index has six int64 columns per record.  This library does not include moira_io.h (the two libraries stay independent of
+ * each other); the column numbers are restated here and must equal MIO_SEQ_OFF / MIO_QUAL_OFF / MIO_QUAL_LEN / MIO_IDX_COLS:
+ */
+#define MPB_IDX_SEQ_OFF  2   /* byte offset of the sequence line (stripped) */
+#define MPB_IDX_QUAL_OFF 4   /* byte offset of the quality line (stripped) */
+#define MPB_IDX_QUAL_LEN 5   /* its length = the bases of the record */
+#define MPB_IDX_COLS     6
+
+typedef struct mpb_text_row { int64_t seq_off, qual_off; int32_t len, pad; } mpb_text_row;   /* 24 bytes */
+
+/*
+ * Host only: the VALIDATED row descriptors of n records -- the only place offsets are trusted from.
+ *   idx          int64[n_records][MPB_IDX_COLS]
+ *   sel          NULL: rows 0..n-1 describe records 0..n-1 (n <= n_records); otherwise row k describes record sel[k]
+ *   text_bytes   bytes of the text the offsets point into
+ *   max_len      > 0: at most that many bases of each record are packed (mio_pack's rule: len = min(QUAL_LEN, max_len))
+ *   row_stride   0: validation and *longest_out only (rows_out may be NULL), so that a caller can size the matrix first
+ *   longest_out  the longest packed length (may be NULL)
+ * Validation is never clamping.  MPB_E_INVALID with *bad_record = k (the position in sel order; bad_record may be NULL) when
+ * an offset or a length is negative, seq_off + len or qual_off + len lies past text_bytes, sel[k] is outside 0..n_records-1,
+ * a packed length is above 65535, or it is above a non-zero row_stride.  A record that ends exactly at text_bytes is fine.
+ */
+int mpb_text_rows(const int64_t *idx, int64_t n_records, const int64_t *sel, int64_t n, int64_t text_bytes,
+                  int32_t max_len, int64_t row_stride, mpb_text_row *rows_out, int64_t *longest_out, int64_t *bad_record);
+
+/*
+ * k_pack_text: d_text + d_rows[n] (mpb_text_rows' descriptors, uploaded) -> d_q_out[n][row_stride] (row_stride % 16 == 0,
+ * 16-byte aligned), d_len_out[n], d_flags_out[n] (bit 0: the packed part holds an upper-case 'N'; may be NULL).
+ * Per base: Q = byte - fastq_offset, Q0 -> 1, sequence byte 'N' -> 0, 'n' -> 255 unless lower_n_is_base; bytes [len, row_stride)
+ * are zero.  fastq_offset must lie in 0..255 (MPB_E_INVALID otherwise: every byte would be out of range).
+ * d_text must be 16-byte aligned and its ALLOCATION must hold round_up(text_bytes, 16) bytes: the kernel fetches whole aligned
+ * 16-byte words, never one outside [d_text, d_text + round_up(text_bytes, 16)), and no byte past a record's end reaches an output.
+ * A quality below 0 or above 254 is written as Q1 / Q254 (as mpb_decode_ascii_device does) and reported through d_status, a
+ * device int64[2] the CALLER initialises to INT64_MAX: [0] = the smallest row position k with some Q < 0, [1] = the same for
+ * Q > 254 (atomic min).  mio_pack's answer from them: the first bad record is the smaller of the two, and its "positive values"
+ * message wins when slot 0 holds that record.
+ * A descriptor that mpb_text_rows would have refused (the kernel checks offsets and length against text_bytes and row_stride
+ * again: nothing is read or written out of bounds whatever d_rows holds) gives a zero row and d_len_out[k] = -1, which
+ * mpb_filter_device reports as a bad length.  Asynchronous on the context's stream.
+ */
+int mpb_pack_text_device(mpb_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, const mpb_text_row *d_rows, int64_t n,
+                         int32_t fastq_offset, int32_t lower_n_is_base, int64_t row_stride,
+                         uint8_t *d_q_out, int32_t *d_len_out, uint8_t *d_flags_out, int64_t *d_status);
+
 /* ---- the hot path --------------------------------------------------------- */
 /*
  * Filter a batch that is RESIDENT IN HBM.
@@ -356,6 +407,29 @@ int mpb_filter_host(mpb_ctx *ctx,
                     const mpb_filter_params *params,
                     double *ee, int32_t *ns, uint8_t *pass,
                     mpb_filter_counts *counts);
+
+/*
+ * Text in, results out: a chunk of FASTQ text in HOST memory with its record index (see mpb_text_rows) is uploaded once,
+ * packed on the device (k_pack_text) and filtered there; synchronous.  In this order: mpb_text_rows on the host, before
+ * anything is uploaded (MPB_E_INVALID, *bad_record); row stride = round_up(max(longest, 1), 128), the ragged narrow pass'
+ * layout; the text is uploaded whole (more than 1 GiB of text is MPB_E_INVALID: split the chunk); the descriptors are
+ * uploaded; then consecutive row ranges whose piece of the matrix is at most 256 MiB are packed and filtered one after the
+ * other -- mpb_filter_device (poisson == 0), or what mpb_filter_poisson_host computes (poisson != 0: k_lambda and the host
+ * tail; with MPB_FLAG_POISSON_DEVICE_TAIL, mpb_filter_poisson_device) -- and the results are copied out at the end.
+ *   ee, ns, pass        as mpb_filter_host; len_out int32[n] and flags_out uint8[n] (bit 0: an upper-case 'N' among the packed
+ *                       bases) may be NULL
+ *   counts              may be NULL; the totals over all pieces
+ * A quality character outside the encodable range gives MPB_E_RANGE with mio_pack's message ("Qualities must have positive
+ * values." / "quality exceeds the encodable maximum 254") and *bad_record = the first such record in sel order, and then NO
+ * result array is written for any read.  Results are bit-identical to mio_pack + mpb_filter_host / mpb_filter_poisson_host on
+ * the same records.  The staging blocks belong to the context, grow on demand and are freed with it.
+ * (Environment MPB_TEXT_PIECE_BYTES: a smaller piece limit, for tests of the piece loop.)
+ */
+int mpb_filter_text_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, const int64_t *idx, int64_t n_records,
+                         const int64_t *sel, int64_t n, int32_t fastq_offset, int32_t max_len, int32_t lower_n_is_base,
+                         const mpb_filter_params *params, int32_t poisson,
+                         double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out,
+                         mpb_filter_counts *counts, int64_t *bad_record);
 
 /*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is

@@ -27,8 +27,10 @@ def FLAG_NARROW_ROWS(r):
 
 K_PREPASS, K_SCAN, K_SCATTER, K_DP, K_OVERFLOW, K_LAMBDA, K_WIDE, K_NARROW, K_FALLBACK, K_SAMPLE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 K_POISSON_TAIL = 10
+K_PACK_TEXT = 11               # MPB_K_PACK_TEXT: FASTQ text + record index -> the packed ragged matrix (k_pack_text)
 KERNEL_NAMES = {K_PREPASS: "prepass", K_SCAN: "scan", K_SCATTER: "scatter", K_DP: "dp", K_OVERFLOW: "overflow", K_LAMBDA: "lambda",
-                K_WIDE: "wide", K_NARROW: "narrow", K_FALLBACK: "fallback", K_SAMPLE: "sample", K_POISSON_TAIL: "poisson_tail"}
+                K_WIDE: "wide", K_NARROW: "narrow", K_FALLBACK: "fallback", K_SAMPLE: "sample", K_POISSON_TAIL: "poisson_tail",
+                K_PACK_TEXT: "pack_text"}
 
 
 class MoiraPBError(RuntimeError):
@@ -54,6 +56,11 @@ class FilterCounts(C.Structure):
                 ("n_overflow", C.c_int64)]
 
 
+class TextRow(C.Structure):
+    """mpb_text_row: one validated row descriptor of k_pack_text (24 bytes)."""
+    _fields_ = [("seq_off", C.c_int64), ("qual_off", C.c_int64), ("len", C.c_int32), ("pad", C.c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/moira_pb.h declares
 _VP, _I32P, _U8P, _DP = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
 PROTOTYPES = {
@@ -77,6 +84,12 @@ PROTOTYPES = {
     "mpb_pack_read_ascii": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, _VP, C.c_int32]),
     "mpb_pack_batch_ascii": (C.c_int, [C.c_char_p, C.c_char_p, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _VP, _VP]),
     "mpb_decode_ascii_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32, _VP, _VP]),
+    "mpb_text_rows": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _VP, C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int64)]),
+    "mpb_pack_text_device": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _VP, _VP, _VP, _VP]),
+    "mpb_filter_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP, C.POINTER(FilterCounts),
+                                       C.POINTER(C.c_int64)]),
     "mpb_encode_ascii_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP]),
     "mpb_decode_classify_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
                                              C.POINTER(FilterParams), _VP, _VP, _VP, _VP, _VP]),

@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmoira_pb.so")
 # the host side of the library: the C ABI layer, unit by unit (mpb_hostonly.cpp includes no HIP header), and the broker
 HOST_SOURCES = [os.path.join(CSRC, name) for name in ("mpb_hostonly.cpp", "mpb_context.cpp", "mpb_resident.cpp", "mpb_hostfed.cpp",
-                                                      "mpb_perread.cpp", "mpb_poisson.cpp", "mpb_broker.cpp")]
+                                                      "mpb_perread.cpp", "mpb_poisson.cpp", "mpb_text.cpp", "mpb_broker.cpp")]
 SOURCES = [os.path.join(CSRC, "mpb_kernels.hip")] + HOST_SOURCES
 DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_host_internal.h"),
                   os.path.join(CSRC, "mpb_shared.h"), os.path.join(CSRC, "mpb_hostonly.h"), os.path.join(CSRC, "mpb_ctx.h"),

@@ -231,6 +231,11 @@ def build_parser():
                    help="(not in moira.py) skip the exact error calculation for reads that provably exceed the "
                         "threshold; only with --collapse false and the mothur pipeline, where the expected errors "
                         "of a discarded read are never used. Kept/discarded sets are unchanged.")
+    f.add_argument("--device_pack", action="store_true",
+                   help="(not in moira.py) FASTQ input on one GPU: upload each chunk of text as it lies in the file and build the "
+                        "quality matrix on the device (one call per chunk) instead of packing it on the host, one length bucket "
+                        "at a time. Results and output files are identical. Where it does not apply (fasta+qual input, the line "
+                        "parser, several GPUs, no GPU) one line says so and host packing is used.")
     return p
 
 
@@ -559,8 +564,21 @@ def make_gpu_backend(device=None):
             return r.ee    # settled reads: +inf from the kernel; a NaN is a genuine failure and raises ReturnedNaNError
         run = eng.filter_poisson if method == "poisson" else eng.filter
         return run(q, lens=lens, alpha=alpha, ambigs=ambigs, round_=round_, uncert=1.0).ee
+    def text(buf, idx, alpha, ambigs, round_, fastq_offset, max_len, lower_n_is_base, method="poisson_binomial", fast_discard=None):
+        """The same for a chunk of FASTQ text as it lies in the file and its record index (--device_pack): the quality
+        matrix is built on the device.  -> (ee per record, has_n per record)."""
+        kw = dict(fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base, alpha=alpha, ambigs=ambigs,
+                  round_=round_)
+        if fast_discard is not None and method == "poisson_binomial":
+            uncert, maxerrors = fast_discard
+            r = eng.filter_text(buf, idx, uncert=uncert, maxerrors=maxerrors, decision_only=True, **kw)
+        else:
+            r = eng.filter_text(buf, idx, poisson=method == "poisson", uncert=1.0, **kw)
+        return r.ee, r.has_n
     backend.engine = eng
     backend.matrix = matrix
+    if len(devs) == 1:
+        backend.text = text                            # one device (the text entry has no multi-GPU form)
     backend.per_read = eng.calculate_errors_PB         # any int quality (a read whose scores do not fit the byte matrix)
     backend.per_read_poisson = eng.calculate_errors_poisson
     backend.methods = ("poisson_binomial", "poisson")
@@ -902,6 +920,11 @@ def _fast_eligible(args, backend):
                 and (args.error_calc != "poisson" or "poisson" in getattr(backend, "methods", ())))
 
 
+def _device_pack_eligible(args, backend):
+    """--device_pack applies to a run the byte-level path takes, FASTQ input, on a backend that packs text on its device."""
+    return bool(args.forward_fastq and getattr(backend, "text", None) is not None and 0 <= args.fastq_offset <= 255)
+
+
 def _record_error(which, e, args):
     """The exception the line parser raises for a record that fails its checks (moira.py:1178-1195;
     the reverse file's empty-line errors name the forward header and file, as there)."""
@@ -1089,7 +1112,7 @@ def _fast_chunks_fasta_qual(args):
             f.close()
 
 
-def _run_fast_fastq(args, backend, o, say, t0):
+def _run_fast_fastq(args, backend, o, say, t0, device_pack=False):
     """Chunks of the input as (buffer, record index); contig construction, packing, collapse and record
     formatting in C (moira_amd/fastio.py, moira_amd/contig.py).  Decisions are write_results'
     (ref: moira/moira.py:842-970), vectorised.
@@ -1131,6 +1154,7 @@ def _run_fast_fastq(args, backend, o, say, t0):
         return label
 
     processed = 0
+    refused_once = False                                 # --device_pack: a chunk went through the host path after all
     disc_err = disc_len = disc_ov = 0.0
     threads = _text_threads(args)                        # --processors: packing / formatting calls in flight
     groups = F.Collapse(threads) if args.collapse else None
@@ -1161,7 +1185,20 @@ def _run_fast_fastq(args, backend, o, say, t0):
             strides = bucket_of(lens, 64)
             ee = np.zeros(n, np.float64)                 # --only_contig: process_data returns 0 (moira.py:809-810)
             has_n = np.zeros(n, bool)
-            for stride in (np.unique(strides) if not only else ()):
+            packed = False
+            if device_pack and not only and n:
+                # --device_pack: the chunk's text goes up as it lies, one call.  A ValueError (a quality character out of range, a
+                # text the entry does not take) sends the chunk through the host path below, which raises what it always raised
+                # -- or takes the chunk; the first such chunk of a run is reported, so that the switch never fails silently.
+                try:
+                    ee, has_n = backend.text(buf, idx, args.alpha, args.ambigs, args.round, in_off, T, n_is_base, method=method,
+                                             fast_discard=fd)
+                    packed = True
+                except ValueError as e:
+                    if not refused_once and not args.nowarnings:
+                        say("--device_pack: the device did not take a chunk (%s): host packing is used for it." % e)
+                    refused_once = True
+            for stride in (np.unique(strides) if not (only or packed) else ()):
                 sel = np.nonzero(strides == stride)[0]
                 q, ln, fl = F.pack_parallel(pool, threads, buf, idx, sel, in_off, T, n_is_base, int(stride))
                 ee[sel] = backend.matrix(q, ln, args.alpha, args.ambigs, args.round, method=method, fast_discard=fd)
@@ -1305,6 +1342,12 @@ def main(args, backend=None, out=None, _no_fastio=False):
     if backend is None and needs_gpu:
         backend = make_gpu_backend(getattr(args, "device", None))
     fast = _fast_eligible(args, backend) and not _no_fastio
+    device_pack = bool(getattr(args, "device_pack", False)) and not args.only_contig
+    if device_pack and not (fast and _device_pack_eligible(args, backend)):
+        device_pack = False
+        if not args.nowarnings:
+            say("--device_pack does not apply to this run (it takes FASTQ input through the byte-level parser on one GPU): "
+                "host packing is used.")
     try:
         o = _open_outputs(args, output_name, binary=fast)
     except IOError as e:
@@ -1346,7 +1389,7 @@ def main(args, backend=None, out=None, _no_fastio=False):
         if fast:
             from . import fastio
             try:
-                processed, disc_err, disc_len, disc_ov = _run_fast_fastq(args, backend, o, say, t0)
+                processed, disc_err, disc_len, disc_ov = _run_fast_fastq(args, backend, o, say, t0, device_pack=device_pack)
             except fastio.Unsupported:
                 # content the byte-level parser does not reproduce: start over with the line parser
                 _close(o)

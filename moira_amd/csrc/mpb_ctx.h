@@ -1,6 +1,6 @@
 // mpb_ctx.h -- the context of the C ABI (struct mpb_ctx) and what the GPU-facing host units share: the error macros, the owner of
 // a growable block (Buf), the carver that lays a block out (Carver), the timing span, and the few functions that cross units
-// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp).  Not installed.
+// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp, mpb_text.cpp).  Not installed.
 #ifndef MPB_CTX_H
 #define MPB_CTX_H
 
@@ -106,6 +106,7 @@ struct PinWords {
     int32_t pt_handed;                                   // reads the Poisson device tail handed back
     unsigned long long pt_kept;                          // ... and the reads it kept
     long long ovf_total;                                 // host pipeline: overflow re-runs of all chunks
+    int64_t text_status[2];                              // mpb_filter_text_host: k_pack_text's status, both ways
 };
 
 struct TimedSpan { int kid; hipEvent_t a, b; };
@@ -170,6 +171,7 @@ struct mpb_ctx {
     Buf ws_rg{BUF_DEVICE}; int64_t ws_rg_cap = 0;    // the ragged pass' order entries, group costs, wave ranges (first ragged call)
     Buf pt_rec{BUF_DEVICE};              // MPB_PT_REC_CAP records of reads k_poisson_tail handed back (first device-tail call)
     int rg_per_cu[MPB_NRG_FORMS] = {0};  // blocks per CU of the ragged pass' instantiations (the first ragged call)
+    Buf text_stage{BUF_DEVICE};          // mpb_filter_text_host: text | descriptors | status | one piece of the matrix | the results of the call
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)

@@ -178,6 +178,43 @@ int mpb_pack_batch_ascii(const char *seq_cat, const char *qual_cat, const int64_
     return MPB_OK;
 }
 
+// The row descriptors k_pack_text walks, from a record index (include/moira_io.h's six columns, restated in moira_pb.h).  This is
+// the only place the offsets of a text are trusted from: every one is checked against the text here, before anything is uploaded.
+int mpb_text_rows(const int64_t *idx, int64_t n_records, const int64_t *sel, int64_t n, int64_t text_bytes, int32_t max_len,
+                  int64_t row_stride, mpb_text_row *rows_out, int64_t *longest_out, int64_t *bad_record)
+{
+    if (bad_record) *bad_record = -1;
+    if (longest_out) *longest_out = 0;
+    if (n < 0 || n_records < 0 || text_bytes < 0 || row_stride < 0 || (n > 0 && !idx) || (n_records > 0 && !idx))
+        return fail(MPB_E_INVALID, "mpb_text_rows: bad arguments");
+    if (row_stride > 0 && n > 0 && !rows_out) return fail(MPB_E_INVALID, "mpb_text_rows: rows_out is NULL");
+    if (!sel && n > n_records) return fail(MPB_E_INVALID, "mpb_text_rows: %lld rows asked of an index of %lld records", (long long)n, (long long)n_records);
+    int64_t longest = 0;
+    for (int64_t k = 0; k < n; k++) {
+        auto bad = [&](const char *what, long long v) {
+            if (bad_record) *bad_record = k;
+            return fail(MPB_E_INVALID, "record at position %lld: %s (%lld)", (long long)k, what, v);
+        };
+        const int64_t r = sel ? sel[k] : k;
+        if (r < 0 || r >= n_records) return bad("sel entry outside the index", (long long)r);
+        const int64_t *row = idx + r * MPB_IDX_COLS;
+        const int64_t so = row[MPB_IDX_SEQ_OFF], qo = row[MPB_IDX_QUAL_OFF];
+        int64_t len = row[MPB_IDX_QUAL_LEN];
+        if (so < 0) return bad("negative sequence offset", (long long)so);
+        if (qo < 0) return bad("negative quality offset", (long long)qo);
+        if (len < 0) return bad("negative length", (long long)len);
+        if (max_len > 0 && len > max_len) len = max_len;                 // mio_pack's rule
+        if (len > MPB_MAX_LEN) return bad("reads longer than 65535 bases are not supported; length", (long long)len);
+        if (len > text_bytes || so > text_bytes - len) return bad("the sequence line ends past the text; offset", (long long)so);
+        if (qo > text_bytes - len) return bad("the quality line ends past the text; offset", (long long)qo);
+        if (row_stride > 0 && len > row_stride) return bad("the read does not fit the row; length", (long long)len);
+        if (len > longest) longest = len;
+        if (row_stride > 0) { rows_out[k].seq_off = so; rows_out[k].qual_off = qo; rows_out[k].len = (int32_t)len; rows_out[k].pad = 0; }
+    }
+    if (longest_out) *longest_out = longest;
+    return MPB_OK;
+}
+
 // Phi^-1 (Acklam's rational approximation, |rel err| < 1.2e-9): only steers the row-budget
 // prediction, never a result.
 double inv_norm_cdf(double p)

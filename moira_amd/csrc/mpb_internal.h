@@ -215,6 +215,11 @@ void mpb_launch_poisson_patch(const MpbPoissonFix *fix, int32_t m, double *ee, u
 void mpb_launch_decode(const uint8_t *seq, const uint8_t *qual, int64_t n, int64_t stride, const int32_t *len,
                        int32_t fixed_len, int32_t offset, uint8_t *out, int32_t *err, hipStream_t s);
 void mpb_launch_count(const uint8_t *pass, int64_t n, const MpbWorkspace &ws, hipStream_t s);
+// k_pack_text: text + validated row descriptors -> n rows of `stride` bytes, lengths, has-'N' flags (may be nullptr); status[2] (set to
+// INT64_MAX by the caller) takes the smallest row position, counted from k0, with a quality below 0 / above 254.  offset in 0..255.
+void mpb_launch_pack_text(const uint8_t *text, int64_t text_bytes, const mpb_text_row *rows, int64_t n, int64_t k0, int32_t offset,
+                          bool lower_n_is_base, int64_t stride, uint8_t *out, int32_t *len_out, uint8_t *flags_out,
+                          int64_t *status, hipStream_t s);
 // the natural-order narrow pass (the context's default table), rows0 in MPB_NAR_MIN_ROWS..MPB_NAR_MAX_ROWS: fixed-length batches
 // (len == nullptr: k_narrow_rs, or k_narrow for rows of no multiple of 64 bytes at three or four rows) and ragged ones (k_rag_sort,
 // k_rag_scan, k_narrow_rg: rows of up to MPB_RG_MAX_STRIDE bytes; split_chunks > 0, rows0 >= 3: groups whose longest read has at

@@ -1758,6 +1758,117 @@ __global__ __launch_bounds__(256) void k_encode_ascii(const uint8_t *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------
+// k_pack_text: a chunk of FASTQ text as it lies in the file + validated row descriptors (mpb_text_rows) -> the packed,
+// zero-padded ragged matrix, the lengths and the has-'N' flags (include/moira_pb.h, mpb_pack_text_device).  The bytes are
+// mio_pack's (csrc/fastio.cpp): Q = byte - offset, Q0 -> 1, 'N' -> 0, 'n' -> 255 unless LOWER_BASE.
+// A pure stream: eight consecutive lanes own one row and walk its 16-byte chunks eight at a time, so a wave writes eight runs
+// of 128 consecutive bytes per step (whole lines at the strides the ragged narrow pass wants).  The two source lines of a
+// record start at arbitrary byte offsets: a lane fetches the one or two ALIGNED 16-byte words that cover the 16 bytes it
+// needs (the second only when its bytes reach into it; the neighbour lane asked for the same word, so it costs the memory
+// nothing) and funnels them with byte-align shifts.  No word outside [text, text + round_up(text_bytes, 16)) is ever asked for:
+// a word is fetched only when a validated base lies in it.  Bytes past the read's end are masked before they reach the
+// matrix, the status or the flags.
+// ------------------------------------------------------------------------------------------
+#define MPB_PT_BELOW 1u           // a lane's findings: some Q < 0
+#define MPB_PT_ABOVE 2u           // ... some Q > 254
+#define MPB_PT_UPPER 4u           // ... an upper-case 'N'
+
+// [k_pack_text chunk code: begin]  (tests/test_text_rows.py runs everything up to the end mark on the host, with decode16 above)
+// 16 bases of one row by decode16's rules (one statement of them for both decoders), of which the first nv are inside the read.
+// LOWER_BASE: a lower-case 'n' is a base like any other -- it reaches decode16 as an 'o'.  What decode16 counts as bad is one
+// kind per call: with an offset of 1..255 no Q exceeds 254, with offset 0 none is negative.
+template <bool LOWER_BASE>
+__device__ __forceinline__ uint4 pack16(const uint4 sq, const uint4 ql, int nv, int offset, uint32_t &st)
+{
+    const uint32_t sw[4] = {sq.x, sq.y, sq.z, sq.w};
+    uint32_t tw[4];
+    uint32_t upper = 0;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const int v = nv - 4 * d;
+        const uint32_t keep = v >= 4 ? 0xffffffffu : v <= 0 ? 0u : ((1u << (8 * v)) - 1u);
+        upper |= zero_bytes(sw[d] ^ 0x4e4e4e4eu) & keep;                        // 0x80 where a base of the read is 'N'
+        tw[d] = LOWER_BASE ? sw[d] ^ (zero_bytes(sw[d] ^ 0x6e6e6e6eu) >> 7) : sw[d];
+    }
+    int bad = 0;
+    const uint4 o = decode16(make_uint4(tw[0], tw[1], tw[2], tw[3]), ql, 0, nv, offset, bad);
+    if (upper) st |= MPB_PT_UPPER;
+    if (bad) st |= offset < 1 ? MPB_PT_ABOVE : MPB_PT_BELOW;
+    return o;
+}
+
+// bytes [sh, sh + 16) of the 32 bytes a | b, sh = 0..15
+__device__ __forceinline__ uint4 funnel16(const uint4 a, const uint4 b, uint32_t sh)
+{
+    uint32_t w0 = a.x, w1 = a.y, w2 = a.z, w3 = a.w, w4 = b.x, w5 = b.y;
+    if (sh & 8u) { w0 = a.z; w1 = a.w; w2 = b.x; w3 = b.y; w4 = b.z; w5 = b.w; }
+    if (sh & 4u) { w0 = w1; w1 = w2; w2 = w3; w3 = w4; w4 = w5; }
+    const uint32_t bs = sh & 3u;
+    return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, bs), __builtin_amdgcn_alignbyte(w2, w1, bs),
+                      __builtin_amdgcn_alignbyte(w3, w2, bs), __builtin_amdgcn_alignbyte(w4, w3, bs));
+}
+
+// the 16 bytes at text[s ..), of which the first m (1..16) are bases of a validated record: s + m <= text_bytes, so the aligned
+// word s lies in ends below round_up(text_bytes, 16), and so does the next one whenever one of the m bytes lies in it
+__device__ __forceinline__ uint4 fetch16(const uint8_t *__restrict__ text, int64_t s, int m)
+{
+    const int64_t base = s & ~(int64_t)15;
+    const uint32_t sh = (uint32_t)(s & 15);
+    const uint4 a = gload16(text + base);
+    uint4 b = make_uint4(0u, 0u, 0u, 0u);
+    if (sh + (uint32_t)m > 16u) b = gload16(text + base + 16);
+    return funnel16(a, b, sh);
+}
+// [k_pack_text chunk code: end]
+
+template <bool LOWER_BASE>
+__global__ __launch_bounds__(256) void k_pack_text(const uint8_t *__restrict__ text, int64_t text_bytes,
+                                                   const mpb_text_row *__restrict__ rows, int64_t n, int64_t k0,
+                                                   int32_t offset, int64_t stride, uint8_t *__restrict__ out, int32_t *__restrict__ len_out,
+                                                   uint8_t *__restrict__ flags_out, long long *__restrict__ status)
+{
+    const int sub = threadIdx.x & 7;
+    const int cpr = (int)(stride >> 4);
+    for (int64_t k = (int64_t)blockIdx.x * 32 + (threadIdx.x >> 3); k < n; k += (int64_t)gridDim.x * 32) {
+        const mpb_text_row r = rows[k];
+        // the descriptors were validated on the host (mpb_text_rows); the same conditions once more, so that nothing is read or
+        // written out of bounds whatever the array holds: such a row is zero and its length -1 (a bad length downstream)
+        const bool ok = r.seq_off >= 0 && r.qual_off >= 0 && r.len >= 0 && (int64_t)r.len <= stride && (int64_t)r.len <= text_bytes &&
+                        r.seq_off <= text_bytes - r.len && r.qual_off <= text_bytes - r.len;
+        const int li = ok ? r.len : 0;
+        uint8_t *const row = out + k * stride;
+        uint32_t st = 0;
+        for (int c = sub; c < cpr; c += 8) {
+            const int nv = li - 16 * c;                                         // bases from this chunk on
+            uint4 o = make_uint4(0u, 0u, 0u, 0u);
+            if (nv > 0) {
+                const int m = min(nv, 16);
+                const uint4 ql = fetch16(text, r.qual_off + 16 * c, m);
+                const uint4 sq = fetch16(text, r.seq_off + 16 * c, m);
+                o = pack16<LOWER_BASE>(sq, ql, nv, offset, st);
+            }
+            *reinterpret_cast<uint4 *>(row + 16 * c) = o;
+        }
+        // the eight lanes of the row (all of them are in this trip: k is theirs in common)
+        st |= (uint32_t)__shfl_xor((int)st, 1);
+        st |= (uint32_t)__shfl_xor((int)st, 2);
+        st |= (uint32_t)__shfl_xor((int)st, 4);
+        if (sub == 0) {
+            len_out[k] = ok ? r.len : -1;
+            if (flags_out) flags_out[k] = (uint8_t)((st & MPB_PT_UPPER) ? 1 : 0);
+            // the smallest row position with a quality out of range, per kind, counted from k0 (the position of rows[0] in the
+            // caller's batch: a batch packed in pieces shares one status).  Rare; the plain look first keeps a batch that is wrong
+            // throughout -- the wrong offset -- from sending every row through one atomic.
+            const long long pos = (long long)(k0 + k);
+            if ((st & MPB_PT_BELOW) && pos < gload(status + 0))
+                __hip_atomic_fetch_min(status + 0, pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((st & MPB_PT_ABOVE) && pos < gload(status + 1))
+                __hip_atomic_fetch_min(status + 1, pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // synthetic fill: one thread per 16-byte chunk of the matrix
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_synth(uint8_t *__restrict__ q, int64_t n, int64_t stride,
@@ -2678,6 +2789,21 @@ void mpb_launch_decode(const uint8_t *seq, const uint8_t *qual, int64_t n, int64
     const int64_t chunks = n * (stride / 16);
     hipLaunchKernelGGL(k_decode_ascii, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, seq, qual, n,
                        stride, len, fixed_len, offset, out, err);
+}
+
+void mpb_launch_pack_text(const uint8_t *text, int64_t text_bytes, const mpb_text_row *rows, int64_t n, int64_t k0, int32_t offset,
+                          bool lower_n_is_base, int64_t stride, uint8_t *out, int32_t *len_out, uint8_t *flags_out,
+                          int64_t *status, hipStream_t s)
+{
+    int64_t blocks = (n + 31) / 32;                      // eight lanes per row
+    if (blocks > (1 << 20)) blocks = 1 << 20;            // the row loop is grid-strided
+    if (blocks < 1) blocks = 1;
+    if (lower_n_is_base)
+        hipLaunchKernelGGL((k_pack_text<true>), dim3((unsigned)blocks), dim3(256), 0, s, text, text_bytes, rows, n, k0, offset, stride, out,
+                           len_out, flags_out, (long long *)status);
+    else
+        hipLaunchKernelGGL((k_pack_text<false>), dim3((unsigned)blocks), dim3(256), 0, s, text, text_bytes, rows, n, k0, offset, stride, out,
+                           len_out, flags_out, (long long *)status);
 }
 
 void mpb_launch_count(const uint8_t *pass, int64_t n, const MpbWorkspace &ws, hipStream_t s)

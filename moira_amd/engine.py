@@ -58,6 +58,59 @@ class FilterResult:
         self.n_pass, self.n_fail, self.n_overflow = n_pass, len(ee) - n_pass, n_overflow
 
 
+class TextFilterResult(FilterResult):
+    """FilterResult of Engine.filter_text, with what the device pack produced next to it: lens (bases packed per read) and
+    has_n (an upper-case 'N' among them)."""
+
+    def __init__(self, ee, ns, passed, lens, has_n, n_pass, n_overflow):
+        FilterResult.__init__(self, ee, ns, passed, n_pass, n_overflow)
+        self.lens, self.has_n = lens, has_n
+
+
+TEXT_ROW_DTYPE = np.dtype([("seq_off", "<i8"), ("qual_off", "<i8"), ("len", "<i4"), ("pad", "<i4")])     # mpb_text_row
+
+
+def _text_ptr(buf):
+    """A chunk of text (bytes, bytearray, memoryview or a uint8 array) -> (object to keep alive, address, length)."""
+    if isinstance(buf, np.ndarray):
+        a = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    else:
+        a = np.frombuffer(buf, np.uint8)
+    return a, a.ctypes.data, int(a.size)
+
+
+def _index_args(idx, sel):
+    idx = np.ascontiguousarray(idx, np.int64)
+    if idx.ndim != 2 or idx.shape[1] != 6:
+        raise ValueError("idx must be an (n_records x 6) int64 record index")
+    if sel is not None:
+        sel = np.ascontiguousarray(sel, np.int64).reshape(-1)
+    return idx, sel, (len(sel) if sel is not None else len(idx))
+
+
+def _check_text(rc, bad):
+    try:
+        L.check(rc)
+    except ValueError as e:
+        e.bad_record = bad.value
+        raise
+
+
+def text_rows(idx, sel=None, text_bytes=0, max_len=0, stride=0):
+    """The validated row descriptors (mpb_text_rows; host only) of the records sel (None: all) of the record index idx over a
+    text of text_bytes bytes -> (rows, longest): rows a TEXT_ROW_DTYPE array (None when stride == 0: validation and the
+    longest packed length only).  ValueError (MPB_E_INVALID) for an offset or length the text cannot hold, a sel entry outside
+    the index, a read above 65535 bases or above the stride; .bad_record = its position in sel order."""
+    idx, sel, n = _index_args(idx, sel)
+    rows = np.zeros(n, TEXT_ROW_DTYPE) if stride else None
+    longest, bad = C.c_int64(0), C.c_int64(-1)
+    rc = L.load().mpb_text_rows(idx.ctypes.data if len(idx) else None, len(idx), sel.ctypes.data if sel is not None else None, n,
+                                int(text_bytes), int(max_len), int(stride), rows.ctypes.data if rows is not None else None,
+                                C.byref(longest), C.byref(bad))
+    _check_text(rc, bad)
+    return rows, longest.value
+
+
 def check_host_batch(q, lens, fixed_len, out, limit):
     """Argument checks shared by every host-batch entry (one GPU or several): -> (q, n, stride, lens, (ee, ns, ps)).
     `limit`: longest read the method takes (None: as long as the row)."""
@@ -210,6 +263,47 @@ class Engine:
                                               int(fastq_offset), int(max_len), stride, q.ctypes.data,
                                               lens.ctypes.data))
         return q, lens
+
+    # ---- FASTQ text as it lies in the file (mpb_text_rows, k_pack_text) ---------------------------
+    @staticmethod
+    def text_rows(idx, sel=None, text_bytes=0, max_len=0, stride=0):
+        """The validated row descriptors of k_pack_text: see the module's text_rows (host only, needs no device)."""
+        return text_rows(idx, sel, text_bytes, max_len, stride)
+
+    def pack_text_device(self, d_text, text_bytes, d_rows, n, stride, d_q_out, d_len_out, d_flags_out=None, d_status=None,
+                         fastq_offset=33, lower_n_is_base=False):
+        """k_pack_text on buffers resident in HBM (DeviceBuffer or raw pointers): the text (capacity round_up(text_bytes, 16)) and
+        the uploaded descriptors of text_rows() -> the packed matrix, the lengths, the has-N flags; d_status is a device
+        int64[2] the caller set to INT64_MAX.  Asynchronous on the engine's stream."""
+        ptr = lambda b: (b.ptr if isinstance(b, DeviceBuffer) else b)
+        L.check(self.lib.mpb_pack_text_device(self.ctx, ptr(d_text), int(text_bytes), ptr(d_rows), int(n), int(fastq_offset),
+                                              1 if lower_n_is_base else 0, int(stride), ptr(d_q_out), ptr(d_len_out),
+                                              ptr(d_flags_out) if d_flags_out is not None else None, ptr(d_status)))
+
+    def filter_text(self, buf, idx, sel=None, fastq_offset=33, max_len=0, lower_n_is_base=False, poisson=False, out=None, **kw):
+        """A chunk of FASTQ text in host memory + its record index (fastio.index, or the contigs' buffer and index) ->
+        TextFilterResult: the text is uploaded once, packed on the device and filtered there (mpb_filter_text_host); results
+        are those of fastio.pack + filter() / filter_poisson() on the same records, bit for bit.  `kw` as filter()'s.
+        ValueError with the library's message for a quality character out of range or an index the text cannot hold
+        (.bad_record = the record's position in sel order); `out` = (ee, ns, pass, lens, flags) arrays to fill."""
+        params = kw.pop("params", None) or self.params(**kw)
+        idx, sel, n = _index_args(idx, sel)
+        keep, addr, nbytes = _text_ptr(buf)
+        if out is None:
+            out = np.empty(n, np.float64), np.empty(n, np.int32), np.empty(n, np.uint8), np.empty(n, np.int32), np.empty(n, np.uint8)
+        ee, ns, ps, lens, flags = out
+        if (ee.dtype, ns.dtype, ps.dtype, lens.dtype, flags.dtype) != (np.float64, np.int32, np.uint8, np.int32, np.uint8) or \
+                not all(a.flags.c_contiguous and len(a) >= n for a in out):
+            raise ValueError("out must be contiguous (float64, int32, uint8, int32, uint8) arrays of at least n entries")
+        counts, bad = L.FilterCounts(), C.c_int64(-1)
+        rc = self.lib.mpb_filter_text_host(self.ctx, addr, nbytes, idx.ctypes.data, len(idx),
+                                           sel.ctypes.data if sel is not None else None, n, int(fastq_offset), int(max_len),
+                                           1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0,
+                                           ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data, flags.ctypes.data,
+                                           C.byref(counts), C.byref(bad))
+        del keep
+        _check_text(rc, bad)
+        return TextFilterResult(ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), counts.n_pass, counts.n_overflow)
 
     def decode_ascii_device(self, d_seq, d_qual, n, stride, d_out, d_len=None, fixed_len=0, fastq_offset=33,
                             d_err=None):

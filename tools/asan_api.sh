@@ -1,6 +1,6 @@
 #!/bin/bash
 # CPU-only AddressSanitizer + UBSan run of the HOST-side code of the C ABI layer: packers, the Poisson tail (threaded),
-# argument validation.  The kernels are not involved (GPU sanitizers are not available on this pool): all of it lives in
+# the row descriptors of the device text pack (mpb_text_rows), argument validation.  The kernels are not involved (GPU sanitizers are not available on this pool): all of it lives in
 # the HIP-free unit (mpb_hostonly.cpp), which is all this builds -- no HIP header, no HIP library, no stub.
 set -e
 cd "$(dirname "$0")/.."
@@ -8,6 +8,7 @@ D=${TMPDIR:-/tmp}/mpb_asan; mkdir -p $D
 cat > $D/main.cpp <<'CPP'
 #include "moira_pb.h"
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -79,6 +80,52 @@ int main()
         int64_t off4[2] = {0, 2};
         bad += mpb_pack_batch_coded(nullptr, negq, off4, 1, 0, 16, qo.data(), ln, codes) != MPB_E_RANGE;
         bad += mpb_pack_batch_coded(nullptr, ql, off2, 3, 0, 8, qo.data(), ln, codes) != MPB_E_INVALID;      // stride not a multiple of 16
+    }
+    // the validated row descriptors of k_pack_text: a good index (sel given and NULL, truncation, sizing call), every refusal, n = 0
+    {
+        // four records over a text of 100 bytes; the last one's quality line ends exactly at the last byte
+        int64_t ix[4][MPB_IDX_COLS] = {{0, 2, 3, 10, 16, 10}, {30, 2, 33, 7, 43, 7}, {52, 2, 55, 0, 58, 0}, {60, 2, 63, 17, 83, 17}};
+        const int64_t *idx = &ix[0][0];
+        mpb_text_row rows[5];
+        int64_t longest = -1, badrec = 7;
+        bad += mpb_text_rows(idx, 4, nullptr, 4, 100, 0, 0, nullptr, &longest, &badrec) != MPB_OK;
+        bad += !(longest == 17 && badrec == -1);
+        bad += mpb_text_rows(idx, 4, nullptr, 4, 100, 0, 32, rows, &longest, &badrec) != MPB_OK;
+        bad += !(rows[0].seq_off == 3 && rows[0].qual_off == 16 && rows[0].len == 10 && rows[3].qual_off == 83 && rows[3].len == 17 && rows[2].len == 0);
+        int64_t sel[5] = {3, 0, 0, 2, 1};
+        bad += mpb_text_rows(idx, 4, sel, 5, 100, 8, 16, rows, &longest, &badrec) != MPB_OK;
+        bad += !(longest == 8 && rows[0].seq_off == 63 && rows[0].len == 8 && rows[1].len == 8 && rows[2].qual_off == 16 && rows[4].len == 7);
+        bad += mpb_text_rows(idx, 4, nullptr, 0, 100, 0, 16, rows, &longest, &badrec) != MPB_OK;
+        bad += mpb_text_rows(nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr) != MPB_OK;
+        // one byte past the text
+        bad += !(mpb_text_rows(idx, 4, nullptr, 4, 99, 0, 32, rows, &longest, &badrec) == MPB_E_INVALID && badrec == 3);
+        ix[1][MPB_IDX_SEQ_OFF] = 94;
+        bad += !(mpb_text_rows(idx, 4, nullptr, 4, 100, 0, 32, rows, &longest, &badrec) == MPB_E_INVALID && badrec == 1);
+        bad += mpb_text_rows(idx, 4, nullptr, 4, 100, 6, 32, rows, &longest, &badrec) != MPB_OK;       // ... which truncation brings back inside
+        ix[1][MPB_IDX_SEQ_OFF] = -1;
+        bad += !(mpb_text_rows(idx, 4, sel, 5, 100, 0, 32, rows, &longest, &badrec) == MPB_E_INVALID && badrec == 4);
+        ix[1][MPB_IDX_SEQ_OFF] = 33; ix[0][MPB_IDX_QUAL_OFF] = -5;
+        bad += !(mpb_text_rows(idx, 4, sel, 5, 100, 0, 32, rows, &longest, &badrec) == MPB_E_INVALID && badrec == 1);
+        ix[0][MPB_IDX_QUAL_OFF] = 16;
+        // sel outside the index, on either side; more rows than records without sel
+        sel[2] = 4;
+        bad += !(mpb_text_rows(idx, 4, sel, 5, 100, 0, 32, rows, &longest, &badrec) == MPB_E_INVALID && badrec == 2);
+        sel[2] = -1;
+        bad += !(mpb_text_rows(idx, 4, sel, 5, 100, 0, 32, rows, &longest, &badrec) == MPB_E_INVALID && badrec == 2);
+        sel[2] = 0;
+        bad += mpb_text_rows(idx, 4, nullptr, 5, 100, 0, 32, rows, &longest, &badrec) != MPB_E_INVALID;
+        // a length above the row, above 65535 (a text that could hold it), and a negative one
+        bad += !(mpb_text_rows(idx, 4, nullptr, 4, 100, 0, 16, rows, &longest, &badrec) == MPB_E_INVALID && badrec == 3);
+        ix[2][MPB_IDX_QUAL_LEN] = 65536;
+        bad += !(mpb_text_rows(idx, 4, nullptr, 4, 1 << 20, 0, 0, nullptr, &longest, &badrec) == MPB_E_INVALID && badrec == 2);
+        ix[2][MPB_IDX_QUAL_LEN] = 65535;
+        bad += !(mpb_text_rows(idx, 4, nullptr, 4, 1 << 20, 0, 0, nullptr, &longest, &badrec) == MPB_OK && longest == 65535);
+        ix[2][MPB_IDX_QUAL_LEN] = -1;
+        bad += !(mpb_text_rows(idx, 4, nullptr, 4, 100, 0, 0, nullptr, &longest, &badrec) == MPB_E_INVALID && badrec == 2);
+        // offsets near INT64_MAX must not wrap
+        ix[2][MPB_IDX_QUAL_LEN] = 5; ix[2][MPB_IDX_QUAL_OFF] = INT64_MAX - 2;
+        bad += !(mpb_text_rows(idx, 4, nullptr, 4, 100, 0, 0, nullptr, &longest, &badrec) == MPB_E_INVALID && badrec == 2);
+        bad += mpb_text_rows(idx, 4, nullptr, -1, 100, 0, 0, nullptr, &longest, &badrec) != MPB_E_INVALID;
     }
     std::printf("asan_api: %d failed checks, version %s\n", bad, mpb_version());
     return bad != 0;
