@@ -432,6 +432,63 @@ int mpb_filter_text_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, con
                          mpb_filter_counts *counts, int64_t *bad_record);
 
 /*
+ * Paired-read contigs on the device (opt-in; the default builder stays mct_contigs_from_fastq of libmoira_contig.so): the
+ * Needleman-Wunsch fill, the traceback and the consensus of a chunk of read pairs that are still FASTQ text, one wave per pair
+ * (k_contig, csrc/mpb_contig_kernels.hip).  The contract is BYTE IDENTITY with mct_contigs_from_fastq on every pair the device
+ * takes; a pair it does not take is HANDED BACK (done[i] = 0, nothing of slot i is defined) and the caller builds it with the
+ * host aligner, so every data error is raised by the code that raises it today.  The device takes a pair when
+ *   1 <= l1, l2 <= MPB_CONTIG_MAX_LEN;  (l1 + l2 + 2) * max(|match|, |mismatch|, |gap|) < 30000 (the CPU's 16-bit predicate);
+ *   every base of the reverse read has a complement;  every quality byte - fastq_offset >= 0;  every contig quality q satisfies
+ *   0 <= q + fastq_offset <= 255;  neither read holds a '-' (make_contig reads a '-' of the alignment as a gap);
+ *   fastq_offset lies in 0..255 (otherwise the whole chunk is handed back).
+ * One measured run (profiles/device_contig_rate.json): 65,536 pairs of 2 x 251 bases, 36.3 ms on 16 host threads, 21.0 ms through
+ * this call, transfers included, none handed back.  No rate is promised; the path stays opt-in.
+ */
+#define MPB_CONTIG_MAX_LEN 384
+typedef struct mpb_pair_row {            /* 56 bytes: offsets into the forward / reverse text */
+    int64_t fseq_off, fqual_off, fhdr_off, rseq_off, rqual_off;
+    int32_t l1, l2, hdr_len, pad;
+} mpb_pair_row;
+typedef struct mpb_contig_params {
+    int32_t match, mismatch, gap, insert, deltaq, consensus /* 0 best, 1 sum, 2 posterior */, qscore_cap, trim_overlap;
+} mpb_contig_params;
+
+/*
+ * Host only: the VALIDATED descriptors of n pairs from the two record indexes (the six columns of include/moira_io.h) -- the
+ * only place the offsets are trusted from.  MPB_E_INVALID with *bad_record = i (may be NULL) when an offset or a length is
+ * negative or lies past its text, a sequence and its quality line differ in length, a length is above 2^31 - 1, or
+ * hdr_len + 2 (l1 + l2) > rec_cap.  Lengths the device does not take (0, above MPB_CONTIG_MAX_LEN) are NOT errors here.
+ */
+int mpb_pair_rows(const int64_t *fidx, const int64_t *ridx, int64_t n, int64_t ftext_bytes, int64_t rtext_bytes,
+                  int64_t rec_cap, mpb_pair_row *rows_out, int64_t *bad_record);
+
+/*
+ * Host only: the two tables the device consensus reads in `posterior` mode, int32[256][256] each, indexed [forward q][reverse q]:
+ * prob2qual of the reference's expression for two equal bases (match) and for two different ones of unequal quality (mismatch;
+ * the diagonal is unused), with the host's libm -- the expressions contig.cpp evaluates (csrc/contig_posterior.h).  An entry
+ * that is not a finite integer is INT32_MIN (such a column hands its pair back).
+ */
+int mpb_contig_posterior_tables(int32_t *match_out, int32_t *mismatch_out);
+
+/*
+ * The chunk call; synchronous.  In this order: mpb_pair_rows, before anything is uploaded (MPB_E_INVALID, *bad_record);
+ * make_contig's parameter checks (insert > 0, deltaq > 0, qscore_cap >= 0, consensus 0..2: MPB_E_INVALID); both texts are
+ * uploaded once, into allocations rounded up to 16 bytes and zeroed past the text; the pairs are bucketed by the LDS their
+ * matrix needs and one launch is made per size class; the slots and arrays come back.  Slot i of out_buf (rec_cap bytes) and
+ * row i of out_idx are written exactly as mct_contigs_from_fastq writes them: header token, contig, q + fastq_offset bytes.
+ * done[i] = 1: the device built pair i; 0: handed back.  Optional (aln_out may be NULL): aln_out[i][0..1][aln_cap] receive
+ * the two aligned strings (no terminator), aln_len_out[i] their length, score_out[i] the alignment score; a pair whose
+ * alignment is longer than aln_cap is handed back.  n_done / n_handed_back (may be NULL) count.  n == 0 is MPB_OK.
+ * The device blocks belong to the context and grow on demand.
+ */
+int mpb_contigs_text_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_bytes, const int64_t *fidx,
+                          const char *rtext, int64_t rtext_bytes, const int64_t *ridx, int64_t n, int32_t fastq_offset,
+                          const mpb_contig_params *params, int64_t rec_cap,
+                          char *out_buf, int64_t *out_idx, int32_t *overlap, int32_t *gaps, int32_t *mismatches, uint8_t *done,
+                          char *aln_out, int64_t aln_cap, int32_t *aln_len_out, int32_t *score_out,
+                          int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record);
+
+/*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is
  * cut into n_ctx contiguous, balanced shards in read order, one host thread per context runs mpb_filter_host
  * (poisson == 0) or mpb_filter_poisson_host (poisson != 0) on its shard, and every shard's results land in the

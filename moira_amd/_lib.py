@@ -61,6 +61,19 @@ class TextRow(C.Structure):
     _fields_ = [("seq_off", C.c_int64), ("qual_off", C.c_int64), ("len", C.c_int32), ("pad", C.c_int32)]
 
 
+class PairRow(C.Structure):
+    """mpb_pair_row: one validated pair descriptor of k_contig (56 bytes)."""
+    _fields_ = [("fseq_off", C.c_int64), ("fqual_off", C.c_int64), ("fhdr_off", C.c_int64), ("rseq_off", C.c_int64),
+                ("rqual_off", C.c_int64), ("l1", C.c_int32), ("l2", C.c_int32), ("hdr_len", C.c_int32), ("pad", C.c_int32)]
+
+
+class ContigParams(C.Structure):
+    """mpb_contig_params (consensus: 0 best, 1 sum, 2 posterior)."""
+    _fields_ = [(k, C.c_int32) for k in ("match", "mismatch", "gap", "insert", "deltaq", "consensus", "qscore_cap", "trim_overlap")]
+
+
+CONTIG_MAX_LEN = 384           # MPB_CONTIG_MAX_LEN: the longest read of a pair the device contig builder takes
+
 # name -> (restype, argtypes): every symbol include/moira_pb.h declares
 _VP, _I32P, _U8P, _DP = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
 PROTOTYPES = {
@@ -90,6 +103,11 @@ PROTOTYPES = {
     "mpb_filter_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP, C.POINTER(FilterCounts),
                                        C.POINTER(C.c_int64)]),
+    "mpb_pair_rows": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _VP, C.POINTER(C.c_int64)]),
+    "mpb_contig_posterior_tables": (C.c_int, [_VP, _VP]),
+    "mpb_contigs_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.POINTER(ContigParams),
+                                        C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mpb_encode_ascii_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP]),
     "mpb_decode_classify_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
                                              C.POINTER(FilterParams), _VP, _VP, _VP, _VP, _VP]),

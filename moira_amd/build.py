@@ -20,13 +20,17 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmoira_pb.so")
 # the host side of the library: the C ABI layer, unit by unit (mpb_hostonly.cpp includes no HIP header), and the broker
 HOST_SOURCES = [os.path.join(CSRC, name) for name in ("mpb_hostonly.cpp", "mpb_context.cpp", "mpb_resident.cpp", "mpb_hostfed.cpp",
-                                                      "mpb_perread.cpp", "mpb_poisson.cpp", "mpb_text.cpp", "mpb_broker.cpp")]
-SOURCES = [os.path.join(CSRC, "mpb_kernels.hip")] + HOST_SOURCES
+                                                      "mpb_perread.cpp", "mpb_poisson.cpp", "mpb_text.cpp", "mpb_contig.cpp",
+                                                      "mpb_broker.cpp")]
+CONTIG_KERNELS = os.path.join(CSRC, "mpb_contig_kernels.hip")      # k_contig: a kernel unit of its own (mpb_kernels.hip stays as it is)
+SOURCES = [os.path.join(CSRC, "mpb_kernels.hip"), CONTIG_KERNELS] + HOST_SOURCES
 DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_host_internal.h"),
                   os.path.join(CSRC, "mpb_shared.h"), os.path.join(CSRC, "mpb_hostonly.h"), os.path.join(CSRC, "mpb_ctx.h"),
                   os.path.join(CSRC, "mpb_dp_tiles.inc"),
                   os.path.join(CSRC, "mpb_narrow_ring.inc"), os.path.join(CSRC, "mpb_narrow_rs.inc"),
                   os.path.join(CSRC, "mpb_narrow_rg.inc"),
+                  os.path.join(CSRC, "mpb_contig_lane.inc"), os.path.join(CSRC, "mpb_contig_args.h"),
+                  os.path.join(CSRC, "contig_posterior.h"),
                   os.path.join(CSRC, "libmoira_pb.map"),
                   os.path.join(ROOT, "include", "moira_pb.h"),
                   os.path.join(ROOT, "include", "mpb_synth.h")]
@@ -46,7 +50,7 @@ CONTIG_SRC = os.path.join(CSRC, "contig.cpp")
 CXX = os.environ.get("CXX", "g++")
 
 
-CONTIG_DEPS = [CONTIG_SRC, os.path.join(ROOT, "include", "moira_contig.h"),
+CONTIG_DEPS = [CONTIG_SRC, os.path.join(CSRC, "contig_posterior.h"), os.path.join(ROOT, "include", "moira_contig.h"),
                os.path.join(ROOT, "include", "moira_io.h")]
 
 
@@ -147,6 +151,9 @@ def build(force=False, verbose=False, extra=()):
 if __name__ == "__main__":
     if "--host-sources" in sys.argv:     # for scripts that build variants of the library (tools/experiments)
         print(" ".join(os.path.relpath(p, ROOT) for p in HOST_SOURCES))
+        sys.exit(0)
+    if "--units-beside-kernels" in sys.argv:     # every unit besides mpb_kernels.hip, which such a script replaces by its variant
+        print(" ".join(os.path.relpath(p, ROOT) for p in [CONTIG_KERNELS] + HOST_SOURCES))
         sys.exit(0)
     build(force="--force" in sys.argv, verbose=True)
     build_contig(force="--force" in sys.argv, verbose=True)

@@ -231,6 +231,12 @@ def build_parser():
                    help="(not in moira.py) skip the exact error calculation for reads that provably exceed the "
                         "threshold; only with --collapse false and the mothur pipeline, where the expected errors "
                         "of a discarded read are never used. Kept/discarded sets are unchanged.")
+    f.add_argument("--device_contigs", action="store_true",
+                   help="(not in moira.py) paired input on one GPU: build the contigs of each chunk on the device (Needleman-Wunsch "
+                        "fill, traceback and consensus, one call per chunk); pairs the device does not take (reads above 384 bases, "
+                        "qualities outside one byte, ...) are built on the host as always. Output files are identical. Where it "
+                        "does not apply (unpaired input, the line parser, more than one GPU, a CPU backend) it is ignored with a "
+                        "message. No rate is promised.")
     f.add_argument("--device_pack", action="store_true",
                    help="(not in moira.py) FASTQ input on one GPU: upload each chunk of text as it lies in the file and build the "
                         "quality matrix on the device (one call per chunk) instead of packing it on the host, one length bucket "
@@ -950,11 +956,40 @@ def _text_threads(args):
     return max(1, min(int(args.processors or 1), usable_cpus(), 64))
 
 
-def _fast_chunks(args):
-    """(buf, idx, aux) per chunk: reads as they are in the file, or contigs built from the two files."""
+def _device_contigs_eligible(args, backend):
+    """--device_contigs applies to a paired run the byte-level path takes, on a backend with one device (the one --device_pack asks for)."""
+    return bool(args.paired and getattr(backend, "text", None) is not None and hasattr(getattr(backend, "engine", None), "contigs_text"))
+
+
+def _chunk_contigs(args, fbuf, fidx, rbuf, ridx, offset, engine=None):
+    """The contigs of one chunk of pairs -> (cbuf, cidx, aux); engine: on its device, the handed-back pairs on the host."""
+    from . import contig as CT
+    from . import fastio as F
+    try:
+        return CT.contigs_from_fastq(fbuf, fidx, rbuf, ridx, offset, args.match, args.mismatch, args.gap, args.insert, args.deltaq,
+                                     args.consensus_qscore, args.qscore_cap, args.trim_overlap, threads=args.processors, engine=engine)
+    except CT.QualityRange as e:
+        raise F.Unsupported(str(e))
+
+
+class _DeferredContigs:
+    """A chunk of pairs whose contigs are still to be built, by whoever takes it off the queue.  With --device_contigs the
+    producer thread only reads and indexes: calls on one context must not overlap (include/moira_pb.h), and the consumer
+    thread is the one that filters on that context, so it makes the device contig call too."""
+
+    def __init__(self, *a):
+        self.a = a
+
+    def build(self):
+        return _chunk_contigs(*self.a)
+
+
+def _fast_chunks(args, contig_engine=None):
+    """(buf, idx, aux) per chunk: reads as they are in the file, or contigs built from the two files.  With contig_engine
+    (--device_contigs) a paired chunk comes as a _DeferredContigs instead: its consumer builds the contigs, on its own thread."""
     from . import fastio as F
     if not args.forward_fastq:
-        yield from _fast_chunks_fasta_qual(args)
+        yield from _fast_chunks_fasta_qual(args, contig_engine)
         return
     if not args.paired:
         fh = open_input_binary(args.forward_fastq, _text_threads(args))
@@ -966,7 +1001,6 @@ def _fast_chunks(args):
         finally:
             fh.close()
         return
-    from . import contig as CT
     half = max(1, _text_threads(args) // 2)
     ffh, rfh = open_input_binary(args.forward_fastq, half), open_input_binary(args.reverse_fastq, half)
     try:
@@ -975,15 +1009,10 @@ def _fast_chunks(args):
             # forward_header != reverse_header (moira.py:1197-1198); ':' -> '_' on both sides cannot change equality
             bad = F.first_header_mismatch(fbuf, fidx, rbuf, ridx)
             n = len(fidx) if bad < 0 else bad
-            if n:
-                try:
-                    cbuf, cidx, aux = CT.contigs_from_fastq(
-                        fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset, args.match, args.mismatch, args.gap,
-                        args.insert, args.deltaq, args.consensus_qscore, args.qscore_cap, args.trim_overlap,
-                        threads=args.processors)
-                except CT.QualityRange as e:
-                    raise F.Unsupported(str(e))
-                yield cbuf, cidx, aux
+            if n and contig_engine is not None:
+                yield _DeferredContigs(args, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset, contig_engine)
+            elif n:
+                yield _chunk_contigs(args, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset)
             if bad >= 0:
                 raise NameMismatchError(F.header_of(fbuf, fidx[bad]), None, F.header_of(rbuf, ridx[bad]), None)
     except F.PairedRecordError as e:
@@ -1078,7 +1107,7 @@ class _InOrder:
             raise self.err
 
 
-def _fast_chunks_fasta_qual(args):
+def _fast_chunks_fasta_qual(args, contig_engine=None):
     """fasta + qual input: records rebuilt as header | sequence | quality bytes (offset 0) by
     mio_fasta_qual_index, so that the rest of the path is the FASTQ one."""
     from . import fastio as F
@@ -1089,7 +1118,6 @@ def _fast_chunks_fasta_qual(args):
             for buf, idx in F.FastaQualChunks(files[0], files[1], CHUNK_READS):
                 yield buf, idx, None
             return
-        from . import contig as CT
         files += [open_input_binary(args.reverse_fasta, half), open_input_binary(args.reverse_qual, half)]
         fwd = iter(F.FastaQualChunks(files[0], files[1], PAIR_CHUNK_READS))
         rev = iter(F.FastaQualChunks(files[2], files[3], PAIR_CHUNK_READS))
@@ -1100,19 +1128,16 @@ def _fast_chunks_fasta_qual(args):
             # a file that ends early, or names that differ, are NameMismatchErrors of the line parser
             if a is None or b is None or len(a[1]) != len(b[1]) or F.first_header_mismatch(a[0], a[1], b[0], b[1]) >= 0:
                 raise F.Unsupported("forward and reverse records do not pair up")
-            try:
-                cbuf, cidx, aux = CT.contigs_from_fastq(
-                    a[0], a[1], b[0], b[1], 0, args.match, args.mismatch, args.gap, args.insert, args.deltaq,
-                    args.consensus_qscore, args.qscore_cap, args.trim_overlap, threads=args.processors)
-            except CT.QualityRange as e:
-                raise F.Unsupported(str(e))
-            yield cbuf, cidx, aux
+            if contig_engine is not None:
+                yield _DeferredContigs(args, a[0], a[1], b[0], b[1], 0, contig_engine)
+            else:
+                yield _chunk_contigs(args, a[0], a[1], b[0], b[1], 0)
     finally:
         for f in files:
             f.close()
 
 
-def _run_fast_fastq(args, backend, o, say, t0, device_pack=False):
+def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs=False):
     """Chunks of the input as (buffer, record index); contig construction, packing, collapse and record
     formatting in C (moira_amd/fastio.py, moira_amd/contig.py).  Decisions are write_results'
     (ref: moira/moira.py:842-970), vectorised.
@@ -1176,7 +1201,9 @@ def _run_fast_fastq(args, backend, o, say, t0, device_pack=False):
         return lanes[k]
     ok = False
     try:
-        for buf, idx, aux in _prefetched(_fast_chunks(args)):
+        for chunk in _prefetched(_fast_chunks(args, backend.engine if device_contigs else None)):
+            # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context)
+            buf, idx, aux = chunk.build() if isinstance(chunk, _DeferredContigs) else chunk
             n = len(idx)
             lens = np.minimum(idx[:, F.SEQ_LEN], T) if T else idx[:, F.SEQ_LEN].copy()
             if not only and method == "poisson_binomial" and n and int(lens.max()) > MAX_PB_LEN:
@@ -1348,6 +1375,12 @@ def main(args, backend=None, out=None, _no_fastio=False):
         if not args.nowarnings:
             say("--device_pack does not apply to this run (it takes FASTQ input through the byte-level parser on one GPU): "
                 "host packing is used.")
+    device_contigs = bool(getattr(args, "device_contigs", False))
+    if device_contigs and not (fast and _device_contigs_eligible(args, backend)):
+        device_contigs = False
+        if not args.nowarnings:
+            say("--device_contigs does not apply to this run (it takes paired input through the byte-level parser on one GPU): "
+                "the host aligner is used.")
     try:
         o = _open_outputs(args, output_name, binary=fast)
     except IOError as e:
@@ -1389,7 +1422,8 @@ def main(args, backend=None, out=None, _no_fastio=False):
         if fast:
             from . import fastio
             try:
-                processed, disc_err, disc_len, disc_ov = _run_fast_fastq(args, backend, o, say, t0, device_pack=device_pack)
+                processed, disc_err, disc_len, disc_ov = _run_fast_fastq(args, backend, o, say, t0, device_pack=device_pack,
+                                                                         device_contigs=device_contigs)
             except fastio.Unsupported:
                 # content the byte-level parser does not reproduce: start over with the line parser
                 _close(o)

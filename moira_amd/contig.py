@@ -152,15 +152,48 @@ def usable_cpus():
     return n
 
 
+def _contigs_device_then_host(engine, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
+                              consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap):
+    """The device builds what it takes; the pairs it hands back (done == 0) go through mct_contigs_from_fastq -- the index
+    rows gathered, the same slot size -- and their slots, index rows and aux rows are scattered into place."""
+    res = engine.contigs_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
+                              CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, rec_cap=rec_cap)
+    cbuf, cidx, aux = res.cbuf, res.cidx, res.aux
+    back = np.nonzero(~res.done)[0]
+    if len(back):
+        m = len(back)
+        sf, sr = np.ascontiguousarray(fidx[back]), np.ascontiguousarray(ridx[back])
+        hbuf, hidx = np.empty(m * rec_cap, np.uint8), np.empty((m, 6), np.int64)
+        haux = np.empty((3, m), np.int32)
+        ptr = lambda b: b.ctypes.data if isinstance(b, np.ndarray) else b
+        rc = L.mct_contigs_from_fastq(m, ptr(fbuf), sf.ctypes.data, ptr(rbuf), sr.ctypes.data, int(fastq_offset), match, mismatch,
+                                      gap, insert, deltaq, CONSENSUS[consensus_qscore], qscore_cap, 1 if trim_overlap else 0,
+                                      min(threads, m), rec_cap, hbuf.ctypes.data, hidx.ctypes.data, haux[0].ctypes.data,
+                                      haux[1].ctypes.data, haux[2].ctypes.data)
+        if rc:
+            # the message names the pair by its position in the host call: put the chunk's position back
+            import re
+            msg = re.sub(r"\b(pair|contig) (\d+)\b", lambda g: "%s %d" % (g.group(1), back[int(g.group(2))]), L.mct_last_error().decode())
+            raise (QualityRange if rc == -7 else ValueError)(msg)
+        cbuf.reshape(len(fidx), rec_cap)[back] = hbuf.reshape(m, rec_cap)
+        shift = (back - np.arange(m)) * rec_cap                       # slot k of the host call is slot back[k] of the chunk
+        hidx[:, 0::2] += shift[:, None]
+        cidx[back] = hidx
+        aux[back] = haux.T
+    return cbuf, cidx, aux
+
+
 class QualityRange(Exception):
     """A quality that the byte-level contig path cannot carry (negative, or q + offset > 255)."""
 
 
 def contigs_from_fastq(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatch=-1, gap=-2, insert=20, deltaq=6,
-                       consensus_qscore="best", qscore_cap=40, trim_overlap=False, threads=None):
+                       consensus_qscore="best", qscore_cap=40, trim_overlap=False, threads=None, engine=None):
     """Contigs of a chunk of paired records that are still FASTQ text (buffers + record indices of
     moira_amd.fastio).  Returns (cbuf uint8[n * rec_cap], cidx int64[n, 6], aux int32[n, 3]): contigs as a
-    buffer + record index again (qualities as bytes q + offset), aux = overlap length, gaps, mismatches."""
+    buffer + record index again (qualities as bytes q + offset), aux = overlap length, gaps, mismatches.
+    engine (a moira_amd.engine.Engine; opt-in): the device builds the pairs it takes (Engine.contigs_text) and this
+    function's host path builds the ones it hands back, so results and errors are the host's either way."""
     L = load()
     if consensus_qscore not in CONSENSUS:
         raise ValueError('consensus_qscore must be "best", "sum" or "posterior".')
@@ -168,6 +201,9 @@ def contigs_from_fastq(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatc
     n = len(fidx)
     threads = threads or usable_cpus()
     rec_cap = int((fidx[:, 1] + 2 * (fidx[:, 3] + ridx[:, 3])).max()) + 8 if n else 8     # header + 2 x (l1 + l2)
+    if engine is not None and n:
+        return _contigs_device_then_host(engine, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
+                                         consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap)
     cbuf = np.empty(n * rec_cap, np.uint8)
     cidx = np.empty((n, 6), np.int64)
     aux = np.empty((3, n), np.int32)

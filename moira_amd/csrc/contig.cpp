@@ -8,6 +8,7 @@
 
 #include "../../include/moira_contig.h"
 #include "../../include/moira_io.h"      // MIO_* record-index columns
+#include "contig_posterior.h"            // qual2prob, prob2qual and the two posterior expressions (shared with libmoira_pb.so)
 
 #include <algorithm>
 #include <memory>
@@ -424,9 +425,6 @@ int nw_align_impl(const char *s1, int n1, const char *s2, int n2, int match, int
     return nw_align_scalar(s1, n1, s2, n2, match, mismatch, gap, aln1, aln2, aln_len, score_out, w.scalar);
 }
 
-inline double qual2prob(int q) { return pow(10, q / (-10.0)); }                       // moira.py:1392-1393
-inline int prob2qual(double p) { return (int)floor(-10 * log10(p)); }                 // moira.py:1395-1396
-
 // ref: moira/moira.py:1376-1558
 int make_contig_impl(const char *fa, const int32_t *fq, const char *ra, const int32_t *rq, int n,
                      int insert, int deltaq, int consensus, int qcap, int trim,
@@ -468,10 +466,8 @@ int make_contig_impl(const char *fa, const int32_t *fq, const char *ra, const in
         } else if (fa[k] == ra[k]) {                                               // :1520-1531
             int q;
             if (consensus == MCT_CONSENSUS_SUM) q = fqa[k] + rqa[k];
-            else if (consensus == MCT_CONSENSUS_POSTERIOR) {
-                const double p1 = qual2prob(fqa[k]), p2 = qual2prob(rqa[k]);
-                q = prob2qual((p1 * p2 / 3) / (1 - p1 - p2 + (4 * p1 * p2 / 3)));
-            } else q = fqa[k] >= rqa[k] ? fqa[k] : rqa[k];
+            else if (consensus == MCT_CONSENSUS_POSTERIOR) q = prob2qual(posterior_match_p(fqa[k], rqa[k]));
+            else q = fqa[k] >= rqa[k] ? fqa[k] : rqa[k];
             push(fa[k], q);
         } else {                                                                   // :1533-1556
             mism++;
@@ -483,10 +479,7 @@ int make_contig_impl(const char *fa, const int32_t *fq, const char *ra, const in
             } else if (fqa[k] == rqa[k]) {
                 push('N', 2);
             } else {
-                double p1, p2; char b;
-                if (fqa[k] > rqa[k]) { p1 = qual2prob(fqa[k]); p2 = qual2prob(rqa[k]); b = fa[k]; }
-                else { p2 = qual2prob(fqa[k]); p1 = qual2prob(rqa[k]); b = ra[k]; }
-                push(b, prob2qual(p1 * (1 - p2 / 3) / (p1 + p2 - (4 * p1 * p2 / 3))));
+                push(fqa[k] > rqa[k] ? fa[k] : ra[k], prob2qual(posterior_mismatch_p(fqa[k], rqa[k])));
             }
         }
     }

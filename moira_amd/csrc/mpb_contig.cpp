@@ -1,0 +1,160 @@
+// mpb_contig.cpp -- paired-read contigs on the device, behind the C ABI of libmoira_pb.so (include/moira_pb.h): the host entry that
+// validates the pair descriptors (mpb_pair_rows, mpb_hostonly.cpp), uploads both texts once, buckets the pairs by the LDS their
+// pointer matrix needs, launches k_contig (mpb_contig_kernels.hip) once per size class and brings the slots and arrays back.
+// A pair the device does not take is handed back (done = 0); the caller builds it with libmoira_contig.so.
+// (Every mpb_* function defined here has C linkage: include/moira_pb.h declares it inside extern "C".)
+
+#include "mpb_ctx.h"
+
+#define CD_FN static inline
+static inline int cd_gload8(const uint8_t *p) { return *p; }
+#include "mpb_contig_args.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace {
+
+// LDS per wave of a launch: a 2 x 150 pair needs 11 KB, 2 x 250 21 KB, 2 x 300 42 KB, 2 x 384 57 KB (cd_lds_bytes).  A static
+// worst case would leave two waves per CU.
+const int32_t k_lds_class[] = {4096, 8192, 12288, 16384, 20480, 24576, 32768, 40960, 49152, MPB_CONTIG_LDS_MAX};
+const int k_n_class = (int)(sizeof(k_lds_class) / sizeof(k_lds_class[0]));
+
+struct ContigStage {
+    uint8_t *ftext, *rtext; mpb_pair_row *rows; int32_t *list;
+    uint8_t *out_buf; int64_t *out_idx; int32_t *overlap, *gaps, *mism; uint8_t *done;
+    uint8_t *aln; int32_t *aln_len, *score;
+    void layout(Carver &k, int64_t fbytes, int64_t rbytes, int64_t n, int64_t rec_cap, int64_t aln_cap)
+    {
+        k.take(ftext, align_up(fbytes > 0 ? fbytes : 1, 16));
+        k.take(rtext, align_up(rbytes > 0 ? rbytes : 1, 16));
+        k.take(rows, n); k.take(list, n);
+        k.take(out_buf, n * rec_cap); k.take(out_idx, n * 6);
+        k.take(overlap, n); k.take(gaps, n); k.take(mism, n); k.take(done, n);
+        k.take(aln, aln_cap > 0 ? 2 * n * aln_cap : 1); k.take(aln_len, aln_cap > 0 ? n : 1); k.take(score, aln_cap > 0 ? n : 1);
+    }
+};
+
+int ensure_tables(mpb_ctx *c)
+{
+    if (c->contig_tabs_ready) return MPB_OK;
+    std::vector<int32_t> t;
+    try { t.resize((size_t)2 * 65536); } catch (const std::bad_alloc &) { return fail(MPB_E_NOMEM, "out of host memory for the posterior tables"); }
+    int rc = mpb_contig_posterior_tables(t.data(), t.data() + 65536);
+    if (rc) return rc;
+    if ((rc = c->contig_tabs.grow(c, (int64_t)t.size() * 4))) return rc;
+    if ((rc = copy_sync(c, c->contig_tabs.p, t.data(), t.size() * 4, hipMemcpyHostToDevice))) return rc;
+    c->contig_tabs_ready = true;
+    return MPB_OK;
+}
+
+}  // namespace
+
+int mpb_contigs_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int64_t *fidx, const char *rtext,
+                          int64_t rtext_bytes, const int64_t *ridx, int64_t n, int32_t fastq_offset,
+                          const mpb_contig_params *params, int64_t rec_cap, char *out_buf, int64_t *out_idx, int32_t *overlap,
+                          int32_t *gaps, int32_t *mismatches, uint8_t *done, char *aln_out, int64_t aln_cap,
+                          int32_t *aln_len_out, int32_t *score_out, int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record)
+{
+    CTXCHK(c);
+    if (bad_record) *bad_record = -1;
+    if (n_done) *n_done = 0;
+    if (n_handed_back) *n_handed_back = 0;
+    if (!params) return fail(MPB_E_INVALID, "params is NULL");
+    if (n < 0 || ftext_bytes < 0 || rtext_bytes < 0 || rec_cap <= 0 || (ftext_bytes > 0 && !ftext) || (rtext_bytes > 0 && !rtext))
+        return fail(MPB_E_INVALID, "mpb_contigs_text_host: bad arguments");
+    if (n > 0x7fffffffll - 4096) return fail(MPB_E_INVALID, "chunk of %lld pairs exceeds 2^31; split it", (long long)n);
+    if (n > 0 && (!fidx || !ridx || !out_buf || !out_idx || !overlap || !gaps || !mismatches || !done))
+        return fail(MPB_E_INVALID, "NULL host buffer");
+    if (aln_out && (aln_cap <= 0 || !aln_len_out || !score_out)) return fail(MPB_E_INVALID, "aln_out needs aln_cap > 0, aln_len_out and score_out");
+    if (!aln_out) aln_cap = 0;
+    // 1. the descriptors, validated on the host before anything is uploaded
+    std::vector<mpb_pair_row> rows;
+    std::vector<int32_t> list;
+    std::vector<int8_t> cls;                             // the size class of a pair (-1: in no list)
+    try { rows.resize((size_t)n); list.resize((size_t)n); cls.assign((size_t)n, -1); } catch (const std::bad_alloc &) { return fail(MPB_E_NOMEM, "out of host memory for %lld pair descriptors", (long long)n); }
+    int rc = mpb_pair_rows(fidx, ridx, n, ftext_bytes, rtext_bytes, rec_cap, rows.data(), bad_record);
+    if (rc) return rc;
+    // 2. make_contig's parameter checks, with its messages
+    if (params->insert <= 0) return fail(MPB_E_INVALID, "insert must be a positive integer");
+    if (params->deltaq <= 0) return fail(MPB_E_INVALID, "deltaq must be a positive integer");
+    if (params->qscore_cap < 0) return fail(MPB_E_INVALID, "qscore_cap must be a non-negative integer");
+    if (params->consensus < 0 || params->consensus > 2) return fail(MPB_E_INVALID, "consensus_qscore must be \"best\", \"sum\" or \"posterior\".");
+    if (n == 0) return MPB_OK;
+    auto mag = [](int32_t v) { return (int64_t)(v < 0 ? -(int64_t)v : v); };
+    const int64_t maxabs = std::max(mag(params->match), std::max(mag(params->mismatch), mag(params->gap)));
+    // 3. the size classes: the pairs the device takes, by the LDS their block needs (a pair outside 1..384 bases, or one whose scores
+    // could leave 16 bits, is in no list: handed back)
+    int64_t per_class[32] = {0};
+    const bool whole_back = fastq_offset < 0 || fastq_offset > 255 || maxabs >= 30000;
+    for (int64_t i = 0; i < n && !whole_back; i++) {
+        if (!cd_row_ok(rows[(size_t)i], ftext_bytes, rtext_bytes, rec_cap, (int)maxabs)) continue;
+        const int need = cd_lds_bytes(rows[(size_t)i].l1, rows[(size_t)i].l2);
+        for (int k = 0; k < k_n_class; k++)
+            if (need <= k_lds_class[k]) { cls[(size_t)i] = (int8_t)k; per_class[k]++; break; }
+    }
+    int64_t first[32], fill[32], listed = 0;
+    for (int k = 0; k < k_n_class; k++) { first[k] = fill[k] = listed; listed += per_class[k]; }
+    for (int64_t i = 0; i < n; i++)
+        if (cls[(size_t)i] >= 0) list[(size_t)fill[cls[(size_t)i]]++] = (int32_t)i;
+    if (listed == 0) {
+        memset(done, 0, (size_t)n);
+        if (n_handed_back) *n_handed_back = n;
+        return MPB_OK;
+    }
+    if (params->consensus == 2 && (rc = ensure_tables(c))) return rc;
+    // 4. the device block of the call
+    ContigStage st{};
+    if ((rc = carve(c, c->contig_stage, [&](Carver &k) { st.layout(k, ftext_bytes, rtext_bytes, n, rec_cap, aln_cap); }))) return rc;
+    hipStream_t s = c->stream;
+    const int64_t fcap = align_up(ftext_bytes > 0 ? ftext_bytes : 1, 16), rcap = align_up(rtext_bytes > 0 ? rtext_bytes : 1, 16);
+    // (everything below is queued on one stream; the host blocks it reads from outlive the synchronisation every path passes)
+    hipError_t e = hipSuccess;
+    if (fcap > ftext_bytes) e = hipMemsetAsync(st.ftext + ftext_bytes, 0, (size_t)(fcap - ftext_bytes), s);
+    if (e == hipSuccess && rcap > rtext_bytes) e = hipMemsetAsync(st.rtext + rtext_bytes, 0, (size_t)(rcap - rtext_bytes), s);
+    if (e == hipSuccess) e = hipMemsetAsync(st.done, 0, (size_t)n, s);
+    if (e == hipSuccess && ftext_bytes > 0) e = hipMemcpyAsync(st.ftext, ftext, (size_t)ftext_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && rtext_bytes > 0) e = hipMemcpyAsync(st.rtext, rtext, (size_t)rtext_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st.rows, rows.data(), (size_t)n * sizeof(mpb_pair_row), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st.list, list.data(), (size_t)listed * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (contig upload)", e); }
+    MpbContigArgs a{};
+    a.ftext = st.ftext; a.fbytes = ftext_bytes; a.rtext = st.rtext; a.rbytes = rtext_bytes;
+    a.rows = st.rows; a.n = n;
+    a.prm.match = params->match; a.prm.mismatch = params->mismatch; a.prm.gap = params->gap; a.prm.insert = params->insert;
+    a.prm.deltaq = params->deltaq; a.prm.consensus = params->consensus; a.prm.qcap = params->qscore_cap;
+    a.prm.trim = params->trim_overlap ? 1 : 0; a.prm.offset = fastq_offset; a.prm.maxabs = (int)maxabs;
+    a.rec_cap = rec_cap;
+    a.tab_match = params->consensus == 2 ? (const int32_t *)c->contig_tabs.p : nullptr;
+    a.tab_mism = a.tab_match ? a.tab_match + 65536 : nullptr;
+    a.out_buf = st.out_buf; a.out_idx = st.out_idx; a.overlap = st.overlap; a.gaps = st.gaps; a.mism = st.mism; a.done = st.done;
+    a.aln_out = aln_out ? st.aln : nullptr; a.aln_cap = aln_cap; a.aln_len = st.aln_len; a.score = st.score;
+    // 5. one launch per size class
+    for (int k = 0; k < k_n_class; k++) {
+        if (!per_class[k]) continue;
+        a.list = st.list + first[k]; a.count = per_class[k]; a.lds_cap = k_lds_class[k];
+        mpb_launch_contigs(a, s);
+    }
+    e = hipGetLastError();
+    // 6. the slots and arrays
+    if (e == hipSuccess) e = hipMemcpyAsync(out_buf, st.out_buf, (size_t)(n * rec_cap), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_idx, st.out_idx, (size_t)n * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(overlap, st.overlap, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(gaps, st.gaps, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(mismatches, st.mism, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(done, st.done, (size_t)n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && aln_out) e = hipMemcpyAsync(aln_out, st.aln, (size_t)(2 * n * aln_cap), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && aln_out) e = hipMemcpyAsync(aln_len_out, st.aln_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && aln_out) e = hipMemcpyAsync(score_out, st.score, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    const hipError_t e_sync = hipStreamSynchronize(s);
+    HIPCHK_KEPT("k_contig / hipMemcpyAsync (contig results)", e);
+    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    int64_t nd = 0;
+    for (int64_t i = 0; i < n; i++) nd += done[i] != 0;
+    if (n_done) *n_done = nd;
+    if (n_handed_back) *n_handed_back = n - nd;
+    return MPB_OK;
+}

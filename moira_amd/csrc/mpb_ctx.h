@@ -172,6 +172,9 @@ struct mpb_ctx {
     Buf pt_rec{BUF_DEVICE};              // MPB_PT_REC_CAP records of reads k_poisson_tail handed back (first device-tail call)
     int rg_per_cu[MPB_NRG_FORMS] = {0};  // blocks per CU of the ragged pass' instantiations (the first ragged call)
     Buf text_stage{BUF_DEVICE};          // mpb_filter_text_host: text | descriptors | status | one piece of the matrix | the results of the call
+    Buf contig_stage{BUF_DEVICE};        // mpb_contigs_text_host: both texts | descriptors | class lists | the slots and arrays of the call
+    Buf contig_tabs{BUF_DEVICE};         // ... and the two posterior tables, uploaded by the first posterior call
+    bool contig_tabs_ready = false;
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)

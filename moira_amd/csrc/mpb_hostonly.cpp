@@ -5,8 +5,10 @@
 // is how tools/asan_api.sh and tools/tsan_poisson.sh run it under the host sanitizers.
 
 #include "mpb_hostonly.h"
+#include "contig_posterior.h"            // the two posterior expressions of make_contig (shared with contig.cpp)
 
 #include <cctype>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -212,6 +214,57 @@ int mpb_text_rows(const int64_t *idx, int64_t n_records, const int64_t *sel, int
         if (row_stride > 0) { rows_out[k].seq_off = so; rows_out[k].qual_off = qo; rows_out[k].len = (int32_t)len; rows_out[k].pad = 0; }
     }
     if (longest_out) *longest_out = longest;
+    return MPB_OK;
+}
+
+// The pair descriptors k_contig walks, from the two record indexes (columns: header offset 0, header length 1, sequence offset 2,
+// sequence length 3, quality offset 4, quality length 5).  As mpb_text_rows: validation, never clamping; the kernel rechecks.
+int mpb_pair_rows(const int64_t *fidx, const int64_t *ridx, int64_t n, int64_t ftext_bytes, int64_t rtext_bytes, int64_t rec_cap,
+                  mpb_pair_row *rows_out, int64_t *bad_record)
+{
+    if (bad_record) *bad_record = -1;
+    if (n < 0 || ftext_bytes < 0 || rtext_bytes < 0 || rec_cap <= 0 || (n > 0 && (!fidx || !ridx || !rows_out)))
+        return fail(MPB_E_INVALID, "mpb_pair_rows: bad arguments");
+    for (int64_t i = 0; i < n; i++) {
+        auto bad = [&](const char *what, long long v) {
+            if (bad_record) *bad_record = i;
+            return fail(MPB_E_INVALID, "pair %lld: %s (%lld)", (long long)i, what, v);
+        };
+        const int64_t *f = fidx + i * MPB_IDX_COLS, *r = ridx + i * MPB_IDX_COLS;
+        const int64_t ho = f[0], hl = f[1], l1 = f[3], l2 = r[3];
+        if (ho < 0 || hl < 0) return bad("negative header offset or length", (long long)(ho < 0 ? ho : hl));
+        if (hl > ftext_bytes || ho > ftext_bytes - hl) return bad("the header ends past the text; offset", (long long)ho);
+        if (l1 < 0 || l2 < 0) return bad("negative length", (long long)(l1 < 0 ? l1 : l2));
+        if (l1 > 0x7fffffffll || l2 > 0x7fffffffll || hl > 0x7fffffffll) return bad("length above 2^31 - 1", (long long)(l1 > l2 ? l1 : l2));
+        if (f[MPB_IDX_QUAL_LEN] != l1) return bad("forward sequence and quality lines differ in length; quality length", (long long)f[MPB_IDX_QUAL_LEN]);
+        if (r[MPB_IDX_QUAL_LEN] != l2) return bad("reverse sequence and quality lines differ in length; quality length", (long long)r[MPB_IDX_QUAL_LEN]);
+        const int64_t fs = f[MPB_IDX_SEQ_OFF], fq = f[MPB_IDX_QUAL_OFF], rs = r[MPB_IDX_SEQ_OFF], rq = r[MPB_IDX_QUAL_OFF];
+        if (fs < 0 || fq < 0 || rs < 0 || rq < 0) return bad("negative offset", (long long)(fs < 0 ? fs : fq < 0 ? fq : rs < 0 ? rs : rq));
+        if (l1 > ftext_bytes || fs > ftext_bytes - l1) return bad("the forward sequence line ends past the text; offset", (long long)fs);
+        if (fq > ftext_bytes - l1) return bad("the forward quality line ends past the text; offset", (long long)fq);
+        if (l2 > rtext_bytes || rs > rtext_bytes - l2) return bad("the reverse sequence line ends past the text; offset", (long long)rs);
+        if (rq > rtext_bytes - l2) return bad("the reverse quality line ends past the text; offset", (long long)rq);
+        if (hl + 2 * (l1 + l2) > rec_cap) return bad("the contig does not fit rec_cap; bytes needed", (long long)(hl + 2 * (l1 + l2)));
+        mpb_pair_row &o = rows_out[i];
+        o.fseq_off = fs; o.fqual_off = fq; o.fhdr_off = ho; o.rseq_off = rs; o.rqual_off = rq;
+        o.l1 = (int32_t)l1; o.l2 = (int32_t)l2; o.hdr_len = (int32_t)hl; o.pad = 0;
+    }
+    return MPB_OK;
+}
+
+int mpb_contig_posterior_tables(int32_t *match_out, int32_t *mismatch_out)
+{
+    if (!match_out || !mismatch_out) return fail(MPB_E_INVALID, "mpb_contig_posterior_tables: NULL table");
+    // prob2qual = (int)floor(-10 log10 p), kept out of the cast where it is no finite integer
+    auto q_of = [](double p) {
+        const double v = floor(-10 * log10(p));
+        return (v > -2e9 && v < 2e9) ? (int32_t)v : INT32_MIN;
+    };
+    for (int f = 0; f < 256; f++)
+        for (int r = 0; r < 256; r++) {
+            match_out[f * 256 + r] = q_of(posterior_match_p(f, r));
+            mismatch_out[f * 256 + r] = f == r ? 2 : q_of(posterior_mismatch_p(f, r));
+        }
     return MPB_OK;
 }
 

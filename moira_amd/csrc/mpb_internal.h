@@ -238,6 +238,9 @@ void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS]);
 // predicted row budgets of `n_sample` reads spread over the batch -> ws.nar_sample (zeroed here)
 void mpb_launch_sample(const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len, const MpbDevParams &prm,
                        const MpbWorkspace &ws, int n_sample, hipStream_t s);
+// k_contig (mpb_contig_kernels.hip; the arguments: mpb_contig_args.h): one wave per listed pair, lds_bytes of LDS per wave
+struct MpbContigArgs;
+void mpb_launch_contigs(const MpbContigArgs &a, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

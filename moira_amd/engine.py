@@ -111,6 +111,34 @@ def text_rows(idx, sel=None, text_bytes=0, max_len=0, stride=0):
     return rows, longest.value
 
 
+PAIR_ROW_DTYPE = np.dtype([("fseq_off", "<i8"), ("fqual_off", "<i8"), ("fhdr_off", "<i8"), ("rseq_off", "<i8"), ("rqual_off", "<i8"),
+                           ("l1", "<i4"), ("l2", "<i4"), ("hdr_len", "<i4"), ("pad", "<i4")])     # mpb_pair_row
+
+
+def pair_rows(fidx, ridx, ftext_bytes, rtext_bytes, rec_cap):
+    """The validated pair descriptors (mpb_pair_rows; host only) of the two record indexes over texts of the given sizes -> a
+    PAIR_ROW_DTYPE array.  ValueError (MPB_E_INVALID) for an offset or length outside its text, a sequence and quality line
+    of different lengths, or hdr_len + 2 (l1 + l2) > rec_cap; .bad_record = the pair's position."""
+    fidx, ridx = np.ascontiguousarray(fidx, np.int64), np.ascontiguousarray(ridx, np.int64)
+    if fidx.ndim != 2 or fidx.shape[1] != 6 or fidx.shape != ridx.shape:
+        raise ValueError("fidx and ridx must be (n x 6) int64 record indexes of the same length")
+    rows = np.zeros(len(fidx), PAIR_ROW_DTYPE)
+    bad = C.c_int64(-1)
+    rc = L.load().mpb_pair_rows(fidx.ctypes.data, ridx.ctypes.data, len(fidx), int(ftext_bytes), int(rtext_bytes), int(rec_cap),
+                                rows.ctypes.data, C.byref(bad))
+    _check_text(rc, bad)
+    return rows
+
+
+class ContigResult:
+    """What Engine.contigs_text returns (see there)."""
+    __slots__ = ("cbuf", "cidx", "aux", "done", "rec_cap", "n_done", "n_handed_back", "aln", "aln_len", "score")
+
+    def __init__(self, *a):
+        for k, v in zip(self.__slots__, a):
+            setattr(self, k, v)
+
+
 def check_host_batch(q, lens, fixed_len, out, limit):
     """Argument checks shared by every host-batch entry (one GPU or several): -> (q, n, stride, lens, (ee, ns, ps)).
     `limit`: longest read the method takes (None: as long as the row)."""
@@ -304,6 +332,48 @@ class Engine:
         del keep
         _check_text(rc, bad)
         return TextFilterResult(ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), counts.n_pass, counts.n_overflow)
+
+    # ---- paired-read contigs on the device (mpb_pair_rows, k_contig) ------------------------------
+    @staticmethod
+    def pair_rows(fidx, ridx, ftext_bytes, rtext_bytes, rec_cap):
+        """The validated pair descriptors of k_contig: see the module's pair_rows (host only, needs no device)."""
+        return pair_rows(fidx, ridx, ftext_bytes, rtext_bytes, rec_cap)
+
+    def contigs_text(self, fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatch=-1, gap=-2, insert=20, deltaq=6,
+                     consensus=0, qscore_cap=40, trim_overlap=False, rec_cap=None, alignments=False):
+        """Contigs of a chunk of paired records that are still FASTQ text, built on the device (mpb_contigs_text_host; consensus
+        0 best, 1 sum, 2 posterior) -> ContigResult: cbuf / cidx / aux as moira_amd.contig.contigs_from_fastq returns them and
+        done (bool per pair).  Slot, index row and aux row of a pair with done == False are undefined: the device handed it
+        back and the host aligner builds it (contigs_from_fastq(..., engine=...) does).  alignments=True also returns the
+        aligned strings and scores (aln uint8[n, 2, aln_cap], aln_len, score)."""
+        fidx, ridx = np.ascontiguousarray(fidx, np.int64), np.ascontiguousarray(ridx, np.int64)
+        if fidx.ndim != 2 or fidx.shape[1] != 6 or fidx.shape != ridx.shape:
+            raise ValueError("fidx and ridx must be (n x 6) int64 record indexes of the same length")
+        n = len(fidx)
+        fkeep, faddr, fbytes = _text_ptr(fbuf)
+        rkeep, raddr, rbytes = _text_ptr(rbuf)
+        if rec_cap is None:
+            rec_cap = int((fidx[:, 1] + 2 * (fidx[:, 3] + ridx[:, 3])).max()) + 8 if n else 8
+        cbuf, cidx = np.empty(n * rec_cap, np.uint8), np.empty((n, 6), np.int64)
+        aux = np.empty((3, n), np.int32)
+        done = np.zeros(n, np.uint8)
+        aln = aln_len = score = None
+        aln_cap = 0
+        if alignments:
+            aln_cap = max(int((fidx[:, 3] + ridx[:, 3]).max()) if n else 1, 1)
+            aln, aln_len, score = np.zeros((n, 2, aln_cap), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        prm = L.ContigParams(int(match), int(mismatch), int(gap), int(insert), int(deltaq), int(consensus), int(qscore_cap),
+                             1 if trim_overlap else 0)
+        n_done, n_back, bad = C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+        rc = self.lib.mpb_contigs_text_host(self.ctx, faddr, fbytes, fidx.ctypes.data, raddr, rbytes, ridx.ctypes.data, n,
+                                            int(fastq_offset), C.byref(prm), int(rec_cap), cbuf.ctypes.data, cidx.ctypes.data,
+                                            aux[0].ctypes.data, aux[1].ctypes.data, aux[2].ctypes.data, done.ctypes.data,
+                                            aln.ctypes.data if alignments else None, aln_cap,
+                                            aln_len.ctypes.data if alignments else None, score.ctypes.data if alignments else None,
+                                            C.byref(n_done), C.byref(n_back), C.byref(bad))
+        del fkeep, rkeep
+        _check_text(rc, bad)
+        return ContigResult(cbuf, cidx, np.ascontiguousarray(aux.T), done.view(bool), rec_cap, n_done.value, n_back.value, aln, aln_len, score)
 
     def decode_ascii_device(self, d_seq, d_qual, n, stride, d_out, d_len=None, fixed_len=0, fastq_offset=33,
                             d_err=None):

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 FL="-O3 --offload-arch=gfx950 -fPIC -shared -std=c++17 -ffp-contract=off -fno-fast-math -pthread -Iinclude -x hip"
 PROBE=${PROBE:-tools/narrow_probe.py}; N=${N:-10000000}
 mkdir -p /tmp/var
-HOST=$(python -m moira_amd.build --host-sources) || exit 1      # the host units of the library, as build.py lists them
+HOST=$(python -m moira_amd.build --units-beside-kernels) || exit 1      # every unit of the library besides mpb_kernels.hip (the host units and k_contig's file), as build.py lists them
 for v in ${VARIANTS:-whole: arith_alone:rs_arith_alone stream_alone:rs_stream_alone}; do
   name=${v%%:*}; patch=${v#*:}; SRC=moira_amd/csrc/mpb_kernels.hip
   if [ "${patch:0:1}" = "@" ]; then python tools/experiments/make_variant.py none /tmp/var/$name.hip ${patch:1} || exit 1; SRC=/tmp/var/$name.hip      # name:@another_copy_of_the_kernels.hip

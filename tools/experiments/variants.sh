@@ -12,7 +12,7 @@ while [ "${1:0:1}" = "-" ]; do
 done
 FL="-O3 --offload-arch=gfx950 -fPIC -shared -std=c++17 -ffp-contract=off -fno-fast-math -pthread -Iinclude -x hip"
 mkdir -p /tmp/var
-HOST=$(python -m moira_amd.build --host-sources) || exit 1      # the host units of the library, as build.py lists them
+HOST=$(python -m moira_amd.build --units-beside-kernels) || exit 1      # every unit of the library besides mpb_kernels.hip (the host units and k_contig's file), as build.py lists them
 names=()
 for spec in "$@"; do
   name=${spec%%:*}; rest=${spec#*:}; defs=${rest%%@*}; names+=($name)
