@@ -744,6 +744,12 @@ int mpb_last_algorithmic_cells(mpb_ctx *ctx, int64_t *cells);
  *   narrow_split ragged batches, narrow_rows >= 3 ("mixed rows"): how many rows a read of a given quality needs grows with its length,
  *                and the pass walks its reads sorted by length -- groups whose longest read has at most this many 16-byte chunks
  *                (safely fewer than the shortest sampled read that needed narrow_rows rows) ran with narrow_rows - 1 rows; 0: none
+ *   narrow_waves the waves of the pass' persistent grid in this call (four per workgroup); 0 when the pass did not run
+ * Environment MPB_NARROW_GRID_BLOCKS (a test hook, read once per call that takes the narrow pass): a value of 1 .. 2048 caps the
+ * workgroups of that grid, after the library's own caps, so that a wave walks several row blocks / stream blocks / groups of a batch
+ * of a few thousand reads (by itself the grid has a wave per block up to what the CUs hold at once, thousands of waves); unset or
+ * any other value: no cap.
+ * Every result is the same whatever the grid (only which wave walks which block changes); narrow_waves reports what was launched.
  */
 typedef struct mpb_path_info {
     int32_t narrow_rows;
@@ -752,7 +758,7 @@ typedef struct mpb_path_info {
     int32_t sample_hist[16];
     int32_t narrow_split;   /* round 6, ragged batches with narrow_rows >= 3: groups of the pass whose longest read has at most this
                                many 16-byte chunks ran with narrow_rows - 1 rows (0: none) */
-    int32_t reserved_;
+    int32_t narrow_waves;   /* waves of the last narrow launch (0: the pass did not run) */
 } mpb_path_info;
 int mpb_last_path(mpb_ctx *ctx, mpb_path_info *out);
 

@@ -228,12 +228,14 @@ void mpb_launch_pack_text(const uint8_t *text, int64_t text_bytes, const mpb_tex
 // MPB_NRG_FORMS ragged instantiations (mpb_narrow_rg_blocks_per_cu; only read for ragged batches).
 // lut_odds != nullptr (MPB_FLAG_ODDS | MPB_FLAG_ODDS_NARROW): the one-FMA twins (k_odds_nar, k_odds_nar_rs, k_odds_nar_rg) on that
 // {a, r = p / (1 - p)} table; no mixed rows then (split_chunks is ignored).
+// grid_cap > 0: at most that many workgroups (the test hook MPB_NARROW_GRID_BLOCKS; 0: none).  *waves: the waves of the grid.
 #define MPB_RG_MAX_STRIDE 4096
 #define MPB_NRG_FORMS 8                   // k_narrow_rg's MPB_NRG_EXACT_FORMS instantiations, then k_odds_nar_rg<2..4>
 #define MPB_NRG_EXACT_FORMS 5
+#define MPB_NAR_GRID_CAP_MAX 2048         // the largest cap the hook takes (MPB_NAR_MAX_WAVES / 4)
 void mpb_launch_narrow(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len,
                        const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int n_cu,
-                       const int *rg_per_cu, hipStream_t s, const double2 *lut_odds = nullptr);
+                       const int *rg_per_cu, int grid_cap, int *waves, hipStream_t s, const double2 *lut_odds = nullptr);
 void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS]);
 // predicted row budgets of `n_sample` reads spread over the batch -> ws.nar_sample (zeroed here)
 void mpb_launch_sample(const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len, const MpbDevParams &prm,

@@ -2890,11 +2890,26 @@ void mpb_narrow_rg_blocks_per_cu(int per_cu[MPB_NRG_FORMS])
     }
 }
 
+// Workgroups (of four waves) of the persistent grid: one wave per row block / stream block / group, at most what the CUs hold at once
+// (per_cu workgroups each) and what the per-wave arrays hold.  grid_cap > 0: at most that many (MPB_NARROW_GRID_BLOCKS, a test hook:
+// with a small grid a wave walks several blocks of a small batch; a smaller grid is resident at once all the same).  *waves: the
+// grid's waves, for mpb_path_info.
+static int64_t nar_grid_blocks(int64_t nblk, int n_cu, int per_cu, int grid_cap, int *waves)
+{
+    int64_t blocks = (nblk + 3) / 4;
+    if (blocks > (int64_t)n_cu * per_cu) blocks = (int64_t)n_cu * per_cu;
+    if (blocks > MPB_NAR_MAX_WAVES / 4) blocks = MPB_NAR_MAX_WAVES / 4;
+    if (grid_cap > 0 && blocks > grid_cap) blocks = grid_cap;
+    if (blocks < 1) blocks = 1;
+    *waves = (int)blocks * 4;
+    return blocks;
+}
+
 // The pass in its one-FMA form (MPB_FLAG_ODDS | MPB_FLAG_ODDS_NARROW): the twins on the {a, r} table `lut`; the grid is sized as in
 // mpb_launch_narrow below; no mixed rows (k_rag_sort without a cut).
 static void launch_narrow_odds(int rows0, const double2 *lut, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len,
                                const int32_t *len, const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass,
-                               int n_cu, const int *rg_per_cu, hipStream_t s)
+                               int n_cu, const int *rg_per_cu, int grid_cap, int *waves, hipStream_t s)
 {
     const int ri = rows0 <= 2 ? 0 : rows0 == 3 ? 1 : 2;
     const int rg = MPB_NRG_EXACT_FORMS + ri;
@@ -2905,10 +2920,7 @@ static void launch_narrow_odds(int rows0, const double2 *lut, const uint8_t *q, 
     if (len && rg_per_cu[rg] < per_cu) per_cu = rg_per_cu[rg];
     const int per_blk = 64 * (rs_k ? rs_k : 1);
     const int64_t nblk = (n + per_blk - 1) / per_blk;
-    int64_t blocks = (nblk + 3) / 4;
-    if (blocks > (int64_t)n_cu * per_cu) blocks = (int64_t)n_cu * per_cu;
-    if (blocks > MPB_NAR_MAX_WAVES / 4) blocks = MPB_NAR_MAX_WAVES / 4;
-    if (blocks < 1) blocks = 1;
+    const int64_t blocks = nar_grid_blocks(nblk, n_cu, per_cu, grid_cap, waves);
     const int nwaves = (int)blocks * 4;
     const dim3 grid((unsigned)blocks), block(256);
     if (len) {
@@ -2934,9 +2946,9 @@ static void launch_narrow_odds(int rows0, const double2 *lut, const uint8_t *q, 
 
 void mpb_launch_narrow(int rows0, int split_chunks, const uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, const int32_t *len,
                        const MpbDevParams &prm, const MpbWorkspace &ws, double *ee, int32_t *ns, uint8_t *pass, int n_cu,
-                       const int *rg_per_cu, hipStream_t s, const double2 *lut_odds)
+                       const int *rg_per_cu, int grid_cap, int *waves, hipStream_t s, const double2 *lut_odds)
 {
-    if (lut_odds) return launch_narrow_odds(rows0, lut_odds, q, n, stride, fixed_len, len, prm, ws, ee, ns, pass, n_cu, rg_per_cu, s);
+    if (lut_odds) return launch_narrow_odds(rows0, lut_odds, q, n, stride, fixed_len, len, prm, ws, ee, ns, pass, n_cu, rg_per_cu, grid_cap, waves, s);
     const int ri = rows0 <= 2 ? 0 : rows0 == 3 ? 1 : 2;
     const bool mixed = len && split_chunks > 0 && rows0 >= 3;          // short groups with a row less (k_narrow_rg<R, R - 1>)
     const int rg = mixed ? ri + 2 : ri;
@@ -2949,10 +2961,7 @@ void mpb_launch_narrow(int rows0, int split_chunks, const uint8_t *q, int64_t n,
     if (len && rg_per_cu[rg] < per_cu) per_cu = rg_per_cu[rg];
     const int per_blk = 64 * (rs_k ? rs_k : 1);              // reads of one row block / stream block / group
     const int64_t nblk = (n + per_blk - 1) / per_blk;
-    int64_t blocks = (nblk + 3) / 4;
-    if (blocks > (int64_t)n_cu * per_cu) blocks = (int64_t)n_cu * per_cu;
-    if (blocks > MPB_NAR_MAX_WAVES / 4) blocks = MPB_NAR_MAX_WAVES / 4;
-    if (blocks < 1) blocks = 1;
+    const int64_t blocks = nar_grid_blocks(nblk, n_cu, per_cu, grid_cap, waves);
     const int nwaves = (int)blocks * 4;
     const dim3 grid((unsigned)blocks), block(256);
     if (len) {

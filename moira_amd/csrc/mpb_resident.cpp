@@ -7,6 +7,7 @@
 #include "mpb_ctx.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 // ---- the hot path --------------------------------------------------------------------------------
@@ -187,6 +188,17 @@ static int narrow_choose(mpb_ctx *c, const uint8_t *d_q, int64_t n, int64_t row_
     return MPB_OK;
 }
 
+// MPB_NARROW_GRID_BLOCKS (include/moira_pb.h, a test hook): a cap on the workgroups of the pass' persistent grid, read per call;
+// 0: none (unset, or anything but 1 .. MPB_NAR_GRID_CAP_MAX)
+static int narrow_grid_cap()
+{
+    const char *e = getenv("MPB_NARROW_GRID_BLOCKS");
+    if (!e || !*e) return 0;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);
+    return *end == 0 && v >= 1 && v <= MPB_NAR_GRID_CAP_MAX ? (int)v : 0;
+}
+
 static int filter_device_narrow(mpb_ctx *c, int rows0, int split, const uint8_t *d_q, int64_t n, int64_t row_stride, const int32_t *d_len,
                                 int32_t fixed_len, const mpb_filter_params *params, const MpbDevParams &prm,
                                 double *d_ee, int32_t *d_ns, uint8_t *d_pass, mpb_filter_counts *counts)
@@ -194,14 +206,17 @@ static int filter_device_narrow(mpb_ctx *c, int rows0, int split, const uint8_t 
     int rc;
     hipStream_t s = c->stream;
     if ((rc = ensure_narrow_workspace(c, n, d_len != nullptr))) return rc;
+    const int grid_cap = narrow_grid_cap();
+    int nwaves = 0;
     { Span t(c, MPB_K_NARROW);
       mpb_launch_narrow(rows0, split, d_q, n, row_stride, fixed_len, d_len, prm, c->ws, d_ee, d_ns, d_pass, c->n_cu > 0 ? c->n_cu : 256,
-                        c->rg_per_cu, s, (params->flags & MPB_FLAG_ODDS_NARROW) ? c->d_lut_odds : nullptr); }
+                        c->rg_per_cu, grid_cap, &nwaves, s, (params->flags & MPB_FLAG_ODDS_NARROW) ? c->d_lut_odds : nullptr); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&c->pin->nar_count, c->ws.nar_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const int64_t m = c->pin->nar_count;
     c->last_path.narrow_rows = rows0;
+    c->last_path.narrow_waves = nwaves;
     c->last_path.narrow_split = d_len && rows0 >= 3 ? split : 0;
     c->last_path.n_fallback = m;
     const bool forced = ((params->flags >> 8) & 15u) != 0;

@@ -535,11 +535,12 @@ class Engine:
                                                        ptr(d_len) if d_len is not None else None, seed, first_read, profile))
 
     def last_path(self):
-        """Which pass the last filter_device call took: dict(narrow_rows, narrow_split, sampled, n_fallback, sample_hist)."""
+        """Which pass the last filter_device call took: dict(narrow_rows, narrow_split, narrow_waves, sampled, n_fallback,
+        sample_hist)."""
         info = L.PathInfo()
         L.check(self.lib.mpb_last_path(self.ctx, C.byref(info)))
         return {"narrow_rows": info.narrow_rows, "sampled": bool(info.sampled), "n_fallback": info.n_fallback,
-                "sample_hist": list(info.sample_hist), "narrow_split": info.narrow_split}
+                "sample_hist": list(info.sample_hist), "narrow_split": info.narrow_split, "narrow_waves": info.narrow_waves}
 
     # ---- measurement ----------------------------------------------------------------------------
     def timing(self, on=True):

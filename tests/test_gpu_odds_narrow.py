@@ -17,6 +17,7 @@ from helpers import mode_expect as X
 from helpers import odds_narrow_inputs as N
 from helpers import opt_in_inputs as I
 from helpers.device_runs import Resident
+from helpers.odds_forced import check_forced, run          # (the rule for a forced R: shared with test_gpu_narrow_walk.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,36 +32,6 @@ def eng():
     e.batched_only = True
     yield e
     e.close()
-
-
-def run(eng, q, lens, fixed, **kw):
-    """One resident batch through mpb_filter_device -> ((ee, ns, pass), counts, path)."""
-    res = Resident(eng, q, None if fixed else lens)
-    try:
-        ee, ns, ps, c, path, intact = res.run(fixed_len=fixed, **kw)
-        assert intact
-        return (ee, ns, ps), c, path
-    finally:
-        res.free()
-
-
-def check_forced(eng, q, lens, fixed, R, ex, m, valid=None, mode_ran=True, **kw):
-    """The rule for a forced R (module docstring) -> (|F|, n_overflow)."""
-    n = len(q)
-    got, c, path = run(eng, q, lens, fixed, odds=True, odds_narrow=True, narrow_rows=R, **kw)
-    F = N.finished(m, q, lens, R)
-    if valid is not None:
-        F &= valid
-    assert path["narrow_rows"] == R and path["narrow_split"] == 0, path
-    ok = X.matches(*got, m.ee, ex[1], m.passed)
-    bad = np.flatnonzero(F & ~ok)
-    assert bad.size == 0, "%d reads the pass finishes differ from the model, first %s: got %r want %r (exact %r)" % (
-        bad.size, bad[:5].tolist(), got[0][bad[:5]].tolist(), m.ee[bad[:5]].tolist(), ex[0][bad[:5]].tolist())
-    assert path["n_fallback"] == n - int(F.sum()), (path["n_fallback"], n - int(F.sum()))
-    X.check_counting_form(got, ex, m, c.n_overflow)
-    if mode_ran:
-        X.check_mode_ran(got, ex, m, among=F)
-    return int(F.sum()), c.n_overflow
 
 
 # ---- 1, 2: fixed and ragged shapes ------------------------------------------------------------------------------------------------

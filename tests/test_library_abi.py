@@ -168,6 +168,22 @@ def test_pack_batch_ascii_matches_per_read_packer(oracle):
                                         out.ctypes.data, None) == L.E_RANGE
 
 
+def test_path_info_layout_is_the_headers():
+    """mpb_path_info as the header declares it and as _lib.PathInfo restates it: the same fields in the same order, 88 bytes; the
+    last word, once reserved, is narrow_waves (the size and every offset are what they were)."""
+    src = open(os.path.join(ROOT, "include", "moira_pb.h")).read()
+    body = re.search(r"typedef struct mpb_path_info \{(.*?)\} mpb_path_info;", src, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decl = re.findall(r"(int32_t|int64_t)\s+(\w+)(?:\[(\d+)\])?;", body)
+    ctype = {"int32_t": C.c_int32, "int64_t": C.c_int64}
+    want = [(name, ctype[t] * int(k) if k else ctype[t]) for t, name, k in decl]
+    assert [(n, t) for n, t in L.PathInfo._fields_] == want
+    assert [n for n, _ in want] == ["narrow_rows", "sampled", "n_fallback", "sample_hist", "narrow_split", "narrow_waves"]
+    assert C.sizeof(L.PathInfo) == 88
+    assert [getattr(L.PathInfo, n).offset for n, _ in want] == [0, 4, 8, 16, 80, 84]
+    assert "MPB_NARROW_GRID_BLOCKS" in src and "reserved_" not in body
+
+
 def test_contig_library_exports_every_declared_symbol():
     import ctypes
     from moira_amd import contig as CT
