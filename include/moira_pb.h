@@ -151,7 +151,9 @@ extern "C" {
 #define MPB_K_SAMPLE    9   /* ... the batch sample that picks the pass */
 #define MPB_K_POISSON_TAIL 10 /* Poisson approximation: the CDF tail on the device (percentile, +Ns / floor, predicate) */
 #define MPB_K_PACK_TEXT 11   /* FASTQ text + record index -> the packed ragged matrix (k_pack_text) */
-#define MPB_K_COUNT     12
+#define MPB_K_CONTIG    12   /* paired-read contigs: the launches of one chunk, one per size class (k_contig) */
+#define MPB_K_CONTIG_ROWS 13 /* the device's contig index -> k_pack_text's row descriptors (k_contig_rows) */
+#define MPB_K_COUNT     14
 
 typedef struct mpb_ctx mpb_ctx;
 
@@ -487,6 +489,37 @@ int mpb_contigs_text_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_bytes, 
                           char *out_buf, int64_t *out_idx, int32_t *overlap, int32_t *gaps, int32_t *mismatches, uint8_t *done,
                           char *aln_out, int64_t aln_cap, int32_t *aln_len_out, int32_t *score_out,
                           int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record);
+
+/*
+ * The chunk call with the filter behind it (opt-in, beside the two calls it joins); synchronous.  Everything
+ * mpb_contigs_text_host does, in its order and with its errors, up to and including the k_contig launches; then k_contig_rows
+ * (one thread per pair, behind them on the context's stream, no synchronisation in between) turns done[] and the device's own
+ * index into the row descriptors of k_pack_text -- a pair that was handed back is an empty read, and an index row is used only
+ * when sequence and quality lengths agree, the packed length min(quality length, max_len if > 0) lies in 0..min(65535, stride)
+ * and both lines lie inside the pair's own slot (otherwise {0, 0, -1}: k_pack_text's zero row of length -1; the kernel checks
+ * every offset against the buffer once more); then mpb_filter_text_host's piece loop (pieces of at most 256 MiB,
+ * MPB_TEXT_PIECE_BYTES, the three poisson forms, its order of errors) over the slot buffer where it lies; then all copies back.
+ * The row stride is round_up(max(1, min(max over the listed pairs of l1 + l2, max_len if > 0)), 128): known before anything runs.
+ *   filtered[i]         1 exactly for the pairs with done[i] = 1 of a chunk whose filter went through.  For them ee / ns / pass /
+ *                       len_out / flags_out (the last two may be NULL) are what mpb_filter_text_host returns for the same slot
+ *                       and index row; for every other pair the five values are undefined
+ *   counts              may be NULL; the filtered pairs only (n_reads = their number)
+ * A quality out of range in a contig, or a filter call that fails, does not fail the call: it returns MPB_OK with the contigs
+ * complete, filtered all zero, *filter_rc and *filter_bad_record (may be NULL) what mpb_filter_text_host over the built pairs
+ * would have returned (the record's position among them), and mpb_last_error() its message.  Errors of the contig parameters,
+ * of mpb_pair_rows and of the filter parameters are returned before anything is uploaded.  A chunk of which the device takes no
+ * pair returns as mpb_contigs_text_host does, filtered all zero.  MPB_FLAG_FAST_FMA, MPB_FLAG_ODDS and MPB_FLAG_ODDS_NARROW are
+ * taken with mpb_filter_text_host's contract.
+ */
+int mpb_contigs_filter_text_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_bytes, const int64_t *fidx,
+                                 const char *rtext, int64_t rtext_bytes, const int64_t *ridx, int64_t n, int32_t fastq_offset,
+                                 const mpb_contig_params *params, int64_t rec_cap,
+                                 char *out_buf, int64_t *out_idx, int32_t *overlap, int32_t *gaps, int32_t *mismatches, uint8_t *done,
+                                 char *aln_out, int64_t aln_cap, int32_t *aln_len_out, int32_t *score_out,
+                                 int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record,
+                                 int32_t max_len, int32_t lower_n_is_base, const mpb_filter_params *filter_params, int32_t poisson,
+                                 double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, uint8_t *filtered,
+                                 mpb_filter_counts *counts, int *filter_rc, int64_t *filter_bad_record);
 
 /*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is

@@ -31,6 +31,8 @@ K_PACK_TEXT = 11               # MPB_K_PACK_TEXT: FASTQ text + record index -> t
 KERNEL_NAMES = {K_PREPASS: "prepass", K_SCAN: "scan", K_SCATTER: "scatter", K_DP: "dp", K_OVERFLOW: "overflow", K_LAMBDA: "lambda",
                 K_WIDE: "wide", K_NARROW: "narrow", K_FALLBACK: "fallback", K_SAMPLE: "sample", K_POISSON_TAIL: "poisson_tail",
                 K_PACK_TEXT: "pack_text"}
+K_CONTIG, K_CONTIG_ROWS = 12, 13     # MPB_K_CONTIG (k_contig, one span per size class), MPB_K_CONTIG_ROWS (k_contig_rows)
+CONTIG_KERNEL_NAMES = {K_CONTIG: "contig", K_CONTIG_ROWS: "contig_rows"}     # the paired pipeline's kernels, beside the filter's
 
 
 class MoiraPBError(RuntimeError):
@@ -108,6 +110,11 @@ PROTOTYPES = {
     "mpb_contigs_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.POINTER(ContigParams),
                                         C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.POINTER(C.c_int64),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mpb_contigs_filter_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
+                                               C.POINTER(ContigParams), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP,
+                                               _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.c_int32, C.c_int32, C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                               C.POINTER(FilterCounts), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mpb_encode_ascii_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP]),
     "mpb_decode_classify_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
                                              C.POINTER(FilterParams), _VP, _VP, _VP, _VP, _VP]),

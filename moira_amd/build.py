@@ -30,6 +30,7 @@ DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_
                   os.path.join(CSRC, "mpb_narrow_ring.inc"), os.path.join(CSRC, "mpb_narrow_rs.inc"),
                   os.path.join(CSRC, "mpb_narrow_rg.inc"),
                   os.path.join(CSRC, "mpb_contig_lane.inc"), os.path.join(CSRC, "mpb_contig_args.h"),
+                  os.path.join(CSRC, "mpb_contig_rows.inc"),
                   os.path.join(CSRC, "contig_posterior.h"),
                   os.path.join(CSRC, "libmoira_pb.map"),
                   os.path.join(ROOT, "include", "moira_pb.h"),

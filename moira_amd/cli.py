@@ -241,7 +241,8 @@ def build_parser():
                    help="(not in moira.py) FASTQ input on one GPU: upload each chunk of text as it lies in the file and build the "
                         "quality matrix on the device (one call per chunk) instead of packing it on the host, one length bucket "
                         "at a time. Results and output files are identical. Where it does not apply (fasta+qual input, the line "
-                        "parser, several GPUs, no GPU) one line says so and host packing is used.")
+                        "parser, several GPUs, no GPU) one line says so and host packing is used. With --device_contigs as well, "
+                        "the contigs of a paired chunk are packed and filtered where the device built them, in the same call.")
     return p
 
 
@@ -570,21 +571,25 @@ def make_gpu_backend(device=None):
             return r.ee    # settled reads: +inf from the kernel; a NaN is a genuine failure and raises ReturnedNaNError
         run = eng.filter_poisson if method == "poisson" else eng.filter
         return run(q, lens=lens, alpha=alpha, ambigs=ambigs, round_=round_, uncert=1.0).ee
-    def text(buf, idx, alpha, ambigs, round_, fastq_offset, max_len, lower_n_is_base, method="poisson_binomial", fast_discard=None):
-        """The same for a chunk of FASTQ text as it lies in the file and its record index (--device_pack): the quality
-        matrix is built on the device.  -> (ee per record, has_n per record)."""
-        kw = dict(fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base, alpha=alpha, ambigs=ambigs,
-                  round_=round_)
+    def text_choice(alpha, ambigs, round_, method="poisson_binomial", fast_discard=None):
+        """The filter arguments a text call makes of the run's options (text below, and the fused contig call)."""
+        kw = dict(alpha=alpha, ambigs=ambigs, round_=round_)
         if fast_discard is not None and method == "poisson_binomial":
             uncert, maxerrors = fast_discard
-            r = eng.filter_text(buf, idx, uncert=uncert, maxerrors=maxerrors, decision_only=True, **kw)
-        else:
-            r = eng.filter_text(buf, idx, poisson=method == "poisson", uncert=1.0, **kw)
+            return dict(uncert=uncert, maxerrors=maxerrors, decision_only=True, **kw)
+        return dict(poisson=method == "poisson", uncert=1.0, **kw)
+    def text(buf, idx, alpha, ambigs, round_, fastq_offset, max_len, lower_n_is_base, method="poisson_binomial", fast_discard=None,
+             sel=None):
+        """The same for a chunk of FASTQ text as it lies in the file and its record index (--device_pack): the quality
+        matrix is built on the device.  -> (ee per record, has_n per record); sel: of those records only."""
+        r = eng.filter_text(buf, idx, sel=sel, fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base,
+                            **text_choice(alpha, ambigs, round_, method, fast_discard))
         return r.ee, r.has_n
     backend.engine = eng
     backend.matrix = matrix
     if len(devs) == 1:
         backend.text = text                            # one device (the text entry has no multi-GPU form)
+        backend.text_choice = text_choice
     backend.per_read = eng.calculate_errors_PB         # any int quality (a read whose scores do not fit the byte matrix)
     backend.per_read_poisson = eng.calculate_errors_poisson
     backend.methods = ("poisson_binomial", "poisson")
@@ -972,21 +977,60 @@ def _chunk_contigs(args, fbuf, fidx, rbuf, ridx, offset, engine=None):
         raise F.Unsupported(str(e))
 
 
+def _fused_applies(device_contigs, device_pack, only, backend):
+    """The fused contig-and-filter call is taken when --device_contigs and --device_pack are both in force for a run that reaches
+    the device pack (not --only_contig), on a backend whose engine has the call."""
+    return bool(device_contigs and device_pack and not only and getattr(backend, "text_choice", None) is not None
+                and hasattr(getattr(backend, "engine", None), "contigs_filter_text"))
+
+
+def _chunk_contigs_filtered(args, fbuf, fidx, rbuf, ridx, offset, backend, filt):
+    """The contigs of one chunk of pairs and their filter in one device call (moira_amd.contig.contigs_from_fastq_filtered) ->
+    (cbuf, cidx, aux, ee, has_n, filter_error); filt = (method, fast_discard, max_len, lower_n_is_base).  The pairs the device
+    does not finish are built on the host and filtered through backend.text, so results and errors are the two-call path's."""
+    from . import contig as CT
+    from . import fastio as F
+    method, fd, T, n_is_base = filt
+    choice = backend.text_choice(args.alpha, args.ambigs, args.round, method, fd)
+    rest = lambda buf, idx, sel: backend.text(buf, idx, args.alpha, args.ambigs, args.round, offset, T, n_is_base, method=method,
+                                              fast_discard=fd, sel=sel)
+    try:
+        return CT.contigs_from_fastq_filtered(fbuf, fidx, rbuf, ridx, offset, args.match, args.mismatch, args.gap, args.insert,
+                                              args.deltaq, args.consensus_qscore, args.qscore_cap, args.trim_overlap,
+                                              threads=args.processors, engine=backend.engine, backend_text=rest, max_len=T,
+                                              lower_n_is_base=n_is_base, **choice)
+    except CT.QualityRange as e:
+        raise F.Unsupported(str(e))
+
+
+def _filtered_where_built(built):
+    """What a chunk brings along -> (buf, idx, aux, (ee, has_n) or None).  A chunk of the fused call whose filter was refused
+    (filter_error) brings no results: it goes through the --device_pack branch as any other chunk does."""
+    if len(built) == 3:
+        return built[0], built[1], built[2], None
+    buf, idx, aux, ee, has_n, err = built
+    return buf, idx, aux, ((ee, has_n) if err is None else None)
+
+
 class _DeferredContigs:
     """A chunk of pairs whose contigs are still to be built, by whoever takes it off the queue.  With --device_contigs the
     producer thread only reads and indexes: calls on one context must not overlap (include/moira_pb.h), and the consumer
-    thread is the one that filters on that context, so it makes the device contig call too."""
+    thread is the one that filters on that context, so it makes the device contig call too.  fused = (backend, filt): the
+    contigs are filtered in the same call (_chunk_contigs_filtered)."""
 
-    def __init__(self, *a):
-        self.a = a
+    def __init__(self, *a, fused=None):
+        self.a, self.fused = a, fused
 
     def build(self):
+        if self.fused is not None:
+            return _chunk_contigs_filtered(*self.a[:6], *self.fused)
         return _chunk_contigs(*self.a)
 
 
-def _fast_chunks(args, contig_engine=None):
+def _fast_chunks(args, contig_engine=None, fused=None):
     """(buf, idx, aux) per chunk: reads as they are in the file, or contigs built from the two files.  With contig_engine
-    (--device_contigs) a paired chunk comes as a _DeferredContigs instead: its consumer builds the contigs, on its own thread."""
+    (--device_contigs) a paired chunk comes as a _DeferredContigs instead: its consumer builds the contigs, on its own thread
+    (fused: and filters them in the same call, FASTQ input only)."""
     from . import fastio as F
     if not args.forward_fastq:
         yield from _fast_chunks_fasta_qual(args, contig_engine)
@@ -1010,7 +1054,7 @@ def _fast_chunks(args, contig_engine=None):
             bad = F.first_header_mismatch(fbuf, fidx, rbuf, ridx)
             n = len(fidx) if bad < 0 else bad
             if n and contig_engine is not None:
-                yield _DeferredContigs(args, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset, contig_engine)
+                yield _DeferredContigs(args, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset, contig_engine, fused=fused)
             elif n:
                 yield _chunk_contigs(args, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset)
             if bad >= 0:
@@ -1201,9 +1245,11 @@ def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs
         return lanes[k]
     ok = False
     try:
-        for chunk in _prefetched(_fast_chunks(args, backend.engine if device_contigs else None)):
-            # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context)
-            buf, idx, aux = chunk.build() if isinstance(chunk, _DeferredContigs) else chunk
+        fused = (backend, (method, fd, T, n_is_base)) if _fused_applies(device_contigs, device_pack, only, backend) else None
+        for chunk in _prefetched(_fast_chunks(args, backend.engine if device_contigs else None, fused)):
+            # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context; with
+            # --device_pack as well they are filtered where they lie, in the same call)
+            buf, idx, aux, filtered = _filtered_where_built(chunk.build() if isinstance(chunk, _DeferredContigs) else chunk)
             n = len(idx)
             lens = np.minimum(idx[:, F.SEQ_LEN], T) if T else idx[:, F.SEQ_LEN].copy()
             if not only and method == "poisson_binomial" and n and int(lens.max()) > MAX_PB_LEN:
@@ -1213,7 +1259,10 @@ def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs
             ee = np.zeros(n, np.float64)                 # --only_contig: process_data returns 0 (moira.py:809-810)
             has_n = np.zeros(n, bool)
             packed = False
-            if device_pack and not only and n:
+            if filtered is not None:
+                ee, has_n = filtered
+                packed = True
+            elif device_pack and not only and n:
                 # --device_pack: the chunk's text goes up as it lies, one call.  A ValueError (a quality character out of range, a
                 # text the entry does not take) sends the chunk through the host path below, which raises what it always raised
                 # -- or takes the chunk; the first such chunk of a run is reported, so that the switch never fails silently.

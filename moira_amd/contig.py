@@ -158,6 +158,13 @@ def _contigs_device_then_host(engine, L, fbuf, fidx, rbuf, ridx, fastq_offset, m
     rows gathered, the same slot size -- and their slots, index rows and aux rows are scattered into place."""
     res = engine.contigs_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
                               CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, rec_cap=rec_cap)
+    return _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
+                                    consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap)
+
+
+def _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
+                             consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap):
+    """The second half of _contigs_device_then_host, on the result of either device call."""
     cbuf, cidx, aux = res.cbuf, res.cidx, res.aux
     back = np.nonzero(~res.done)[0]
     if len(back):
@@ -216,3 +223,45 @@ def contigs_from_fastq(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatc
         raise QualityRange(L.mct_last_error().decode())
     _check(rc)
     return cbuf, cidx, np.ascontiguousarray(aux.T)
+
+
+def contigs_from_fastq_filtered(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatch=-1, gap=-2, insert=20, deltaq=6,
+                                consensus_qscore="best", qscore_cap=40, trim_overlap=False, threads=None, engine=None,
+                                backend_text=None, max_len=0, lower_n_is_base=False, poisson=False, **kw):
+    """contigs_from_fastq(..., engine=engine) and the filter of its contigs, with the chunk kept on the device in between
+    (Engine.contigs_filter_text) -> (cbuf, cidx, aux, ee, has_n, filter_error).  The pairs the device hands back are built by
+    the host aligner exactly as contigs_from_fastq builds them, and every pair the fused call did not filter -- those, or all
+    of them when the chunk's filter was refused -- is then filtered where the host path filters it: backend_text(cbuf, cidx, sel)
+    -> (ee, has_n) of the records sel (default: Engine.filter_text with this call's max_len, lower_n_is_base, poisson and kw).
+    Results and errors are therefore the host path's for every pair the device did not finish.  A refused filter leaves ee and
+    has_n to the caller instead: filter_error is what filter_text would have raised (else None), and nothing more is asked of
+    the device for the chunk; a ValueError of backend_text on the rest is returned the same way."""
+    L = load()
+    if consensus_qscore not in CONSENSUS:
+        raise ValueError('consensus_qscore must be "best", "sum" or "posterior".')
+    if engine is None:
+        raise ValueError("contigs_from_fastq_filtered needs an engine: the fused call has no host form")
+    fidx, ridx = np.ascontiguousarray(fidx), np.ascontiguousarray(ridx)
+    n = len(fidx)
+    threads = threads or usable_cpus()
+    rec_cap = int((fidx[:, 1] + 2 * (fidx[:, 3] + ridx[:, 3])).max()) + 8 if n else 8     # header + 2 x (l1 + l2)
+    if backend_text is None:
+        def backend_text(buf, idx, sel):
+            r = engine.filter_text(buf, idx, sel=sel, fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base,
+                                   poisson=poisson, **kw)
+            return r.ee, r.has_n
+    res = engine.contigs_filter_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
+                                     CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, rec_cap=rec_cap, max_len=max_len,
+                                     lower_n_is_base=lower_n_is_base, poisson=poisson, **kw)
+    cbuf, cidx, aux = _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
+                                               consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap)
+    ee, has_n = np.array(res.ee, np.float64), np.array(res.has_n, bool)
+    if res.filter_error is not None:
+        return cbuf, cidx, aux, ee, has_n, res.filter_error
+    rest = np.nonzero(~np.asarray(res.filtered, bool))[0]
+    if len(rest):
+        try:
+            ee[rest], has_n[rest] = backend_text(cbuf, cidx, rest)
+        except ValueError as e:                          # a host-built contig the text filter refuses: the chunk's error as well
+            return cbuf, cidx, aux, ee, has_n, e
+    return cbuf, cidx, aux, ee, has_n, None

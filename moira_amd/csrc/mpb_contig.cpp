@@ -2,6 +2,8 @@
 // validates the pair descriptors (mpb_pair_rows, mpb_hostonly.cpp), uploads both texts once, buckets the pairs by the LDS their
 // pointer matrix needs, launches k_contig (mpb_contig_kernels.hip) once per size class and brings the slots and arrays back.
 // A pair the device does not take is handed back (done = 0); the caller builds it with libmoira_contig.so.
+// mpb_contigs_filter_text_host is the same chunk call with the filter behind it: k_contig_rows hands the device's own index to
+// k_pack_text, and mpb_filter_text_host's piece loop (filter_text_pieces, mpb_text.cpp) runs over the slots where they lie.
 // (Every mpb_* function defined here has C linkage: include/moira_pb.h declares it inside extern "C".)
 
 #include "mpb_ctx.h"
@@ -32,7 +34,7 @@ struct ContigStage {
         k.take(ftext, align_up(fbytes > 0 ? fbytes : 1, 16));
         k.take(rtext, align_up(rbytes > 0 ? rbytes : 1, 16));
         k.take(rows, n); k.take(list, n);
-        k.take(out_buf, n * rec_cap); k.take(out_idx, n * 6);
+        k.take(out_buf, align_up(n * rec_cap, 16)); k.take(out_idx, n * 6);     // (a text k_pack_text may read: whole 16-byte words)
         k.take(overlap, n); k.take(gaps, n); k.take(mism, n); k.take(done, n);
         k.take(aln, aln_cap > 0 ? 2 * n * aln_cap : 1); k.take(aln_len, aln_cap > 0 ? n : 1); k.take(score, aln_cap > 0 ? n : 1);
     }
@@ -51,24 +53,38 @@ int ensure_tables(mpb_ctx *c)
     return MPB_OK;
 }
 
-}  // namespace
+// what mpb_contigs_filter_text_host asks for beyond the contigs: the filter of the slots where they lie
+struct FilterAsk {
+    int32_t max_len, lower_n_is_base; const mpb_filter_params *params; int32_t poisson;
+    double *ee; int32_t *ns; uint8_t *pass; int32_t *len_out; uint8_t *flags_out; uint8_t *filtered;
+    mpb_filter_counts *counts; int *filter_rc; int64_t *filter_bad_record;
+};
 
-int mpb_contigs_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int64_t *fidx, const char *rtext,
-                          int64_t rtext_bytes, const int64_t *ridx, int64_t n, int32_t fastq_offset,
-                          const mpb_contig_params *params, int64_t rec_cap, char *out_buf, int64_t *out_idx, int32_t *overlap,
-                          int32_t *gaps, int32_t *mismatches, uint8_t *done, char *aln_out, int64_t aln_cap,
-                          int32_t *aln_len_out, int32_t *score_out, int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record)
+// the chunk call of both entries (fa == nullptr: mpb_contigs_text_host)
+int contigs_chunk(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int64_t *fidx, const char *rtext,
+                  int64_t rtext_bytes, const int64_t *ridx, int64_t n, int32_t fastq_offset,
+                  const mpb_contig_params *params, int64_t rec_cap, char *out_buf, int64_t *out_idx, int32_t *overlap,
+                  int32_t *gaps, int32_t *mismatches, uint8_t *done, char *aln_out, int64_t aln_cap,
+                  int32_t *aln_len_out, int32_t *score_out, int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record,
+                  const FilterAsk *fa)
 {
     CTXCHK(c);
     if (bad_record) *bad_record = -1;
     if (n_done) *n_done = 0;
     if (n_handed_back) *n_handed_back = 0;
+    if (fa) {
+        if (fa->filter_rc) *fa->filter_rc = MPB_OK;
+        if (fa->filter_bad_record) *fa->filter_bad_record = -1;
+        if (fa->counts) { fa->counts->n_reads = 0; fa->counts->n_pass = 0; fa->counts->n_fail = 0; fa->counts->n_overflow = 0; }
+    }
     if (!params) return fail(MPB_E_INVALID, "params is NULL");
     if (n < 0 || ftext_bytes < 0 || rtext_bytes < 0 || rec_cap <= 0 || (ftext_bytes > 0 && !ftext) || (rtext_bytes > 0 && !rtext))
         return fail(MPB_E_INVALID, "mpb_contigs_text_host: bad arguments");
     if (n > 0x7fffffffll - 4096) return fail(MPB_E_INVALID, "chunk of %lld pairs exceeds 2^31; split it", (long long)n);
     if (n > 0 && (!fidx || !ridx || !out_buf || !out_idx || !overlap || !gaps || !mismatches || !done))
         return fail(MPB_E_INVALID, "NULL host buffer");
+    if (fa && n > 0 && (!fa->ee || !fa->ns || !fa->pass || !fa->filtered)) return fail(MPB_E_INVALID, "NULL host buffer");
+    if (fa && n > 0) memset(fa->filtered, 0, (size_t)n);
     if (aln_out && (aln_cap <= 0 || !aln_len_out || !score_out)) return fail(MPB_E_INVALID, "aln_out needs aln_cap > 0, aln_len_out and score_out");
     if (!aln_out) aln_cap = 0;
     // 1. the descriptors, validated on the host before anything is uploaded
@@ -83,6 +99,7 @@ int mpb_contigs_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, co
     if (params->deltaq <= 0) return fail(MPB_E_INVALID, "deltaq must be a positive integer");
     if (params->qscore_cap < 0) return fail(MPB_E_INVALID, "qscore_cap must be a non-negative integer");
     if (params->consensus < 0 || params->consensus > 2) return fail(MPB_E_INVALID, "consensus_qscore must be \"best\", \"sum\" or \"posterior\".");
+    if (fa && (rc = check_params(fa->params))) return rc;
     if (n == 0) return MPB_OK;
     auto mag = [](int32_t v) { return (int64_t)(v < 0 ? -(int64_t)v : v); };
     const int64_t maxabs = std::max(mag(params->match), std::max(mag(params->mismatch), mag(params->gap)));
@@ -106,9 +123,23 @@ int mpb_contigs_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, co
         return MPB_OK;
     }
     if (params->consensus == 2 && (rc = ensure_tables(c))) return rc;
-    // 4. the device block of the call
+    // 4. the device block of the call (with a filter: the text call's block too, before anything is queued -- a block that
+    // grows waits for the stream).  The row stride of the matrix is known here: no contig is longer than its pair's l1 + l2.
     ContigStage st{};
     if ((rc = carve(c, c->contig_stage, [&](Carver &k) { st.layout(k, ftext_bytes, rtext_bytes, n, rec_cap, aln_cap); }))) return rc;
+    TextStage ts{};
+    int64_t stride = 0, piece_rows = 0;
+    if (fa) {
+        int64_t longest = 0;
+        for (int64_t k = 0; k < listed; k++) {
+            const mpb_pair_row &r = rows[(size_t)list[(size_t)k]];
+            longest = std::max(longest, (int64_t)r.l1 + r.l2);
+        }
+        if (fa->max_len > 0) longest = std::min(longest, (int64_t)fa->max_len);
+        stride = align_up(std::max<int64_t>(longest, 1), 128);
+        piece_rows = text_piece_rows(n, stride);
+        if ((rc = carve(c, c->text_stage, [&](Carver &k) { ts.layout(k, 0, n, piece_rows, stride); }))) return rc;
+    }
     hipStream_t s = c->stream;
     const int64_t fcap = align_up(ftext_bytes > 0 ? ftext_bytes : 1, 16), rcap = align_up(rtext_bytes > 0 ? rtext_bytes : 1, 16);
     // (everything below is queued on one stream; the host blocks it reads from outlive the synchronisation every path passes)
@@ -136,10 +167,42 @@ int mpb_contigs_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, co
     for (int k = 0; k < k_n_class; k++) {
         if (!per_class[k]) continue;
         a.list = st.list + first[k]; a.count = per_class[k]; a.lds_cap = k_lds_class[k];
+        Span t(c, MPB_K_CONTIG);
         mpb_launch_contigs(a, s);
     }
     e = hipGetLastError();
+    // 5b. the filter of the slots where they lie: the device's own index becomes k_pack_text's descriptors (k_contig_rows, behind
+    // the launches above on the same stream), then mpb_filter_text_host's piece loop over the slot buffer.  A quality out of
+    // range or a filter call that fails leaves the contigs valid: it is reported beside them, and nothing counts as filtered.
+    int frc = MPB_OK;
+    int64_t f_pass = 0, f_overflow = 0, f_bad = -1;
+    char f_msg[MPB_ERR_LEN] = "";
+    if (fa && e == hipSuccess) {
+        { Span t(c, MPB_K_CONTIG_ROWS);
+          mpb_launch_contig_rows(st.out_idx, st.done, n, rec_cap, fa->max_len, stride, ts.rows, s); }
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            frc = filter_text_pieces(c, st.out_buf, n * rec_cap, ts.rows, n, stride, piece_rows, fastq_offset, fa->lower_n_is_base,
+                                     fa->params, fa->poisson, ts, &f_pass, &f_overflow, &f_bad);
+            if (frc != MPB_OK && frc != MPB_E_RANGE && frc != MPB_E_INVALID) return frc;      // (the stream is synchronised)
+            if (frc) { strncpy(f_msg, mpb_last_error(), sizeof(f_msg) - 1); }
+        }
+    }
+    const bool host_tail = fa && fa->poisson && !(fa->params->flags & MPB_FLAG_POISSON_DEVICE_TAIL);
+    std::vector<int32_t> len_tmp;
+    int32_t *len_host = fa ? fa->len_out : nullptr;
+    if (host_tail && !len_host) {
+        try { len_tmp.resize((size_t)n); } catch (const std::bad_alloc &) { (void)hipStreamSynchronize(s); return fail(MPB_E_NOMEM, "out of host memory"); }
+        len_host = len_tmp.data();
+    }
     // 6. the slots and arrays
+    if (fa && frc == MPB_OK) {
+        if (e == hipSuccess) e = hipMemcpyAsync(fa->ee, ts.ee, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(fa->ns, ts.ns, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && !host_tail) e = hipMemcpyAsync(fa->pass, ts.pass, (size_t)n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && len_host) e = hipMemcpyAsync(len_host, ts.len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && fa->flags_out) e = hipMemcpyAsync(fa->flags_out, ts.flags, (size_t)n, hipMemcpyDeviceToHost, s);
+    }
     if (e == hipSuccess) e = hipMemcpyAsync(out_buf, st.out_buf, (size_t)(n * rec_cap), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(out_idx, st.out_idx, (size_t)n * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(overlap, st.overlap, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
@@ -156,5 +219,58 @@ int mpb_contigs_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, co
     for (int64_t i = 0; i < n; i++) nd += done[i] != 0;
     if (n_done) *n_done = nd;
     if (n_handed_back) *n_handed_back = n - nd;
+    if (!fa) return MPB_OK;
+    // 7. the filter's outcome per pair: a pair counts as filtered when the device built it and the chunk's filter went through
+    if (frc != MPB_OK) {
+        if (fa->filter_rc) *fa->filter_rc = frc;
+        if (f_bad >= 0) {                                // a position in pair order -> in the order of the built pairs, as a
+            int64_t rank = 0;                            // mpb_filter_text_host call over them would have counted it
+            for (int64_t i = 0; i < f_bad && i < n; i++) rank += done[i] != 0;
+            f_bad = rank;
+        }
+        if (fa->filter_bad_record) *fa->filter_bad_record = f_bad;
+        (void)fail(frc, "%s", f_msg);                    // mpb_last_error() holds the filter's message
+        return MPB_OK;
+    }
+    if (host_tail) {
+        // the reference's scalar tail with the host's libm, in place: ee holds lambda (mpb_filter_text_host's arithmetic)
+        if ((rc = mpb_poisson_finish_host(fa->ee, fa->ns, len_host, 0, n, fa->params, fa->ee, fa->pass))) return rc;
+    }
+    int64_t np = 0;
+    for (int64_t i = 0; i < n; i++) {
+        fa->filtered[i] = done[i] != 0;
+        np += done[i] != 0 && fa->pass[i] != 0;
+    }
+    (void)f_pass;                                        // (the pieces' own count includes the empty rows of handed-back pairs)
+    if (fa->counts) { fa->counts->n_reads = nd; fa->counts->n_pass = np; fa->counts->n_fail = nd - np; fa->counts->n_overflow = f_overflow; }
     return MPB_OK;
+}
+
+}  // namespace
+
+int mpb_contigs_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int64_t *fidx, const char *rtext,
+                          int64_t rtext_bytes, const int64_t *ridx, int64_t n, int32_t fastq_offset,
+                          const mpb_contig_params *params, int64_t rec_cap, char *out_buf, int64_t *out_idx, int32_t *overlap,
+                          int32_t *gaps, int32_t *mismatches, uint8_t *done, char *aln_out, int64_t aln_cap,
+                          int32_t *aln_len_out, int32_t *score_out, int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record)
+{
+    return contigs_chunk(c, ftext, ftext_bytes, fidx, rtext, rtext_bytes, ridx, n, fastq_offset, params, rec_cap, out_buf, out_idx,
+                         overlap, gaps, mismatches, done, aln_out, aln_cap, aln_len_out, score_out, n_done, n_handed_back, bad_record,
+                         nullptr);
+}
+
+int mpb_contigs_filter_text_host(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int64_t *fidx, const char *rtext,
+                                 int64_t rtext_bytes, const int64_t *ridx, int64_t n, int32_t fastq_offset,
+                                 const mpb_contig_params *params, int64_t rec_cap, char *out_buf, int64_t *out_idx, int32_t *overlap,
+                                 int32_t *gaps, int32_t *mismatches, uint8_t *done, char *aln_out, int64_t aln_cap,
+                                 int32_t *aln_len_out, int32_t *score_out, int64_t *n_done, int64_t *n_handed_back, int64_t *bad_record,
+                                 int32_t max_len, int32_t lower_n_is_base, const mpb_filter_params *filter_params, int32_t poisson,
+                                 double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, uint8_t *filtered,
+                                 mpb_filter_counts *counts, int *filter_rc, int64_t *filter_bad_record)
+{
+    const FilterAsk fa{max_len, lower_n_is_base, filter_params, poisson, ee, ns, pass, len_out, flags_out, filtered, counts,
+                       filter_rc, filter_bad_record};
+    return contigs_chunk(c, ftext, ftext_bytes, fidx, rtext, rtext_bytes, ridx, n, fastq_offset, params, rec_cap, out_buf, out_idx,
+                         overlap, gaps, mismatches, done, aln_out, aln_cap, aln_len_out, score_out, n_done, n_handed_back, bad_record,
+                         &fa);
 }

@@ -12,12 +12,19 @@
 //   write   only now, when nothing can hand the pair back any more: slot, index row, the three numbers, done = 1
 // Every LDS and global index derives from lengths cd_row_ok checked against the buffer sizes and rec_cap; a descriptor it
 // refuses leaves done = 0 and touches nothing.  LDS is sized per launch (the host buckets the pairs by cd_lds_bytes).
+// Also here: k_contig_rows, which turns done[] and the index written below into k_pack_text's row descriptors, so that the
+// contigs can be filtered in the slots they were written to (mpb_contigs_filter_text_host; per pair: mpb_contig_rows.inc).
 
 #include "mpb_internal.h"
 
 #define CD_FN __device__ __forceinline__
 __device__ __forceinline__ int cd_gload8(const uint8_t *p) { return *p; }
 #include "mpb_contig_args.h"
+
+#define CR_FN __device__ __forceinline__
+__device__ __forceinline__ int cr_done(const uint8_t *done, int64_t i) { return done[i]; }
+__device__ __forceinline__ int64_t cr_idx(const int64_t *out_idx, int64_t k) { return out_idx[k]; }
+#include "mpb_contig_rows.inc"
 
 namespace {
 
@@ -137,7 +144,25 @@ __global__ __launch_bounds__(CD_LANES) void k_contig(const MpbContigArgs a)
     }
 }
 
+// k_contig_rows: done[n] + the index k_contig wrote -> the row descriptors k_pack_text walks over the slot buffer, one thread per
+// pair (mpb_contig_rows.inc).  It runs behind the k_contig launches on the same stream and reads what they wrote; rows[i] is
+// written for every i < n, whatever the index holds.
+__global__ __launch_bounds__(256) void k_contig_rows(const int64_t *__restrict__ out_idx, const uint8_t *__restrict__ done, int64_t n,
+                                                     int64_t rec_cap, int32_t max_len, int64_t stride, mpb_text_row *__restrict__ rows)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    rows[i] = cr_row(out_idx, done, i, rec_cap, max_len, stride);
+}
+
 }  // namespace
+
+void mpb_launch_contig_rows(const int64_t *out_idx, const uint8_t *done, int64_t n, int64_t rec_cap, int32_t max_len, int64_t stride,
+                            mpb_text_row *rows, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_contig_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out_idx, done, n, rec_cap, max_len, stride, rows);
+}
 
 void mpb_launch_contigs(const MpbContigArgs &a, hipStream_t s)
 {

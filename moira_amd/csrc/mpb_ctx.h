@@ -229,6 +229,29 @@ void drain_pipeline(mpb_ctx *c);
 int filter_host_pipeline(mpb_ctx *c, const uint8_t *q, int64_t n, int64_t row_stride, const int32_t *len, int32_t fixed_len,
                          const mpb_filter_params *params, double *ee, int32_t *ns, uint8_t *pass, mpb_filter_counts *counts,
                          int poisson);
+// mpb_text.cpp: the staging block of a text call (text | descriptors | status | one piece of the matrix | the results of the call)
+struct TextStage {
+    uint8_t *text; mpb_text_row *rows; int64_t *status; uint8_t *q; int32_t *len; uint8_t *flags;
+    double *ee; int32_t *ns; uint8_t *pass;
+    void layout(Carver &k, int64_t text_bytes, int64_t n, int64_t piece_rows, int64_t stride)
+    {
+        k.take(text, align_up(text_bytes > 0 ? text_bytes : 1, 16));
+        k.take(rows, n);
+        k.take(status, 2);
+        k.take(q, piece_rows * stride);
+        k.take(len, n); k.take(flags, n);
+        k.take(ee, n); k.take(ns, n); k.take(pass, n);
+    }
+};
+// the rows of one piece of the matrix for n rows of `stride` bytes (at most 256 MiB; MPB_TEXT_PIECE_BYTES: less)
+int64_t text_piece_rows(int64_t n, int64_t stride);
+// The piece loop of a text call: n rows described by d_rows over d_text (both on the device; k_pack_text's contract) are packed
+// into st.q and filtered piece by piece into st.len / flags / ee / ns / pass, with mpb_filter_text_host's three poisson forms and
+// its order of errors (a quality out of range: MPB_E_RANGE and *bad_record, a position in row order; else the first filter call
+// that failed).  The stream is synchronised when it returns, whatever it returns.
+int filter_text_pieces(mpb_ctx *c, const uint8_t *d_text, int64_t text_bytes, const mpb_text_row *d_rows, int64_t n, int64_t stride,
+                       int64_t piece_rows, int32_t fastq_offset, int32_t lower_n_is_base, const mpb_filter_params *params,
+                       int32_t poisson, const TextStage &st, int64_t *n_pass, int64_t *n_overflow, int64_t *bad_record);
 // mpb_perread.cpp: the per-read entry's resident kernel leaves (before anything is freed: the runtime waits for the whole
 // device there); ... and its stream and blocks go
 void serve_quiesce(mpb_ctx *c);

@@ -243,6 +243,9 @@ void mpb_launch_sample(const uint8_t *q, int64_t n, int64_t stride, int32_t fixe
 // k_contig (mpb_contig_kernels.hip; the arguments: mpb_contig_args.h): one wave per listed pair, lds_bytes of LDS per wave
 struct MpbContigArgs;
 void mpb_launch_contigs(const MpbContigArgs &a, hipStream_t s);
+// k_contig_rows: done[n] and k_contig's index -> the n row descriptors of k_pack_text over the slot buffer (mpb_contig_rows.inc)
+void mpb_launch_contig_rows(const int64_t *out_idx, const uint8_t *done, int64_t n, int64_t rec_cap, int32_t max_len, int64_t stride,
+                            mpb_text_row *rows, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

@@ -1,6 +1,7 @@
 // mpb_text.cpp -- FASTQ text as it lies in the file, behind the C ABI of libmoira_pb.so (include/moira_pb.h): the device pack
 // from a text buffer and its validated row descriptors (k_pack_text), and the host entry that uploads a chunk's text once,
-// packs it on the device and filters it there.  The descriptors come from mpb_text_rows (mpb_hostonly.cpp).
+// packs it on the device and filters it there.  The descriptors come from mpb_text_rows (mpb_hostonly.cpp).  The piece loop
+// (filter_text_pieces) takes a text and descriptors that are on the device already: mpb_contig.cpp runs it over contig slots.
 // (Every mpb_* function defined here has C linkage: include/moira_pb.h declares it inside extern "C".)
 
 #include "mpb_ctx.h"
@@ -44,34 +45,67 @@ int mpb_pack_text_device(mpb_ctx *c, const uint8_t *d_text, int64_t text_bytes, 
                           d_flags_out, d_status);
 }
 
-namespace {
-
-// the staging block of one mpb_filter_text_host call
-struct TextStage {
-    uint8_t *text; mpb_text_row *rows; int64_t *status; uint8_t *q; int32_t *len; uint8_t *flags;
-    double *ee; int32_t *ns; uint8_t *pass;
-    void layout(Carver &k, int64_t text_bytes, int64_t n, int64_t piece_rows, int64_t stride)
-    {
-        k.take(text, align_up(text_bytes > 0 ? text_bytes : 1, 16));
-        k.take(rows, n);
-        k.take(status, 2);
-        k.take(q, piece_rows * stride);
-        k.take(len, n); k.take(flags, n);
-        k.take(ee, n); k.take(ns, n); k.take(pass, n);
-    }
-};
-
-int64_t piece_limit()
+int64_t text_piece_rows(int64_t n, int64_t stride)
 {
     int64_t lim = MPB_TEXT_PIECE_BYTES;
     if (const char *e = getenv("MPB_TEXT_PIECE_BYTES")) {          // a smaller piece, for tests of the piece loop
         const long long v = atoll(e);
         if (v > 0 && v < lim) lim = v;
     }
-    return lim;
+    int64_t piece_rows = lim / stride;
+    if (piece_rows < 1) piece_rows = 1;
+    if (piece_rows > n) piece_rows = n;
+    return piece_rows;
 }
 
-}  // namespace
+int filter_text_pieces(mpb_ctx *c, const uint8_t *d_text, int64_t text_bytes, const mpb_text_row *d_rows, int64_t n, int64_t stride,
+                       int64_t piece_rows, int32_t fastq_offset, int32_t lower_n_is_base, const mpb_filter_params *params,
+                       int32_t poisson, const TextStage &st, int64_t *n_pass_out, int64_t *n_overflow_out, int64_t *bad_record)
+{
+    const bool device_tail = poisson && params && (params->flags & MPB_FLAG_POISSON_DEVICE_TAIL);
+    hipStream_t s = c->stream;
+    char first_err[MPB_ERR_LEN] = "";                     // the message of the first filter call that failed
+    int64_t *status = &c->pin->text_status[0];
+    status[0] = status[1] = INT64_MAX;
+    // (everything below is queued on one stream; the host blocks it reads from -- the pinned words -- outlive the synchronisation
+    // that every path out of here passes)
+    const hipError_t e_up = hipMemcpyAsync(st.status, status, 2 * sizeof(int64_t), hipMemcpyHostToDevice, s);
+    if (e_up != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (text upload)", e_up); }
+    // piece by piece: pack, look at the status, filter where the piece lies.  The status holds positions in row order (each piece
+    // is packed with its first row's position as the base), and the pieces come in that order: the first piece that leaves it
+    // dirty holds the first bad record, and nothing after it is packed or filtered.  mio_pack's error would have come before any
+    // filter's: when a filter call fails, the pieces after it are still packed (not filtered) so that a bad quality there is seen.
+    int rc = MPB_OK;
+    int64_t n_pass = 0, n_overflow = 0;
+    bool dirty = false;
+    for (int64_t lo = 0; lo < n && !dirty; lo += piece_rows) {
+        const int64_t m = n - lo < piece_rows ? n - lo : piece_rows;
+        const int prc = pack_text_rows(c, d_text, text_bytes, d_rows + lo, m, lo, fastq_offset, lower_n_is_base, stride, st.q,
+                                       st.len + lo, st.flags + lo, st.status);
+        if (prc) { (void)hipStreamSynchronize(s); return prc; }
+        const hipError_t e_st = hipMemcpyAsync(status, st.status, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
+        const hipError_t e_sync = hipStreamSynchronize(s);
+        HIPCHK_KEPT("hipMemcpyAsync (status)", e_st);
+        HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+        dirty = status[0] != INT64_MAX || status[1] != INT64_MAX;
+        if (dirty || rc != MPB_OK) continue;
+        mpb_filter_counts pc{};
+        if (!poisson) rc = mpb_filter_device(c, st.q, m, stride, st.len + lo, 0, params, st.ee + lo, st.ns + lo, st.pass + lo, &pc);
+        else if (device_tail) rc = mpb_filter_poisson_device(c, st.q, m, stride, st.len + lo, 0, params, st.ee + lo, st.ns + lo, st.pass + lo, nullptr, &pc);
+        else rc = mpb_poisson_lambda_device(c, st.q, m, stride, st.len + lo, 0, st.ee + lo, st.ns + lo);     // (the host tail runs later)
+        if (rc != MPB_OK) { strncpy(first_err, mpb_last_error(), sizeof(first_err) - 1); continue; }
+        n_pass += pc.n_pass; n_overflow += pc.n_overflow;
+    }
+    if (dirty) {
+        const int64_t first = status[0] < status[1] ? status[0] : status[1];
+        if (bad_record) *bad_record = first;
+        if (status[0] == first) return fail(MPB_E_RANGE, "Qualities must have positive values.");
+        return fail(MPB_E_RANGE, "quality exceeds the encodable maximum 254");
+    }
+    if (rc) { (void)hipStreamSynchronize(s); return fail(rc, "%s", first_err); }
+    *n_pass_out = n_pass; *n_overflow_out = n_overflow;
+    return MPB_OK;
+}
 
 int mpb_filter_text_host(mpb_ctx *c, const char *text, int64_t text_bytes, const int64_t *idx, int64_t n_records,
                          const int64_t *sel, int64_t n, int32_t fastq_offset, int32_t max_len, int32_t lower_n_is_base,
@@ -102,53 +136,20 @@ int mpb_filter_text_host(mpb_ctx *c, const char *text, int64_t text_bytes, const
     std::vector<mpb_text_row> rows;
     try { rows.resize((size_t)n); } catch (const std::bad_alloc &) { return fail(MPB_E_NOMEM, "out of host memory for %lld row descriptors", (long long)n); }
     if ((rc = mpb_text_rows(idx, n_records, sel, n, text_bytes, max_len, stride, rows.data(), nullptr, bad_record))) return rc;
-    int64_t piece_rows = piece_limit() / stride;
-    if (piece_rows < 1) piece_rows = 1;
-    if (piece_rows > n) piece_rows = n;
+    const int64_t piece_rows = text_piece_rows(n, stride);
     TextStage st{};
     if ((rc = carve(c, c->text_stage, [&](Carver &k) { st.layout(k, text_bytes, n, piece_rows, stride); }))) return rc;
     hipStream_t s = c->stream;
-    char first_err[MPB_ERR_LEN] = "";                     // the message of the first filter call that failed
-    int64_t *status = &c->pin->text_status[0];
-    status[0] = status[1] = INT64_MAX;
-    // (everything below is queued on one stream; the host blocks it reads from -- the caller's text, `rows`, the pinned words --
-    // outlive the synchronisation that every path out of here passes)
+    // (everything below is queued on one stream; the host blocks it reads from -- the caller's text, `rows` -- outlive the
+    // synchronisation that every path out of here passes)
     hipError_t e_up = hipSuccess;
     if (text_bytes > 0) e_up = hipMemcpyAsync(st.text, text, (size_t)text_bytes, hipMemcpyHostToDevice, s);
     if (e_up == hipSuccess) e_up = hipMemcpyAsync(st.rows, rows.data(), (size_t)n * sizeof(mpb_text_row), hipMemcpyHostToDevice, s);
-    if (e_up == hipSuccess) e_up = hipMemcpyAsync(st.status, status, 2 * sizeof(int64_t), hipMemcpyHostToDevice, s);
     if (e_up != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (text upload)", e_up); }
-    // 5. piece by piece: pack, look at the status, filter where the piece lies.  The status holds positions in sel order (each piece
-    // is packed with its first row's position as the base), and the pieces come in that order: the first piece that leaves it
-    // dirty holds the first bad record, and nothing after it is packed or filtered.  mio_pack's error would have come before any
-    // filter's: when a filter call fails, the pieces after it are still packed (not filtered) so that a bad quality there is seen.
+    // 5. the piece loop (above)
     int64_t n_pass = 0, n_overflow = 0;
-    bool dirty = false;
-    for (int64_t lo = 0; lo < n && !dirty; lo += piece_rows) {
-        const int64_t m = n - lo < piece_rows ? n - lo : piece_rows;
-        const int prc = pack_text_rows(c, st.text, text_bytes, st.rows + lo, m, lo, fastq_offset, lower_n_is_base, stride, st.q,
-                                       st.len + lo, st.flags + lo, st.status);
-        if (prc) { (void)hipStreamSynchronize(s); return prc; }
-        const hipError_t e_st = hipMemcpyAsync(status, st.status, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-        const hipError_t e_sync = hipStreamSynchronize(s);
-        HIPCHK_KEPT("hipMemcpyAsync (status)", e_st);
-        HIPCHK_KEPT("hipStreamSynchronize", e_sync);
-        dirty = status[0] != INT64_MAX || status[1] != INT64_MAX;
-        if (dirty || rc != MPB_OK) continue;
-        mpb_filter_counts pc{};
-        if (!poisson) rc = mpb_filter_device(c, st.q, m, stride, st.len + lo, 0, params, st.ee + lo, st.ns + lo, st.pass + lo, &pc);
-        else if (device_tail) rc = mpb_filter_poisson_device(c, st.q, m, stride, st.len + lo, 0, params, st.ee + lo, st.ns + lo, st.pass + lo, nullptr, &pc);
-        else rc = mpb_poisson_lambda_device(c, st.q, m, stride, st.len + lo, 0, st.ee + lo, st.ns + lo);     // (the host tail runs below)
-        if (rc != MPB_OK) { strncpy(first_err, mpb_last_error(), sizeof(first_err) - 1); continue; }
-        n_pass += pc.n_pass; n_overflow += pc.n_overflow;
-    }
-    if (dirty) {
-        const int64_t first = status[0] < status[1] ? status[0] : status[1];
-        if (bad_record) *bad_record = first;
-        if (status[0] == first) return fail(MPB_E_RANGE, "Qualities must have positive values.");
-        return fail(MPB_E_RANGE, "quality exceeds the encodable maximum 254");
-    }
-    if (rc) return fail(rc, "%s", first_err);
+    if ((rc = filter_text_pieces(c, st.text, text_bytes, st.rows, n, stride, piece_rows, fastq_offset, lower_n_is_base, params, poisson,
+                                 st, &n_pass, &n_overflow, bad_record))) return rc;
     // the results, whole
     hipError_t e_out = hipMemcpyAsync(ee, st.ee, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e_out == hipSuccess) e_out = hipMemcpyAsync(ns, st.ns, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);

@@ -139,6 +139,19 @@ class ContigResult:
             setattr(self, k, v)
 
 
+class ContigFilterResult(ContigResult):
+    """What Engine.contigs_filter_text returns: ContigResult's fields, and the filter's results where the contigs lie -- ee, ns,
+    passed, lens, has_n per pair (defined where filtered is True), n_pass / n_overflow over the filtered pairs, and filter_error:
+    None, or the ValueError Engine.filter_text would have raised over the built pairs (.bad_record), not raised."""
+    __slots__ = ("ee", "ns", "passed", "lens", "has_n", "filtered", "n_pass", "n_overflow", "filter_error")
+
+    def __init__(self, contigs, *a):
+        for k in ContigResult.__slots__:
+            setattr(self, k, getattr(contigs, k))
+        for k, v in zip(ContigFilterResult.__slots__, a):
+            setattr(self, k, v)
+
+
 def check_host_batch(q, lens, fixed_len, out, limit):
     """Argument checks shared by every host-batch entry (one GPU or several): -> (q, n, stride, lens, (ee, ns, ps)).
     `limit`: longest read the method takes (None: as long as the row)."""
@@ -340,12 +353,13 @@ class Engine:
         return pair_rows(fidx, ridx, ftext_bytes, rtext_bytes, rec_cap)
 
     def contigs_text(self, fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatch=-1, gap=-2, insert=20, deltaq=6,
-                     consensus=0, qscore_cap=40, trim_overlap=False, rec_cap=None, alignments=False):
+                     consensus=0, qscore_cap=40, trim_overlap=False, rec_cap=None, alignments=False, filter=None):
         """Contigs of a chunk of paired records that are still FASTQ text, built on the device (mpb_contigs_text_host; consensus
         0 best, 1 sum, 2 posterior) -> ContigResult: cbuf / cidx / aux as moira_amd.contig.contigs_from_fastq returns them and
         done (bool per pair).  Slot, index row and aux row of a pair with done == False are undefined: the device handed it
         back and the host aligner builds it (contigs_from_fastq(..., engine=...) does).  alignments=True also returns the
-        aligned strings and scores (aln uint8[n, 2, aln_cap], aln_len, score)."""
+        aligned strings and scores (aln uint8[n, 2, aln_cap], aln_len, score).
+        filter: what contigs_filter_text hands on (the one marshalling of a chunk serves both entries); not for callers."""
         fidx, ridx = np.ascontiguousarray(fidx, np.int64), np.ascontiguousarray(ridx, np.int64)
         if fidx.ndim != 2 or fidx.shape[1] != 6 or fidx.shape != ridx.shape:
             raise ValueError("fidx and ridx must be (n x 6) int64 record indexes of the same length")
@@ -365,15 +379,57 @@ class Engine:
         prm = L.ContigParams(int(match), int(mismatch), int(gap), int(insert), int(deltaq), int(consensus), int(qscore_cap),
                              1 if trim_overlap else 0)
         n_done, n_back, bad = C.c_int64(0), C.c_int64(0), C.c_int64(-1)
-        rc = self.lib.mpb_contigs_text_host(self.ctx, faddr, fbytes, fidx.ctypes.data, raddr, rbytes, ridx.ctypes.data, n,
-                                            int(fastq_offset), C.byref(prm), int(rec_cap), cbuf.ctypes.data, cidx.ctypes.data,
-                                            aux[0].ctypes.data, aux[1].ctypes.data, aux[2].ctypes.data, done.ctypes.data,
-                                            aln.ctypes.data if alignments else None, aln_cap,
-                                            aln_len.ctypes.data if alignments else None, score.ctypes.data if alignments else None,
-                                            C.byref(n_done), C.byref(n_back), C.byref(bad))
+        chunk = (self.ctx, faddr, fbytes, fidx.ctypes.data, raddr, rbytes, ridx.ctypes.data, n,
+                 int(fastq_offset), C.byref(prm), int(rec_cap), cbuf.ctypes.data, cidx.ctypes.data,
+                 aux[0].ctypes.data, aux[1].ctypes.data, aux[2].ctypes.data, done.ctypes.data,
+                 aln.ctypes.data if alignments else None, aln_cap,
+                 aln_len.ctypes.data if alignments else None, score.ctypes.data if alignments else None,
+                 C.byref(n_done), C.byref(n_back), C.byref(bad))
+        if filter is None:
+            rc = self.lib.mpb_contigs_text_host(*chunk)
+        else:
+            max_len, lower_n_is_base, poisson, params, (ee, ns, ps, lens, flags) = filter
+            filtered = np.zeros(n, np.uint8)
+            counts, frc, fbad = L.FilterCounts(), C.c_int(0), C.c_int64(-1)
+            rc = self.lib.mpb_contigs_filter_text_host(*chunk, int(max_len), 1 if lower_n_is_base else 0, C.byref(params),
+                                                       1 if poisson else 0, ee.ctypes.data, ns.ctypes.data, ps.ctypes.data,
+                                                       lens.ctypes.data, flags.ctypes.data, filtered.ctypes.data, C.byref(counts),
+                                                       C.byref(frc), C.byref(fbad))
         del fkeep, rkeep
         _check_text(rc, bad)
-        return ContigResult(cbuf, cidx, np.ascontiguousarray(aux.T), done.view(bool), rec_cap, n_done.value, n_back.value, aln, aln_len, score)
+        res = ContigResult(cbuf, cidx, np.ascontiguousarray(aux.T), done.view(bool), rec_cap, n_done.value, n_back.value, aln, aln_len, score)
+        if filter is None:
+            return res
+        err = None
+        if frc.value:
+            try:
+                _check_text(frc.value, fbad)
+            except ValueError as e:
+                err = e
+        return ContigFilterResult(res, ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), filtered.view(bool),
+                                  counts.n_pass, counts.n_overflow, err)
+
+    def contigs_filter_text(self, fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatch=-1, gap=-2, insert=20, deltaq=6,
+                            consensus=0, qscore_cap=40, trim_overlap=False, rec_cap=None, alignments=False, max_len=0,
+                            lower_n_is_base=False, poisson=False, out=None, **kw):
+        """contigs_text and filter_text in one call that keeps the chunk on the device (mpb_contigs_filter_text_host): the contigs
+        are built, then packed and filtered in the slots they were written to, and everything comes back at the end ->
+        ContigFilterResult.  For the pairs with filtered == True (the pairs the device built, unless the chunk's filter was
+        refused) ee / ns / passed / lens / has_n are those of filter_text(cbuf, cidx, sel=those pairs), bit for bit; for the
+        others they are undefined and the caller filters them once the host has built them (moira_amd.contig.
+        contigs_from_fastq_filtered does).  max_len, lower_n_is_base, poisson, out and `kw` as filter_text's.  What filter_text
+        would have raised for the chunk is returned as filter_error (with .bad_record), not raised: the contigs are valid."""
+        params = kw.pop("params", None) or self.params(**kw)
+        n = len(fidx)
+        if out is None:
+            out = np.empty(n, np.float64), np.empty(n, np.int32), np.empty(n, np.uint8), np.empty(n, np.int32), np.empty(n, np.uint8)
+        ee, ns, ps, lens, flags = out
+        if (ee.dtype, ns.dtype, ps.dtype, lens.dtype, flags.dtype) != (np.float64, np.int32, np.uint8, np.int32, np.uint8) or \
+                not all(a.flags.c_contiguous and len(a) >= n for a in out):
+            raise ValueError("out must be contiguous (float64, int32, uint8, int32, uint8) arrays of at least n entries")
+        return self.contigs_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq, consensus, qscore_cap,
+                                 trim_overlap, rec_cap=rec_cap, alignments=alignments,
+                                 filter=(max_len, lower_n_is_base, poisson, params, out))
 
     def decode_ascii_device(self, d_seq, d_qual, n, stride, d_out, d_len=None, fixed_len=0, fastq_offset=33,
                             d_err=None):
@@ -552,7 +608,7 @@ class Engine:
     def kernel_times(self):
         """{name: (total_ms, launches)} since the last reset (synchronises)."""
         out = {}
-        for kid, name in L.KERNEL_NAMES.items():
+        for kid, name in list(L.KERNEL_NAMES.items()) + list(L.CONTIG_KERNEL_NAMES.items()):
             ms, cnt = C.c_double(), C.c_int64()
             L.check(self.lib.mpb_kernel_time(self.ctx, kid, C.byref(ms), C.byref(cnt)))
             out[name] = (ms.value, cnt.value)
