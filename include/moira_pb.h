@@ -153,7 +153,10 @@ extern "C" {
 #define MPB_K_PACK_TEXT 11   /* FASTQ text + record index -> the packed ragged matrix (k_pack_text) */
 #define MPB_K_CONTIG    12   /* paired-read contigs: the launches of one chunk, one per size class (k_contig) */
 #define MPB_K_CONTIG_ROWS 13 /* the device's contig index -> k_pack_text's row descriptors (k_contig_rows) */
-#define MPB_K_COUNT     14
+#define MPB_K_BGZF_DEFLATE 14 /* .gz output on the device: one raw-deflate stream per BGZF member (k_bgzf_deflate) */
+#define MPB_K_BGZF_SCAN  15  /* ... the prefix of the members' sizes (k_bgzf_scan) */
+#define MPB_K_BGZF_FRAME 16  /* ... header, stream and trailer of every member into the dense output (k_bgzf_frame) */
+#define MPB_K_COUNT     17
 
 typedef struct mpb_ctx mpb_ctx;
 
@@ -520,6 +523,34 @@ int mpb_contigs_filter_text_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_
                                  int32_t max_len, int32_t lower_n_is_base, const mpb_filter_params *filter_params, int32_t poisson,
                                  double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, uint8_t *filtered,
                                  mpb_filter_counts *counts, int *filter_rc, int64_t *filter_bad_record);
+
+/*
+ * .gz output on the device (opt-in; the default compressor stays the host's zlib).  The text is cut into BGZF members (SAM/BAM
+ * specification section 4.1: gzip members that state their size in a 'B','C' extra field) of at most MPB_BGZF_DATA text bytes,
+ * each its own window, and every member is compressed by one workgroup (k_bgzf_deflate, csrc/mpb_bgzf_kernels.hip): LZ77 with
+ * a hash table in LDS (matches of 3..258 bytes at distances up to 32768, confined to the member; greedy parse), then whichever
+ * of a dynamic-Huffman, a fixed-Huffman and a stored block is shortest.  The output is a function of the text alone: the same
+ * text gives the same bytes on every call.  k_bgzf_scan and k_bgzf_frame put header (18 bytes, BSIZE = stream + 25), stream and
+ * trailer (CRC-32 and ISIZE; the CRC is computed on the host while the kernels run) of all members behind each other, and that
+ * dense stream is what is copied back.
+ *
+ * mpb_bgzf_bound (host only): *out_cap = text_bytes + 31 * ceil(text_bytes / MPB_BGZF_DATA), every member stored.
+ * mpb_bgzf_compress_host: the members of text[0 .. text_bytes) in order into out, WITHOUT the format's end marker (the writer
+ * appends it when it closes the file); *out_bytes = their length.  out_cap must be at least the bound (MPB_E_INVALID otherwise,
+ * as for a NULL out / out_bytes or a NULL text with text_bytes > 0).  text_bytes == 0 gives zero members and *out_bytes = 0.
+ * stats (may be NULL) receives the counts of the call.  A call of more than 1024 members (65,280 KiB of text) is cut into pieces
+ * of 1024 members inside the call (environment MPB_BGZF_PIECE_MEMBERS: fewer, 1 .. 1024, for tests of the piece loop); per piece
+ * the device holds about 447 MiB (text, 4 bytes of token per text byte, the slots, the framed output).  The blocks belong to
+ * the context and grow on demand.  Synchronous.
+ */
+#define MPB_BGZF_DATA 0xff00
+typedef struct mpb_bgzf_stats {
+    int64_t members, dynamic, fixed, stored;       /* members = dynamic + fixed + stored: the block type each member got */
+    int64_t literals, matches, matched_bytes;      /* tokens over all members; literals + matched_bytes = text_bytes */
+} mpb_bgzf_stats;
+int mpb_bgzf_bound(int64_t text_bytes, int64_t *out_cap);
+int mpb_bgzf_compress_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, uint8_t *out, int64_t out_cap,
+                           int64_t *out_bytes, mpb_bgzf_stats *stats);
 
 /*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is

@@ -33,6 +33,9 @@ KERNEL_NAMES = {K_PREPASS: "prepass", K_SCAN: "scan", K_SCATTER: "scatter", K_DP
                 K_PACK_TEXT: "pack_text"}
 K_CONTIG, K_CONTIG_ROWS = 12, 13     # MPB_K_CONTIG (k_contig, one span per size class), MPB_K_CONTIG_ROWS (k_contig_rows)
 CONTIG_KERNEL_NAMES = {K_CONTIG: "contig", K_CONTIG_ROWS: "contig_rows"}     # the paired pipeline's kernels, beside the filter's
+K_BGZF_DEFLATE, K_BGZF_SCAN, K_BGZF_FRAME = 14, 15, 16     # MPB_K_BGZF_*: .gz output on the device (k_bgzf_deflate / _scan / _frame)
+BGZF_KERNEL_NAMES = {K_BGZF_DEFLATE: "bgzf_deflate", K_BGZF_SCAN: "bgzf_scan", K_BGZF_FRAME: "bgzf_frame"}
+BGZF_DATA = 0xff00             # MPB_BGZF_DATA: text bytes per BGZF member
 
 
 class MoiraPBError(RuntimeError):
@@ -72,6 +75,11 @@ class PairRow(C.Structure):
 class ContigParams(C.Structure):
     """mpb_contig_params (consensus: 0 best, 1 sum, 2 posterior)."""
     _fields_ = [(k, C.c_int32) for k in ("match", "mismatch", "gap", "insert", "deltaq", "consensus", "qscore_cap", "trim_overlap")]
+
+
+class BgzfStats(C.Structure):
+    """mpb_bgzf_stats: the counts of one mpb_bgzf_compress_host call."""
+    _fields_ = [(k, C.c_int64) for k in ("members", "dynamic", "fixed", "stored", "literals", "matches", "matched_bytes")]
 
 
 CONTIG_MAX_LEN = 384           # MPB_CONTIG_MAX_LEN: the longest read of a pair the device contig builder takes
@@ -115,6 +123,8 @@ PROTOTYPES = {
                                                _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.c_int32, C.c_int32, C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                                C.POINTER(FilterCounts), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "mpb_bgzf_bound": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "mpb_bgzf_compress_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(BgzfStats)]),
     "mpb_encode_ascii_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP]),
     "mpb_decode_classify_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
                                              C.POINTER(FilterParams), _VP, _VP, _VP, _VP, _VP]),

@@ -243,6 +243,13 @@ def build_parser():
                         "at a time. Results and output files are identical. Where it does not apply (fasta+qual input, the line "
                         "parser, several GPUs, no GPU) one line says so and host packing is used. With --device_contigs as well, "
                         "the contigs of a paired chunk are packed and filtered where the device built them, in the same call.")
+    f.add_argument("--device_compress", action="store_true",
+                   help="(not in moira.py) with -oc gz on one GPU: compress the .gz outputs on the device (BGZF members of 65,280 "
+                        "text bytes, one workgroup each, batches of 16 MiB of text per call on a context of its own) instead of "
+                        "with zlib on the host's threads. Every file decompresses to the same bytes; the compressed bytes differ "
+                        "(greedy parse, one member as the window: measured once on the golden reads, " + DEVICE_COMPRESS_MEASURED +
+                        "). Where it does not apply (no -oc gz, the line parser, several GPUs, no GPU) one line says so and host "
+                        "zlib is used; a batch the device does not take is compressed on the host, with one message.")
     return p
 
 
@@ -779,6 +786,42 @@ def bgzf_compress(data, level=4):
     return b"".join(out)
 
 
+# what tools/device_bgzf_rate.py measured once (profiles/device_bgzf_rate.json), quoted by --device_compress's help
+DEVICE_COMPRESS_MEASURED = ("0.98 / 0.75 / 1.05 of zlib level 4's bytes for fastq / fasta / qual text, and 3.8 to 5.4 GB/s of text in "
+                            "memory against 1.9 to 2.7 GB/s on 16 host threads; one pair of runs on 268 MB of FASTQ took 0.75 s either way")
+
+
+class DeviceCompressor:
+    """The one device compressor of a run (--device_compress): a second Engine on the filter's device, for compression only --
+    calls on one context must not overlap, and the writers' pool threads run beside the filtering thread -- behind a lock.  All
+    .gz writers of the run share it."""
+
+    def __init__(self, device, say=None):
+        import threading
+        from .engine import Engine
+        self.engine = Engine(device)
+        self.lock = threading.Lock()
+        self.say = say
+        self.reported = False
+
+    def compress(self, data):
+        with self.lock:
+            return self.engine.bgzf_compress(data)
+
+    def report(self, e):
+        """A batch went through host zlib after all: said once per run (as --device_pack's refused chunks are)."""
+        with self.lock:
+            first, self.reported = not self.reported, True
+        if first and self.say is not None:
+            self.say("--device_compress: the device did not take a batch (%s): host zlib is used for it." % e)
+
+    def close(self):
+        with self.lock:
+            if self.engine is not None:
+                self.engine.close()
+                self.engine = None
+
+
 class _BlockCompressedWriter:
     """A .gz output written as a sequence of independently compressed blocks (gzip members: the format defines the
     concatenation of valid files as a valid file, and gzip / zcat / Python 2 and 3 read it as one), so that the blocks are
@@ -788,9 +831,15 @@ class _BlockCompressedWriter:
     write() cuts its data into 1 MiB blocks, hands them to a pool and writes out, in order, whatever has finished; at
     most `WINDOW` blocks are in flight.  One compressor thread per file is what bounds a run with compressed output
     otherwise: ~60 MB/s of text per file at gzip level 4.  A .gz output is BGZF (bgzf_compress: each 1 MiB block becomes
-    17 members, the file ends with the format's end marker), so it can also be READ on several threads."""
+    17 members, the file ends with the format's end marker), so it can also be READ on several threads.
+    With a `compressor` (--device_compress: an object with compress(data) -> the BGZF members of data, and optionally
+    report(exception)) the 1 MiB blocks of a .gz output are collected into batches of BATCH_BLOCKS and one call is made per
+    batch, from a pool thread as before; the batch is compressed as one text, so its members are full ones but the last.  A call
+    that raises makes the batch go through bgzf_compress block by block.  Order, back-pressure (at most WINDOW blocks in flight)
+    and the end marker are the same."""
     BLOCK = 1 << 20
     WINDOW = 64
+    BATCH_BLOCKS = 16                                           # 16 MiB of text per device call
     _pool = None
 
     @classmethod
@@ -801,10 +850,12 @@ class _BlockCompressedWriter:
             cls._pool = ThreadPoolExecutor(max(2, min(usable_cpus(), 32)))
         return cls._pool
 
-    def __init__(self, path, kind):
+    def __init__(self, path, kind, compressor=None):
         import collections
         self.f = open(path, "wb")
         self.kind = kind
+        self.compressor = compressor if kind == "gz" else None
+        self.batch = []                                         # blocks waiting for their batch to fill (compressor only)
         self.carry = b""
         self.inflight = collections.deque()
         self.wrote = False
@@ -822,12 +873,32 @@ class _BlockCompressedWriter:
             return bgzf_compress(block, 4)                      # level 4: same content, ~4x the speed of level 9
         return self.bz.compress(block)                          # (tasks of the one-thread pool run in submission order)
 
+    def _pack_batch(self, blocks):
+        try:
+            return self.compressor.compress(b"".join(blocks))
+        except Exception as e:                                  # the device did not take it: the host's members, said once
+            report = getattr(self.compressor, "report", None)
+            if report is not None:
+                report(e)
+            return b"".join(bgzf_compress(b, 4) for b in blocks)
+
     def _drain(self, keep):
         while len(self.inflight) > keep:
             self.f.write(self.inflight.popleft().result())      # in order; waits for the oldest block only
             self.wrote = True
 
+    def _flush_batch(self):
+        if self.batch:
+            blocks, self.batch = self.batch, []
+            self.inflight.append(self.pool().submit(self._pack_batch, blocks))
+            self._drain(max(1, self.WINDOW // self.BATCH_BLOCKS))
+
     def _submit(self, block):
+        if self.compressor is not None:
+            self.batch.append(block)
+            if len(self.batch) >= self.BATCH_BLOCKS:
+                self._flush_batch()
+            return
         self.inflight.append((self.own or self.pool()).submit(self._pack, block))
         self._drain(self.WINDOW)
 
@@ -856,6 +927,7 @@ class _BlockCompressedWriter:
             if self.carry:
                 self._submit(self.carry)
                 self.carry = b""
+            self._flush_batch()                                 # (a partial batch)
             self._drain(0)
             if self.kind == "gz":
                 self.f.write(BGZF_EOF)                          # (also what makes an empty output a valid archive)
@@ -866,10 +938,10 @@ class _BlockCompressedWriter:
             self.f = None
 
 
-def _open_outputs(args, output_name, binary=False):
+def _open_outputs(args, output_name, binary=False, compressor=None):
     mode = "wb" if binary else "wt"
     if args.output_compression == "gz":
-        opener, suffix = (lambda p: _BlockCompressedWriter(p, "gz") if binary else gzip.open(p, mode, compresslevel=4)), ".gz"
+        opener, suffix = (lambda p: _BlockCompressedWriter(p, "gz", compressor) if binary else gzip.open(p, mode, compresslevel=4)), ".gz"
     elif args.output_compression == "bz2":
         opener, suffix = (lambda p: _BlockCompressedWriter(p, "bz2") if binary else bz2.open(p, mode)), ".bz2"
     else:
@@ -934,6 +1006,12 @@ def _fast_eligible(args, backend):
 def _device_pack_eligible(args, backend):
     """--device_pack applies to a run the byte-level path takes, FASTQ input, on a backend that packs text on its device."""
     return bool(args.forward_fastq and getattr(backend, "text", None) is not None and 0 <= args.fastq_offset <= 255)
+
+
+def _device_compress_eligible(args, backend):
+    """--device_compress applies to a run with -oc gz that the byte-level path takes, on a GPU backend with one device."""
+    eng = getattr(backend, "engine", None)
+    return bool(args.output_compression == "gz" and eng is not None and hasattr(eng, "bgzf_compress") and hasattr(eng, "device"))
 
 
 def _record_error(which, e, args):
@@ -1430,9 +1508,18 @@ def main(args, backend=None, out=None, _no_fastio=False):
         if not args.nowarnings:
             say("--device_contigs does not apply to this run (it takes paired input through the byte-level parser on one GPU): "
                 "the host aligner is used.")
+    compressor = None
+    if bool(getattr(args, "device_compress", False)):
+        if fast and _device_compress_eligible(args, backend):
+            compressor = DeviceCompressor(backend.engine.device, None if args.nowarnings else say)
+        elif not args.nowarnings:
+            say("--device_compress does not apply to this run (it takes -oc gz output of the byte-level parser on one GPU): "
+                "host zlib is used.")
     try:
-        o = _open_outputs(args, output_name, binary=fast)
+        o = _open_outputs(args, output_name, binary=fast, compressor=compressor)
     except IOError as e:
+        if compressor is not None:
+            compressor.close()
         say(str(e))
         say()
         return 1
@@ -1476,6 +1563,9 @@ def main(args, backend=None, out=None, _no_fastio=False):
             except fastio.Unsupported:
                 # content the byte-level parser does not reproduce: start over with the line parser
                 _close(o)
+                if compressor is not None:
+                    compressor.close()
+                    compressor = None
                 return main(args, backend=backend, out=out, _no_fastio=True)
         else:
             for rec in parse:
@@ -1519,6 +1609,8 @@ def main(args, backend=None, out=None, _no_fastio=False):
         return 1
     finally:
         _close(o)
+        if compressor is not None:
+            compressor.close()
     return 0
 
 

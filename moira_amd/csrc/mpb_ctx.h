@@ -175,6 +175,7 @@ struct mpb_ctx {
     Buf contig_stage{BUF_DEVICE};        // mpb_contigs_text_host: both texts | descriptors | class lists | the slots and arrays of the call
     Buf contig_tabs{BUF_DEVICE};         // ... and the two posterior tables, uploaded by the first posterior call
     bool contig_tabs_ready = false;
+    Buf bgzf_stage{BUF_DEVICE};          // mpb_bgzf_compress_host: one piece of text | tokens | slots | sizes | offsets | CRCs | the framed output
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)

@@ -686,3 +686,74 @@ int mpb_shard_bounds(int64_t n, int32_t world, int32_t rank, int64_t *lo, int64_
     *hi = *lo + base + (rank < rem ? 1 : 0);
     return MPB_OK;
 }
+
+// ---- .gz output on the device: the host's share (the bound, and the CRC-32 of every member while the kernels run) -----------------
+int mpb_bgzf_bound(int64_t text_bytes, int64_t *out_cap)
+{
+    if (text_bytes < 0 || !out_cap) return fail(MPB_E_INVALID, "mpb_bgzf_bound: bad arguments");
+    if (text_bytes > (int64_t)1 << 56) return fail(MPB_E_INVALID, "mpb_bgzf_bound: %lld bytes of text", (long long)text_bytes);
+    const int64_t members = (text_bytes + MPB_BGZF_DATA - 1) / MPB_BGZF_DATA;
+    *out_cap = text_bytes + 31 * members;                  // every member stored: 18 + 5 + text + 8
+    return MPB_OK;
+}
+
+namespace {
+struct BgzfCrcTables {                                     // RFC 1952 section 8, eight bytes per step
+    uint32_t t[8][256];
+    BgzfCrcTables()
+    {
+        for (uint32_t i = 0; i < 256; i++) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; k++) c = (c & 1) ? 0xedb88320u ^ (c >> 1) : c >> 1;
+            t[0][i] = c;
+        }
+        for (uint32_t i = 0; i < 256; i++)
+            for (int k = 1; k < 8; k++) t[k][i] = t[0][t[k - 1][i] & 0xff] ^ (t[k - 1][i] >> 8);
+    }
+};
+const BgzfCrcTables g_bgzf_crc;
+
+uint32_t bgzf_crc32(const uint8_t *p, size_t n)
+{
+    uint32_t c = 0xffffffffu;
+    while (n >= 8) {
+        uint64_t v;
+        memcpy(&v, p, 8);
+        v ^= c;
+        c = g_bgzf_crc.t[7][v & 0xff] ^ g_bgzf_crc.t[6][(v >> 8) & 0xff] ^ g_bgzf_crc.t[5][(v >> 16) & 0xff] ^
+            g_bgzf_crc.t[4][(v >> 24) & 0xff] ^ g_bgzf_crc.t[3][(v >> 32) & 0xff] ^ g_bgzf_crc.t[2][(v >> 40) & 0xff] ^
+            g_bgzf_crc.t[1][(v >> 48) & 0xff] ^ g_bgzf_crc.t[0][v >> 56];
+        p += 8; n -= 8;
+    }
+    while (n--) c = g_bgzf_crc.t[0][(c ^ *p++) & 0xff] ^ (c >> 8);
+    return ~c;
+}
+}  // namespace
+
+void bgzf_member_crcs(const uint8_t *text, int64_t text_bytes, int64_t n_members, uint32_t *crc_out)
+{
+    auto run = [=](int64_t lo, int64_t hi) {
+        for (int64_t m = lo; m < hi; m++) {
+            const int64_t off = m * (int64_t)MPB_BGZF_DATA;
+            const int64_t len = text_bytes - off < (int64_t)MPB_BGZF_DATA ? text_bytes - off : (int64_t)MPB_BGZF_DATA;
+            crc_out[m] = bgzf_crc32(text + off, (size_t)len);
+        }
+    };
+    const int threads = n_members >= 32 ? staging_threads() : 1;
+    if (threads <= 1) { run(0, n_members); return; }
+    std::vector<std::thread> th;
+    const int64_t per = (n_members + threads - 1) / threads;
+    int64_t taken = per < n_members ? per : n_members;     // helpers take [per, taken); the rest is done here
+    try {
+        th.reserve((size_t)threads);
+        for (int t = 1; t < threads; t++) {
+            const int64_t lo = per * t, hi = lo + per < n_members ? lo + per : n_members;
+            if (lo >= n_members) break;
+            th.emplace_back(run, lo, hi);
+            taken = hi;
+        }
+    } catch (...) { }                                      // no more threads to be had: this one does what is left
+    run(0, per < n_members ? per : n_members);
+    if (taken < n_members) run(taken, n_members);
+    for (auto &t : th) t.join();
+}

@@ -37,6 +37,9 @@ int64_t pipeline_chunk_reads(int64_t n, int64_t row_stride);
 int poisson_finish_marked(const mpb_filter_params *p, const int32_t *ns, const int32_t *len, int32_t fixed_len, int64_t n,
                           double *ee, uint8_t *pass, int64_t *n_marked);
 
+// CRC-32 of every BGZF member of a text (member m = bytes [m * MPB_BGZF_DATA, ...)), on a few threads
+void bgzf_member_crcs(const uint8_t *text, int64_t text_bytes, int64_t n_members, uint32_t *crc_out);
+
 bool parse_cpulist(const char *s, cpu_set_t *set, int *count);
 int staging_threads();
 void parallel_copy(void *dst, const void *src, size_t bytes, int threads);

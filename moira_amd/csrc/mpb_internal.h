@@ -246,6 +246,18 @@ void mpb_launch_contigs(const MpbContigArgs &a, hipStream_t s);
 // k_contig_rows: done[n] and k_contig's index -> the n row descriptors of k_pack_text over the slot buffer (mpb_contig_rows.inc)
 void mpb_launch_contig_rows(const int64_t *out_idx, const uint8_t *done, int64_t n, int64_t rec_cap, int32_t max_len, int64_t stride,
                             mpb_text_row *rows, hipStream_t s);
+// .gz output on the device (mpb_bgzf_kernels.hip): a member's slot holds its raw-deflate stream, at most MPB_BGZF_DATA + 5 bytes
+// (a stored block), written in whole 32-bit words
+#define MPB_BGZF_SLOT 65536
+// k_bgzf_deflate: one workgroup per member of text[text_bytes] (the allocation rounded up to 16 bytes) -> slots[m][MPB_BGZF_SLOT],
+// size[m], mstat[m][4] = {block type, literals, matches, matched bytes}; tok[m][MPB_BGZF_DATA] is its token scratch
+void mpb_launch_bgzf_deflate(const uint8_t *text, int64_t text_bytes, int64_t n_members, uint32_t *tok, uint8_t *slots,
+                             uint32_t *size, uint32_t *mstat, hipStream_t s);
+// k_bgzf_scan: off[0 .. n_members] = the exclusive prefix of size + 26 (one block)
+void mpb_launch_bgzf_scan(const uint32_t *size, int64_t n_members, int64_t *off, hipStream_t s);
+// k_bgzf_frame: header, stream and trailer (crc[m], ISIZE) of every member, dense, into out[out_cap]
+void mpb_launch_bgzf_frame(const uint8_t *slots, const uint32_t *size, const int64_t *off, const uint32_t *crc, int64_t text_bytes,
+                           int64_t n_members, int64_t out_cap, uint8_t *out, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

@@ -598,6 +598,27 @@ class Engine:
         return {"narrow_rows": info.narrow_rows, "sampled": bool(info.sampled), "n_fallback": info.n_fallback,
                 "sample_hist": list(info.sample_hist), "narrow_split": info.narrow_split, "narrow_waves": info.narrow_waves}
 
+    # ---- .gz output on the device -----------------------------------------------------------------
+    def bgzf_compress(self, data):
+        """`data` (bytes-like) as BGZF members compressed on the device (mpb_bgzf_compress_host: k_bgzf_deflate, k_bgzf_scan,
+        k_bgzf_frame), in order, WITHOUT the format's end marker -- the bytes moira_amd.cli.bgzf_compress returns differ (another
+        deflate), what they inflate to does not.  The counts of the call: bgzf_stats()."""
+        mv = memoryview(data).cast("B")
+        n = len(mv)
+        src = np.frombuffer(mv, np.uint8) if n else np.empty(0, np.uint8)
+        cap = C.c_int64()
+        L.check(self.lib.mpb_bgzf_bound(n, C.byref(cap)))
+        out = np.empty(max(cap.value, 1), np.uint8)
+        got, st = C.c_int64(), L.BgzfStats()
+        L.check(self.lib.mpb_bgzf_compress_host(self.ctx, src.ctypes.data if n else None, n, out.ctypes.data, cap.value,
+                                                C.byref(got), C.byref(st)))
+        self._bgzf_stats = {k: int(getattr(st, k)) for k, _ in L.BgzfStats._fields_}
+        return out[:got.value].tobytes()
+
+    def bgzf_stats(self):
+        """{members, dynamic, fixed, stored, literals, matches, matched_bytes} of the last bgzf_compress call (None before one)."""
+        return getattr(self, "_bgzf_stats", None)
+
     # ---- measurement ----------------------------------------------------------------------------
     def timing(self, on=True):
         L.check(self.lib.mpb_timing_enable(self.ctx, 1 if on else 0))
@@ -608,7 +629,7 @@ class Engine:
     def kernel_times(self):
         """{name: (total_ms, launches)} since the last reset (synchronises)."""
         out = {}
-        for kid, name in list(L.KERNEL_NAMES.items()) + list(L.CONTIG_KERNEL_NAMES.items()):
+        for kid, name in list(L.KERNEL_NAMES.items()) + list(L.CONTIG_KERNEL_NAMES.items()) + list(L.BGZF_KERNEL_NAMES.items()):
             ms, cnt = C.c_double(), C.c_int64()
             L.check(self.lib.mpb_kernel_time(self.ctx, kid, C.byref(ms), C.byref(cnt)))
             out[name] = (ms.value, cnt.value)
