@@ -156,7 +156,8 @@ extern "C" {
 #define MPB_K_BGZF_DEFLATE 14 /* .gz output on the device: one raw-deflate stream per BGZF member (k_bgzf_deflate) */
 #define MPB_K_BGZF_SCAN  15  /* ... the prefix of the members' sizes (k_bgzf_scan) */
 #define MPB_K_BGZF_FRAME 16  /* ... header, stream and trailer of every member into the dense output (k_bgzf_frame) */
-#define MPB_K_COUNT     17
+#define MPB_K_BGZF_INFLATE 17 /* BGZF .gz input on the device: one member per wave (k_bgzf_inflate) */
+#define MPB_K_COUNT     18
 
 typedef struct mpb_ctx mpb_ctx;
 
@@ -551,6 +552,59 @@ typedef struct mpb_bgzf_stats {
 int mpb_bgzf_bound(int64_t text_bytes, int64_t *out_cap);
 int mpb_bgzf_compress_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, uint8_t *out, int64_t out_cap,
                            int64_t *out_bytes, mpb_bgzf_stats *stats);
+
+/*
+ * BGZF .gz input on the device (opt-in; the default inflater stays the host's, libmoira_io's mio_bgzf_inflate_mt, which is also
+ * the only code that defines an error).  BGZF members are independent and at most 64 KiB each way, so every member is inflated by
+ * one wave (k_bgzf_inflate, csrc/mpb_inflate_kernels.hip): its whole text in LDS, the compressed bytes staged through a small LDS
+ * ring, the Huffman tables built by the lanes together.  The device takes a SUBSET of what the host decoder takes: a member it
+ * does not take is handed back (done[k] = 0, why[k] says where it stopped) and the caller inflates that member on the host.
+ *
+ * mpb_bgzf_member_rows (host only, no context): the VALIDATED row of every member -- the only place offsets are trusted from.
+ * in[in_len] holds the members; offs / sizes / out_offs[n + 1] are the arrays mio_bgzf_scan fills (member k is in[offs[k],
+ * offs[k] + sizes[k]), its text goes to bytes [out_offs[k], out_offs[k + 1]) of the output).  Per member the gzip header is parsed
+ * here: magic, CM = 8, FLG = FEXTRA only, XLEN, the walk of the subfields to 'B','C' with a 2-byte value, BSIZE + 1 == sizes[k],
+ * stream and trailer inside the member, ISIZE == out_offs[k + 1] - out_offs[k] and within 0 .. 65536.  rows_out[k] gets the
+ * stream's place in `in`, the text's place in the output and both lengths, crc_out[k] the trailer's CRC-32.  A member that
+ * cannot be vouched for gets out_len = -1 and why_out[k] = MPB_BGZF_WHY_HEADER (why_out may be NULL) -- never an error return.
+ * MPB_E_INVALID is for the arguments: a NULL array, n or in_len negative, out_offs decreasing or starting below 0, a member
+ * that does not lie inside in.
+ *
+ * mpb_bgzf_inflate_host: rows as above, then pieces of at most 4096 consecutive members (environment
+ * MPB_BGZF_INFLATE_PIECE_MEMBERS: fewer, 1 .. 4096, for tests of the piece loop) whose compressed bytes are one contiguous range
+ * of `in` of at most 4096 * 65536 bytes: that range and the rows are uploaded, k_bgzf_inflate runs, status, counters and the
+ * piece's text range come back; then the CRC-32 of every taken member's text is computed on a few host threads and compared with
+ * its trailer's.  done[k] = 1 only when the device took member k and CRC and length match; bytes of out that belong to a member
+ * with done[k] = 0 are unspecified.  why (may be NULL) receives MPB_BGZF_WHY_* per member.  out_cap must be at least out_offs[n].
+ * A problem in a member's content never fails the call.  stats (may be NULL) receives the counts of the call.  The device blocks
+ * belong to the context and grow on demand (a piece of 4096 full members: 256 MiB each way).  Synchronous.
+ */
+#define MPB_BGZF_WHY_OK 0
+#define MPB_BGZF_WHY_HEADER 1            /* mpb_bgzf_member_rows could not vouch for the member */
+#define MPB_BGZF_WHY_BLOCK_TYPE 2        /* BTYPE 3 */
+#define MPB_BGZF_WHY_STORED_LENGTH 3     /* LEN != ~NLEN */
+#define MPB_BGZF_WHY_CODE_LENGTH_CODE 4  /* the code-length code is over-subscribed or incomplete, or a pattern without a code was met */
+#define MPB_BGZF_WHY_REPEAT 5            /* repeat code 16 first, or a run past HLIT + HDIST */
+#define MPB_BGZF_WHY_TREE 6              /* HLIT / HDIST too large, no end-of-block code, an over-subscribed or incomplete code */
+#define MPB_BGZF_WHY_SYMBOL 7            /* a literal/length pattern without a code, or symbol 286 / 287 */
+#define MPB_BGZF_WHY_DISTANCE 8          /* a distance pattern without a code, symbol 30 / 31, or a distance before the member's start */
+#define MPB_BGZF_WHY_OVERRUN 9           /* more text than ISIZE */
+#define MPB_BGZF_WHY_SHORT 10            /* the final block ended with less text than ISIZE */
+#define MPB_BGZF_WHY_TRUNCATED 11        /* the stream ended inside a block */
+#define MPB_BGZF_WHY_TRAILING_BYTES 12   /* bytes between the final block and the trailer */
+#define MPB_BGZF_WHY_CRC 13              /* the text's CRC-32 is not the trailer's */
+typedef struct mpb_bgzf_member_row { int64_t stream_off, out_off; int32_t stream_len, out_len; } mpb_bgzf_member_row;   /* 24 bytes */
+typedef struct mpb_bgzf_inflate_stats {
+    int64_t members, taken, handed_back;             /* members = taken + handed_back */
+    int64_t stored_blocks, fixed_blocks, dynamic_blocks;   /* of the taken members, as are the counts below */
+    int64_t literals, matches, matched_bytes;
+    int64_t longest_code;                            /* the longest code length of any Huffman code built */
+} mpb_bgzf_inflate_stats;
+int mpb_bgzf_member_rows(const uint8_t *in, int64_t in_len, const int64_t *offs, const int32_t *sizes, const int64_t *out_offs,
+                         int64_t n, mpb_bgzf_member_row *rows_out, uint32_t *crc_out, uint8_t *why_out);
+int mpb_bgzf_inflate_host(mpb_ctx *ctx, const uint8_t *in, int64_t in_len, const int64_t *offs, const int32_t *sizes,
+                          const int64_t *out_offs, int64_t n, uint8_t *out, int64_t out_cap, uint8_t *done, uint8_t *why,
+                          mpb_bgzf_inflate_stats *stats);
 
 /*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is

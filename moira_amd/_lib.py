@@ -35,6 +35,10 @@ K_CONTIG, K_CONTIG_ROWS = 12, 13     # MPB_K_CONTIG (k_contig, one span per size
 CONTIG_KERNEL_NAMES = {K_CONTIG: "contig", K_CONTIG_ROWS: "contig_rows"}     # the paired pipeline's kernels, beside the filter's
 K_BGZF_DEFLATE, K_BGZF_SCAN, K_BGZF_FRAME = 14, 15, 16     # MPB_K_BGZF_*: .gz output on the device (k_bgzf_deflate / _scan / _frame)
 BGZF_KERNEL_NAMES = {K_BGZF_DEFLATE: "bgzf_deflate", K_BGZF_SCAN: "bgzf_scan", K_BGZF_FRAME: "bgzf_frame"}
+K_BGZF_INFLATE = 17             # MPB_K_BGZF_INFLATE: BGZF .gz input on the device (k_bgzf_inflate)
+INFLATE_KERNEL_NAMES = {K_BGZF_INFLATE: "bgzf_inflate"}
+BGZF_WHY = ("ok", "header", "block type", "stored length", "code-length code", "repeat", "tree", "symbol", "distance", "overrun",
+            "short", "truncated", "trailing bytes", "crc")     # MPB_BGZF_WHY_*
 BGZF_DATA = 0xff00             # MPB_BGZF_DATA: text bytes per BGZF member
 
 
@@ -82,6 +86,17 @@ class BgzfStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("members", "dynamic", "fixed", "stored", "literals", "matches", "matched_bytes")]
 
 
+class BgzfMemberRow(C.Structure):
+    """mpb_bgzf_member_row: one validated member descriptor of k_bgzf_inflate (24 bytes)."""
+    _fields_ = [("stream_off", C.c_int64), ("out_off", C.c_int64), ("stream_len", C.c_int32), ("out_len", C.c_int32)]
+
+
+class BgzfInflateStats(C.Structure):
+    """mpb_bgzf_inflate_stats: the counts of one mpb_bgzf_inflate_host call."""
+    _fields_ = [(k, C.c_int64) for k in ("members", "taken", "handed_back", "stored_blocks", "fixed_blocks", "dynamic_blocks",
+                                         "literals", "matches", "matched_bytes", "longest_code")]
+
+
 CONTIG_MAX_LEN = 384           # MPB_CONTIG_MAX_LEN: the longest read of a pair the device contig builder takes
 
 # name -> (restype, argtypes): every symbol include/moira_pb.h declares
@@ -125,6 +140,9 @@ PROTOTYPES = {
                                                C.POINTER(FilterCounts), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mpb_bgzf_bound": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
     "mpb_bgzf_compress_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(BgzfStats)]),
+    "mpb_bgzf_member_rows": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
+    "mpb_bgzf_inflate_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
+                                        C.POINTER(BgzfInflateStats)]),
     "mpb_encode_ascii_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP]),
     "mpb_decode_classify_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
                                              C.POINTER(FilterParams), _VP, _VP, _VP, _VP, _VP]),

@@ -250,6 +250,12 @@ def build_parser():
                         "(greedy parse, one member as the window: measured once on the golden reads, " + DEVICE_COMPRESS_MEASURED +
                         "). Where it does not apply (no -oc gz, the line parser, several GPUs, no GPU) one line says so and host "
                         "zlib is used; a batch the device does not take is compressed on the host, with one message.")
+    f.add_argument("--device_inflate", action="store_true",
+                   help="(not in moira.py) BGZF .gz input (bgzip, Illumina's writers, this package's own .gz outputs) on one GPU: "
+                        "inflate the members on the device (one wave per member, on a context of its own that --device_compress "
+                        "shares) instead of on the host's threads. A member the device does not take is inflated on the host, so "
+                        "errors and output files are identical. Where it does not apply (no .gz input, the line parser, several "
+                        "GPUs, no GPU) one line says so and the host inflater is used. " + DEVICE_INFLATE_MEASURED)
     return p
 
 
@@ -398,10 +404,10 @@ class _ReadAhead:
         self.fh.close()
 
 
-def open_input_binary(filename, threads=1):
+def open_input_binary(filename, threads=1, inflater=None):
     """Same sniffing, bytes out: the C parser (moira_amd/fastio.py) takes whole blocks.  `threads`: what a BGZF-blocked
     gzip file (bgzip, Illumina's writers, this package's own .gz outputs) is inflated on; any other gzip file is one
-    stream on one thread."""
+    stream on one thread.  `inflater` (--device_inflate): what inflates the BGZF members instead (fastio.GzipReader)."""
     with io.open(filename, "rb") as fh:
         start = fh.read(3)
     if start.startswith(b"\x42\x5a\x68"):
@@ -411,7 +417,7 @@ def open_input_binary(filename, threads=1):
         if os.environ.get("MOIRA_ZLIB_INPUT"):
             return _ReadAhead(gzip.open(filename, "rb"))
         from . import fastio as F
-        return _ReadAhead(F.GzipReader(io.open(filename, "rb", buffering=0), threads=threads))
+        return _ReadAhead(F.GzipReader(io.open(filename, "rb", buffering=0), threads=threads, inflater=inflater))
     return io.open(filename, "rb", buffering=0)
 
 
@@ -794,7 +800,7 @@ DEVICE_COMPRESS_MEASURED = ("0.98 / 0.75 / 1.05 of zlib level 4's bytes for fast
 class DeviceCompressor:
     """The one device compressor of a run (--device_compress): a second Engine on the filter's device, for compression only --
     calls on one context must not overlap, and the writers' pool threads run beside the filtering thread -- behind a lock.  All
-    .gz writers of the run share it."""
+    .gz writers of the run share it, and so does the run's DeviceInflater (--device_inflate)."""
 
     def __init__(self, device, say=None):
         import threading
@@ -820,6 +826,46 @@ class DeviceCompressor:
             if self.engine is not None:
                 self.engine.close()
                 self.engine = None
+
+
+# what tools/device_bgzf_inflate_rate.py measured once (profiles/device_bgzf_inflate_rate.json), quoted by --device_inflate's help
+DEVICE_INFLATE_MEASURED = ("Measured once on the golden reads tiled to 256 MiB: 4.7 GB/s of text against 14.5 GB/s on 16 host threads (the "
+                           "kernel alone 7.0 GB/s), and a run of 468,752 reads took 0.84 s with the switch, 0.61 s without: the host "
+                           "inflater is the faster one, and no rate is promised.")
+
+
+class DeviceInflater:
+    """The one device inflater of a run (--device_inflate), as fastio.GzipReader calls it: the two files of a paired run inflate on
+    two read-ahead threads beside the filtering thread, so the run owns ONE auxiliary Engine behind ONE lock for inflating -- the
+    DeviceCompressor's (`share`) when --device_compress is on as well, else a second Engine on the filter's device of its own."""
+
+    def __init__(self, device, say=None, share=None):
+        import threading
+        self.owner = share is None
+        if share is not None:
+            self.engine, self.lock = share.engine, share.lock
+        else:
+            from .engine import Engine
+            self.engine, self.lock = Engine(device), threading.Lock()
+        self.say = say
+        self.reported = False
+
+    def __call__(self, data, offs, sizes, out_offs, out):
+        with self.lock:
+            return self.engine.bgzf_inflate(data, offs, sizes, out_offs, out=out)[1]
+
+    def report(self, e):
+        """A batch went through the host inflater after all: said once per run."""
+        with self.lock:
+            first, self.reported = not self.reported, True
+        if first and self.say is not None:
+            self.say("--device_inflate: the device did not take a batch (%s): the host inflater is used for it." % e)
+
+    def close(self):
+        with self.lock:
+            if self.owner and self.engine is not None:
+                self.engine.close()
+            self.engine = None
 
 
 class _BlockCompressedWriter:
@@ -1014,6 +1060,22 @@ def _device_compress_eligible(args, backend):
     return bool(args.output_compression == "gz" and eng is not None and hasattr(eng, "bgzf_compress") and hasattr(eng, "device"))
 
 
+def _device_inflate_eligible(args, backend):
+    """--device_inflate applies to a run with a gzip input that the byte-level path takes, on a GPU backend with one device."""
+    eng = getattr(backend, "engine", None)
+    if eng is None or not hasattr(eng, "bgzf_inflate") or not hasattr(eng, "device"):
+        return False
+    for name in (args.forward_fastq, args.reverse_fastq, args.forward_fasta, args.forward_qual, args.reverse_fasta, args.reverse_qual):
+        if name:
+            try:
+                with io.open(name, "rb") as fh:
+                    if fh.read(3) == b"\x1f\x8b\x08":
+                        return True
+            except IOError:
+                pass
+    return False
+
+
 def _record_error(which, e, args):
     """The exception the line parser raises for a record that fails its checks (moira.py:1178-1195;
     the reverse file's empty-line errors name the forward header and file, as there)."""
@@ -1114,7 +1176,7 @@ def _fast_chunks(args, contig_engine=None, fused=None):
         yield from _fast_chunks_fasta_qual(args, contig_engine)
         return
     if not args.paired:
-        fh = open_input_binary(args.forward_fastq, _text_threads(args))
+        fh = open_input_binary(args.forward_fastq, _text_threads(args), getattr(args, "_inflater", None))
         try:
             for buf, idx in F.FastqChunks(fh, CHUNK_READS, threads=_text_threads(args)):
                 yield buf, idx, None
@@ -1124,7 +1186,8 @@ def _fast_chunks(args, contig_engine=None, fused=None):
             fh.close()
         return
     half = max(1, _text_threads(args) // 2)
-    ffh, rfh = open_input_binary(args.forward_fastq, half), open_input_binary(args.reverse_fastq, half)
+    inflater = getattr(args, "_inflater", None)
+    ffh, rfh = open_input_binary(args.forward_fastq, half, inflater), open_input_binary(args.reverse_fastq, half, inflater)
     try:
         # reading + indexing the two files runs one chunk ahead of contig construction, on a thread of its own
         for fbuf, fidx, rbuf, ridx in _prefetched(iter(F.PairedFastqChunks(ffh, rfh, PAIR_CHUNK_READS, threads=_text_threads(args))), depth=1):
@@ -1234,13 +1297,14 @@ def _fast_chunks_fasta_qual(args, contig_engine=None):
     mio_fasta_qual_index, so that the rest of the path is the FASTQ one."""
     from . import fastio as F
     half = max(1, _text_threads(args) // 2)
-    files = [open_input_binary(args.forward_fasta, half), open_input_binary(args.forward_qual, half)]
+    inflater = getattr(args, "_inflater", None)
+    files = [open_input_binary(args.forward_fasta, half, inflater), open_input_binary(args.forward_qual, half, inflater)]
     try:
         if not args.paired:
             for buf, idx in F.FastaQualChunks(files[0], files[1], CHUNK_READS):
                 yield buf, idx, None
             return
-        files += [open_input_binary(args.reverse_fasta, half), open_input_binary(args.reverse_qual, half)]
+        files += [open_input_binary(args.reverse_fasta, half, inflater), open_input_binary(args.reverse_qual, half, inflater)]
         fwd = iter(F.FastaQualChunks(files[0], files[1], PAIR_CHUNK_READS))
         rev = iter(F.FastaQualChunks(files[2], files[3], PAIR_CHUNK_READS))
         while True:
@@ -1515,9 +1579,19 @@ def main(args, backend=None, out=None, _no_fastio=False):
         elif not args.nowarnings:
             say("--device_compress does not apply to this run (it takes -oc gz output of the byte-level parser on one GPU): "
                 "host zlib is used.")
+    inflater = None
+    if bool(getattr(args, "device_inflate", False)):
+        if fast and _device_inflate_eligible(args, backend):
+            inflater = DeviceInflater(backend.engine.device, None if args.nowarnings else say, share=compressor)
+        elif not args.nowarnings:
+            say("--device_inflate does not apply to this run (it takes .gz input of the byte-level parser on one GPU): "
+                "the host inflater is used.")
+    args._inflater = inflater
     try:
         o = _open_outputs(args, output_name, binary=fast, compressor=compressor)
     except IOError as e:
+        if inflater is not None:
+            inflater.close()
         if compressor is not None:
             compressor.close()
         say(str(e))
@@ -1563,9 +1637,13 @@ def main(args, backend=None, out=None, _no_fastio=False):
             except fastio.Unsupported:
                 # content the byte-level parser does not reproduce: start over with the line parser
                 _close(o)
+                if inflater is not None:
+                    inflater.close()
+                    inflater = None
                 if compressor is not None:
                     compressor.close()
                     compressor = None
+                args._inflater = None
                 return main(args, backend=backend, out=out, _no_fastio=True)
         else:
             for rec in parse:
@@ -1609,8 +1687,11 @@ def main(args, backend=None, out=None, _no_fastio=False):
         return 1
     finally:
         _close(o)
+        if inflater is not None:
+            inflater.close()
         if compressor is not None:
             compressor.close()
+        args._inflater = None
     return 0
 
 

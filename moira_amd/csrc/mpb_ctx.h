@@ -176,6 +176,7 @@ struct mpb_ctx {
     Buf contig_tabs{BUF_DEVICE};         // ... and the two posterior tables, uploaded by the first posterior call
     bool contig_tabs_ready = false;
     Buf bgzf_stage{BUF_DEVICE};          // mpb_bgzf_compress_host: one piece of text | tokens | slots | sizes | offsets | CRCs | the framed output
+    Buf inflate_stage{BUF_DEVICE};       // mpb_bgzf_inflate_host: one piece of compressed bytes | rows | status rows | the piece's text
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)

@@ -712,6 +712,7 @@ struct BgzfCrcTables {                                     // RFC 1952 section 8
     }
 };
 const BgzfCrcTables g_bgzf_crc;
+}  // namespace
 
 uint32_t bgzf_crc32(const uint8_t *p, size_t n)
 {
@@ -728,7 +729,6 @@ uint32_t bgzf_crc32(const uint8_t *p, size_t n)
     while (n--) c = g_bgzf_crc.t[0][(c ^ *p++) & 0xff] ^ (c >> 8);
     return ~c;
 }
-}  // namespace
 
 void bgzf_member_crcs(const uint8_t *text, int64_t text_bytes, int64_t n_members, uint32_t *crc_out)
 {
@@ -756,4 +756,48 @@ void bgzf_member_crcs(const uint8_t *text, int64_t text_bytes, int64_t n_members
     run(0, per < n_members ? per : n_members);
     if (taken < n_members) run(taken, n_members);
     for (auto &t : th) t.join();
+}
+
+// ---- BGZF .gz input on the device: the validated rows (the only place a member's offsets are trusted from) ------------------------
+int mpb_bgzf_member_rows(const uint8_t *in, int64_t in_len, const int64_t *offs, const int32_t *sizes, const int64_t *out_offs,
+                         int64_t n, mpb_bgzf_member_row *rows_out, uint32_t *crc_out, uint8_t *why_out)
+{
+    if (n < 0 || in_len < 0 || !out_offs || (n > 0 && (!in || !offs || !sizes || !rows_out || !crc_out)))
+        return fail(MPB_E_INVALID, "mpb_bgzf_member_rows: bad arguments");
+    if (out_offs[0] < 0) return fail(MPB_E_INVALID, "mpb_bgzf_member_rows: out_offs[0] = %lld", (long long)out_offs[0]);
+    for (int64_t k = 0; k < n; k++) {
+        if (out_offs[k + 1] < out_offs[k])
+            return fail(MPB_E_INVALID, "mpb_bgzf_member_rows: out_offs decreases at member %lld", (long long)k);
+        if (offs[k] < 0 || sizes[k] < 0 || offs[k] > in_len - (int64_t)sizes[k])
+            return fail(MPB_E_INVALID, "mpb_bgzf_member_rows: member %lld (offset %lld, %d bytes) does not lie inside the %lld bytes of input",
+                        (long long)k, (long long)offs[k], (int)sizes[k], (long long)in_len);
+    }
+    for (int64_t k = 0; k < n; k++) {
+        mpb_bgzf_member_row &r = rows_out[k];
+        r.stream_off = 0; r.out_off = out_offs[k]; r.stream_len = 0; r.out_len = -1;
+        crc_out[k] = 0;
+        if (why_out) why_out[k] = MPB_BGZF_WHY_HEADER;
+        const uint8_t *p = in + offs[k];
+        const int64_t size = sizes[k];
+        if (size < 12 + 6 + 8 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) continue;
+        const int64_t xlen = p[10] | (p[11] << 8), xend = 12 + xlen;
+        if (xend + 8 > size) continue;                       // the extra field, then at least the trailer
+        int64_t bsize = -1;
+        for (int64_t q = 12; q + 4 <= xend;) {               // the first 'B','C' subfield with a 2-byte value, as mio_bgzf_scan reads it
+            const int64_t slen = p[q + 2] | (p[q + 3] << 8);
+            if (p[q] == 'B' && p[q + 1] == 'C' && slen == 2 && q + 6 <= xend) { bsize = p[q + 4] | (p[q + 5] << 8); break; }
+            q += 4 + slen;
+        }
+        if (bsize < 0 || bsize + 1 != size) continue;
+        const uint8_t *t = p + size - 8;
+        const uint32_t crc = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
+        const int64_t isize = t[4] | (t[5] << 8) | (t[6] << 16) | ((int64_t)t[7] << 24);
+        if (isize > 65536 || isize != out_offs[k + 1] - out_offs[k]) continue;
+        r.stream_off = offs[k] + xend;
+        r.stream_len = (int32_t)(size - xend - 8);
+        r.out_len = (int32_t)isize;
+        crc_out[k] = crc;
+        if (why_out) why_out[k] = MPB_BGZF_WHY_OK;
+    }
+    return MPB_OK;
 }

@@ -38,6 +38,7 @@ int poisson_finish_marked(const mpb_filter_params *p, const int32_t *ns, const i
                           double *ee, uint8_t *pass, int64_t *n_marked);
 
 // CRC-32 of every BGZF member of a text (member m = bytes [m * MPB_BGZF_DATA, ...)), on a few threads
+uint32_t bgzf_crc32(const uint8_t *p, size_t n);          // RFC 1952 section 8, eight bytes per step
 void bgzf_member_crcs(const uint8_t *text, int64_t text_bytes, int64_t n_members, uint32_t *crc_out);
 
 bool parse_cpulist(const char *s, cpu_set_t *set, int *count);

@@ -258,6 +258,12 @@ void mpb_launch_bgzf_scan(const uint32_t *size, int64_t n_members, int64_t *off,
 // k_bgzf_frame: header, stream and trailer (crc[m], ISIZE) of every member, dense, into out[out_cap]
 void mpb_launch_bgzf_frame(const uint8_t *slots, const uint32_t *size, const int64_t *off, const uint32_t *crc, int64_t text_bytes,
                            int64_t n_members, int64_t out_cap, uint8_t *out, hipStream_t s);
+// BGZF .gz input on the device (mpb_inflate_kernels.hip).  k_bgzf_inflate: one wave per member of rows[n_members] over in[in_bytes]
+// (a 256-byte aligned block) -> its text at text + out_off (text[text_bytes]) when taken, and mstat[m][MPB_INFLATE_MSTAT] =
+// {why, stored / fixed / dynamic blocks, literals, matches, matched bytes, longest code}; the rows are checked again in the kernel
+#define MPB_INFLATE_MSTAT 8
+void mpb_launch_bgzf_inflate(const uint8_t *in, int64_t in_bytes, const mpb_bgzf_member_row *rows, int64_t n_members, uint8_t *text,
+                             int64_t text_bytes, uint32_t *mstat, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

@@ -619,6 +619,38 @@ class Engine:
         """{members, dynamic, fixed, stored, literals, matches, matched_bytes} of the last bgzf_compress call (None before one)."""
         return getattr(self, "_bgzf_stats", None)
 
+    # ---- BGZF .gz input on the device --------------------------------------------------------------
+    def bgzf_inflate(self, data, offs, sizes, out_offs, out=None):
+        """The BGZF members of `data` (bytes-like; member k = data[offs[k] : offs[k] + sizes[k]], its text at out_offs[k] ..
+        out_offs[k + 1] -- the arrays libmoira_io's mio_bgzf_scan fills) inflated on the device (mpb_bgzf_inflate_host:
+        k_bgzf_inflate, one wave per member, then the CRC-32 check on the host).  Returns (text, done, why) as uint8 arrays:
+        done[k] = 1 where member k was taken and its CRC and length match, else 0 with why[k] one of MPB_BGZF_WHY_* (names:
+        _lib.BGZF_WHY) -- the bytes of such a member in `text` are unspecified and the caller inflates it on the host.  `out`: a
+        uint8 array of at least out_offs[-1] bytes to write into.  The counts of the call: bgzf_inflate_stats()."""
+        src = data if isinstance(data, np.ndarray) else np.frombuffer(memoryview(data).cast("B"), np.uint8)
+        offs = np.ascontiguousarray(offs, np.int64)
+        sizes = np.ascontiguousarray(sizes, np.int32)
+        out_offs = np.ascontiguousarray(out_offs, np.int64)
+        n = len(offs)
+        if src.dtype != np.uint8 or not src.flags.c_contiguous or len(sizes) != n or len(out_offs) != n + 1:
+            raise ValueError("bgzf_inflate: data must be contiguous bytes, sizes as long as offs, out_offs one longer")
+        total = int(out_offs[n])
+        if out is None:
+            out = np.empty(max(total, 1), np.uint8)
+        elif out.dtype != np.uint8 or not out.flags.c_contiguous or len(out) < total:
+            raise ValueError("bgzf_inflate: out must be a contiguous uint8 array of at least %d bytes" % total)
+        done, why, st = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8), L.BgzfInflateStats()
+        L.check(self.lib.mpb_bgzf_inflate_host(self.ctx, src.ctypes.data, len(src), offs.ctypes.data, sizes.ctypes.data,
+                                               out_offs.ctypes.data, n, out.ctypes.data, len(out), done.ctypes.data, why.ctypes.data,
+                                               C.byref(st)))
+        self._bgzf_inflate_stats = {k: int(getattr(st, k)) for k, _ in L.BgzfInflateStats._fields_}
+        return out[:total], done[:n], why[:n]
+
+    def bgzf_inflate_stats(self):
+        """{members, taken, handed_back, stored_blocks, fixed_blocks, dynamic_blocks, literals, matches, matched_bytes,
+        longest_code} of the last bgzf_inflate call (None before one)."""
+        return getattr(self, "_bgzf_inflate_stats", None)
+
     # ---- measurement ----------------------------------------------------------------------------
     def timing(self, on=True):
         L.check(self.lib.mpb_timing_enable(self.ctx, 1 if on else 0))
@@ -629,7 +661,8 @@ class Engine:
     def kernel_times(self):
         """{name: (total_ms, launches)} since the last reset (synchronises)."""
         out = {}
-        for kid, name in list(L.KERNEL_NAMES.items()) + list(L.CONTIG_KERNEL_NAMES.items()) + list(L.BGZF_KERNEL_NAMES.items()):
+        for kid, name in (list(L.KERNEL_NAMES.items()) + list(L.CONTIG_KERNEL_NAMES.items()) + list(L.BGZF_KERNEL_NAMES.items())
+                          + list(L.INFLATE_KERNEL_NAMES.items())):
             ms, cnt = C.c_double(), C.c_int64()
             L.check(self.lib.mpb_kernel_time(self.ctx, kid, C.byref(ms), C.byref(cnt)))
             out[name] = (ms.value, cnt.value)

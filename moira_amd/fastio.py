@@ -367,16 +367,23 @@ class GzipReader:
     """read(n) over a gzip file, decoded by libmoira_io's own inflate (csrc/inflate.cpp) instead of zlib: about three
     times the text rate, which is what a run on compressed input is bounded by (one stream per file cannot be split).
     `raw` is the compressed file opened in binary mode.  Multi-member files and zero padding are read as gzip reads
-    them; CRC-32 and length of every member are checked; corrupt or truncated input raises OSError."""
+    them; CRC-32 and length of every member are checked; corrupt or truncated input raises OSError.
+    `inflater` (the CLI's --device_inflate): a callable inflater(data, offs, sizes, out_offs, out) -> done that inflates the BGZF
+    members of a batch (mio_bgzf_scan's arrays over the uint8 array `data`) into the uint8 array `out` and returns one byte per
+    member, 1 where the member's text is in place.  Every member with done = 0 is decoded by mio_bgzf_inflate_mt on that member
+    alone, into its place, so an error is the host decoder's, word for word.  An inflater that raises sends the whole batch to
+    the host decoder; inflater.report(exception), when it has one, is told (it says so once per run)."""
     WINDOW = 32768
     MAX_BGZF = 1 << 16                                     # members per parallel batch
 
-    def __init__(self, raw, in_block=1 << 23, threads=1):
+    def __init__(self, raw, in_block=1 << 23, threads=1, inflater=None):
         self.L = load()
         self.threads = max(1, int(threads))
+        self.inflater = inflater
+        self.inflater_members = self.inflater_handed_back = 0      # members the inflater was given / the host decoded after it
         # BGZF members (bgzip, Illumina's writers, this package's own outputs) state their size, so a batch of them
         # inflates on `threads` threads; the first member that is not BGZF switches to the one-stream decoder for good
-        self.bgzf = self.threads > 1 and in_block >= (1 << 17)
+        self.bgzf = (self.threads > 1 or inflater is not None) and in_block >= (1 << 17)
         self.bgzf_batches = 0
         self.raw = raw
         self.st = self.L.mio_inflate_create()
@@ -455,10 +462,29 @@ class GzipReader:
             return None
         total = int(out_offs[nb])
         out = np.empty(max(total, 1), np.uint8)
-        rc = self.L.mio_bgzf_inflate_mt(self.inbuf.ctypes.data + self.in_pos, offs.ctypes.data, sizes.ctypes.data,
-                                        out_offs.ctypes.data, nb, out.ctypes.data, self.threads)
-        if rc < 0:
-            raise OSError("gzip input: " + self.L.mio_inflate_error().decode())
+        done = None
+        if self.inflater is not None:
+            try:
+                done = self.inflater(self.inbuf[self.in_pos:self.in_len], offs[:nb], sizes[:nb], out_offs[:nb + 1], out)
+            except Exception as e:                             # noqa: B902 -- the whole batch goes to the host decoder
+                if hasattr(self.inflater, "report"):
+                    self.inflater.report(e)
+        if done is None:
+            rc = self.L.mio_bgzf_inflate_mt(self.inbuf.ctypes.data + self.in_pos, offs.ctypes.data, sizes.ctypes.data,
+                                            out_offs.ctypes.data, nb, out.ctypes.data, self.threads)
+            if rc < 0:
+                raise OSError("gzip input: " + self.L.mio_inflate_error().decode())
+        else:
+            self.inflater_members += nb
+            for k in np.flatnonzero(np.asarray(done[:nb]) == 0).tolist():      # in order: the lowest bad member's error
+                self.inflater_handed_back += 1
+                rc = self.L.mio_bgzf_inflate_mt(self.inbuf.ctypes.data + self.in_pos, offs[k:].ctypes.data, sizes[k:].ctypes.data,
+                                                out_offs[k:].ctypes.data, 1, out.ctypes.data, 1)
+                if rc < 0:
+                    msg = self.L.mio_inflate_error().decode()
+                    if msg.startswith("BGZF block 0:"):        # (that call saw one member: its number in the batch)
+                        msg = "BGZF block %d:%s" % (k, msg[len("BGZF block 0:"):])
+                    raise OSError("gzip input: " + msg)
         self.in_pos += int(offs[nb - 1]) + int(sizes[nb - 1])
         self.bgzf_batches += 1
         return out[:total].tobytes()
