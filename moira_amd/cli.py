@@ -407,7 +407,7 @@ class _ReadAhead:
 def open_input_binary(filename, threads=1, inflater=None):
     """Same sniffing, bytes out: the C parser (moira_amd/fastio.py) takes whole blocks.  `threads`: what a BGZF-blocked
     gzip file (bgzip, Illumina's writers, this package's own .gz outputs) is inflated on; any other gzip file is one
-    stream on one thread.  `inflater` (--device_inflate): what inflates the BGZF members instead (fastio.GzipReader)."""
+    stream on one thread.  `inflater` (the run's _DevicePaths.inflater): what inflates the BGZF members instead (fastio.GzipReader)."""
     with io.open(filename, "rb") as fh:
         start = fh.read(3)
     if start.startswith(b"\x42\x5a\x68"):
@@ -797,75 +797,73 @@ DEVICE_COMPRESS_MEASURED = ("0.98 / 0.75 / 1.05 of zlib level 4's bytes for fast
                             "memory against 1.9 to 2.7 GB/s on 16 host threads; one pair of runs on 268 MB of FASTQ took 0.75 s either way")
 
 
-class DeviceCompressor:
-    """The one device compressor of a run (--device_compress): a second Engine on the filter's device, for compression only --
-    calls on one context must not overlap, and the writers' pool threads run beside the filtering thread -- behind a lock.  All
-    .gz writers of the run share it, and so does the run's DeviceInflater (--device_inflate)."""
-
-    def __init__(self, device, say=None):
-        import threading
-        from .engine import Engine
-        self.engine = Engine(device)
-        self.lock = threading.Lock()
-        self.say = say
-        self.reported = False
-
-    def compress(self, data):
-        with self.lock:
-            return self.engine.bgzf_compress(data)
-
-    def report(self, e):
-        """A batch went through host zlib after all: said once per run (as --device_pack's refused chunks are)."""
-        with self.lock:
-            first, self.reported = not self.reported, True
-        if first and self.say is not None:
-            self.say("--device_compress: the device did not take a batch (%s): host zlib is used for it." % e)
-
-    def close(self):
-        with self.lock:
-            if self.engine is not None:
-                self.engine.close()
-                self.engine = None
-
-
 # what tools/device_bgzf_inflate_rate.py measured once (profiles/device_bgzf_inflate_rate.json), quoted by --device_inflate's help
 DEVICE_INFLATE_MEASURED = ("Measured once on the golden reads tiled to 256 MiB: 4.7 GB/s of text against 14.5 GB/s on 16 host threads (the "
                            "kernel alone 7.0 GB/s), and a run of 468,752 reads took 0.84 s with the switch, 0.61 s without: the host "
                            "inflater is the faster one, and no rate is promised.")
 
+class _SaidOnce:
+    """A message of a run that is said the first time it applies (a batch or a chunk that went through the host after all),
+    from whichever thread meets it; say: None keeps it quiet (--nowarnings)."""
 
-class DeviceInflater:
-    """The one device inflater of a run (--device_inflate), as fastio.GzipReader calls it: the two files of a paired run inflate on
-    two read-ahead threads beside the filtering thread, so the run owns ONE auxiliary Engine behind ONE lock for inflating -- the
-    DeviceCompressor's (`share`) when --device_compress is on as well, else a second Engine on the filter's device of its own."""
-
-    def __init__(self, device, say=None, share=None):
+    def __init__(self, say, message):
         import threading
-        self.owner = share is None
-        if share is not None:
-            self.engine, self.lock = share.engine, share.lock
-        else:
-            from .engine import Engine
-            self.engine, self.lock = Engine(device), threading.Lock()
-        self.say = say
-        self.reported = False
+        self.say, self.message, self.lock = say, message, threading.Lock()
 
-    def __call__(self, data, offs, sizes, out_offs, out):
+    def __call__(self, e):
+        with self.lock:
+            say, self.say = self.say, None
+        if say is not None:
+            say(self.message % e)
+
+
+class _Role:
+    """One role of the run's auxiliary engine as its user takes it: _BlockCompressedWriter calls .compress, fastio.GzipReader
+    the object itself; .report(exception) says that role's message, once per run."""
+
+    def __init__(self, call, report):
+        self.call, self.report = call, report
+
+    def __call__(self, *a):
+        return self.call(*a)
+    compress = __call__
+
+
+class _DevicePaths:
+    """The opt-in device paths of one run, resolved (`on`: the switches in force): .pack, .contigs, and .compressor / .inflater
+    (a _Role or None).  It owns the run's ONE auxiliary Engine on the filter's device (--device_compress, --device_inflate, or
+    both: no third context), behind ONE lock: calls on one context must not overlap (include/moira_pb.h), and the writers' pool
+    threads and the read-ahead threads (two for a paired run) run beside the filtering thread.  make: the engine's constructor."""
+
+    def __init__(self, on=(), device=None, say=None, make=None):
+        self.pack, self.contigs = "device_pack" in on, "device_contigs" in on
+        self.pack_refused = _SaidOnce(say, "--device_pack: the device did not take a chunk (%s): host packing is used for it.")
+        self.engine = self.compressor = self.inflater = None
+        if "device_compress" in on or "device_inflate" in on:
+            import threading
+            if make is None:
+                from .engine import Engine as make
+            self.engine, self.lock = make(device), threading.Lock()
+        if "device_compress" in on:
+            self.compressor = _Role(self.compress, _SaidOnce(
+                say, "--device_compress: the device did not take a batch (%s): host zlib is used for it."))
+        if "device_inflate" in on:
+            self.inflater = _Role(self.inflate, _SaidOnce(
+                say, "--device_inflate: the device did not take a batch (%s): the host inflater is used for it."))
+
+    def compress(self, data):
+        with self.lock:
+            return self.engine.bgzf_compress(data)
+
+    def inflate(self, data, offs, sizes, out_offs, out):
         with self.lock:
             return self.engine.bgzf_inflate(data, offs, sizes, out_offs, out=out)[1]
 
-    def report(self, e):
-        """A batch went through the host inflater after all: said once per run."""
-        with self.lock:
-            first, self.reported = not self.reported, True
-        if first and self.say is not None:
-            self.say("--device_inflate: the device did not take a batch (%s): the host inflater is used for it." % e)
-
     def close(self):
-        with self.lock:
-            if self.owner and self.engine is not None:
+        if self.engine is not None:
+            with self.lock:
                 self.engine.close()
-            self.engine = None
+                self.engine = None
 
 
 class _BlockCompressedWriter:
@@ -878,7 +876,7 @@ class _BlockCompressedWriter:
     most `WINDOW` blocks are in flight.  One compressor thread per file is what bounds a run with compressed output
     otherwise: ~60 MB/s of text per file at gzip level 4.  A .gz output is BGZF (bgzf_compress: each 1 MiB block becomes
     17 members, the file ends with the format's end marker), so it can also be READ on several threads.
-    With a `compressor` (--device_compress: an object with compress(data) -> the BGZF members of data, and optionally
+    With a `compressor` (the run's _DevicePaths.compressor: an object with compress(data) -> the BGZF members of data, and optionally
     report(exception)) the 1 MiB blocks of a .gz output are collected into batches of BATCH_BLOCKS and one call is made per
     batch, from a pool thread as before; the batch is compressed as one text, so its members are full ones but the last.  A call
     that raises makes the batch go through bgzf_compress block by block.  Order, back-pressure (at most WINDOW blocks in flight)
@@ -984,10 +982,10 @@ class _BlockCompressedWriter:
             self.f = None
 
 
-def _open_outputs(args, output_name, binary=False, compressor=None):
+def _open_outputs(args, output_name, binary, paths):
     mode = "wb" if binary else "wt"
     if args.output_compression == "gz":
-        opener, suffix = (lambda p: _BlockCompressedWriter(p, "gz", compressor) if binary else gzip.open(p, mode, compresslevel=4)), ".gz"
+        opener, suffix = (lambda p: _BlockCompressedWriter(p, "gz", paths.compressor) if binary else gzip.open(p, mode, compresslevel=4)), ".gz"
     elif args.output_compression == "bz2":
         opener, suffix = (lambda p: _BlockCompressedWriter(p, "bz2") if binary else bz2.open(p, mode)), ".bz2"
     else:
@@ -1167,16 +1165,16 @@ class _DeferredContigs:
         return _chunk_contigs(*self.a)
 
 
-def _fast_chunks(args, contig_engine=None, fused=None):
+def _fast_chunks(args, paths, contig_engine=None, fused=None):
     """(buf, idx, aux) per chunk: reads as they are in the file, or contigs built from the two files.  With contig_engine
     (--device_contigs) a paired chunk comes as a _DeferredContigs instead: its consumer builds the contigs, on its own thread
     (fused: and filters them in the same call, FASTQ input only)."""
     from . import fastio as F
     if not args.forward_fastq:
-        yield from _fast_chunks_fasta_qual(args, contig_engine)
+        yield from _fast_chunks_fasta_qual(args, paths, contig_engine)
         return
     if not args.paired:
-        fh = open_input_binary(args.forward_fastq, _text_threads(args), getattr(args, "_inflater", None))
+        fh = open_input_binary(args.forward_fastq, _text_threads(args), paths.inflater)
         try:
             for buf, idx in F.FastqChunks(fh, CHUNK_READS, threads=_text_threads(args)):
                 yield buf, idx, None
@@ -1186,8 +1184,7 @@ def _fast_chunks(args, contig_engine=None, fused=None):
             fh.close()
         return
     half = max(1, _text_threads(args) // 2)
-    inflater = getattr(args, "_inflater", None)
-    ffh, rfh = open_input_binary(args.forward_fastq, half, inflater), open_input_binary(args.reverse_fastq, half, inflater)
+    ffh, rfh = open_input_binary(args.forward_fastq, half, paths.inflater), open_input_binary(args.reverse_fastq, half, paths.inflater)
     try:
         # reading + indexing the two files runs one chunk ahead of contig construction, on a thread of its own
         for fbuf, fidx, rbuf, ridx in _prefetched(iter(F.PairedFastqChunks(ffh, rfh, PAIR_CHUNK_READS, threads=_text_threads(args))), depth=1):
@@ -1292,19 +1289,18 @@ class _InOrder:
             raise self.err
 
 
-def _fast_chunks_fasta_qual(args, contig_engine=None):
+def _fast_chunks_fasta_qual(args, paths, contig_engine=None):
     """fasta + qual input: records rebuilt as header | sequence | quality bytes (offset 0) by
     mio_fasta_qual_index, so that the rest of the path is the FASTQ one."""
     from . import fastio as F
     half = max(1, _text_threads(args) // 2)
-    inflater = getattr(args, "_inflater", None)
-    files = [open_input_binary(args.forward_fasta, half, inflater), open_input_binary(args.forward_qual, half, inflater)]
+    files = [open_input_binary(args.forward_fasta, half, paths.inflater), open_input_binary(args.forward_qual, half, paths.inflater)]
     try:
         if not args.paired:
             for buf, idx in F.FastaQualChunks(files[0], files[1], CHUNK_READS):
                 yield buf, idx, None
             return
-        files += [open_input_binary(args.reverse_fasta, half, inflater), open_input_binary(args.reverse_qual, half, inflater)]
+        files += [open_input_binary(args.reverse_fasta, half, paths.inflater), open_input_binary(args.reverse_qual, half, paths.inflater)]
         fwd = iter(F.FastaQualChunks(files[0], files[1], PAIR_CHUNK_READS))
         rev = iter(F.FastaQualChunks(files[2], files[3], PAIR_CHUNK_READS))
         while True:
@@ -1323,7 +1319,7 @@ def _fast_chunks_fasta_qual(args, contig_engine=None):
             f.close()
 
 
-def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs=False):
+def _run_fast_fastq(args, backend, o, say, t0, paths):
     """Chunks of the input as (buffer, record index); contig construction, packing, collapse and record
     formatting in C (moira_amd/fastio.py, moira_amd/contig.py).  Decisions are write_results'
     (ref: moira/moira.py:842-970), vectorised.
@@ -1365,7 +1361,6 @@ def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs
         return label
 
     processed = 0
-    refused_once = False                                 # --device_pack: a chunk went through the host path after all
     disc_err = disc_len = disc_ov = 0.0
     threads = _text_threads(args)                        # --processors: packing / formatting calls in flight
     groups = F.Collapse(threads) if args.collapse else None
@@ -1385,10 +1380,36 @@ def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs
         if k not in lanes:
             lanes[k] = _InOrder()
         return lanes[k]
+
+    def score(buf, idx, lens, filtered):
+        """(ee, has_n) of one chunk, by the path it takes: the fused call's results as they came, one text call, or one packed
+        matrix per length bucket."""
+        if filtered is not None:
+            return filtered
+        ee = np.zeros(len(idx), np.float64)              # --only_contig: process_data returns 0 (moira.py:809-810)
+        has_n = np.zeros(len(idx), bool)
+        if only:
+            return ee, has_n
+        if paths.pack and len(idx):
+            # --device_pack: the chunk's text goes up as it lies, one call.  A ValueError (a quality character out of range, a
+            # text the entry does not take) sends the chunk through the host path below, which raises what it always raised
+            # -- or takes the chunk; the first such chunk of a run is reported, so that the switch never fails silently.
+            try:
+                return backend.text(buf, idx, args.alpha, args.ambigs, args.round, in_off, T, n_is_base, method=method,
+                                    fast_discard=fd)
+            except ValueError as e:
+                paths.pack_refused(e)
+        strides = bucket_of(lens, 64)
+        for stride in np.unique(strides):
+            sel = np.nonzero(strides == stride)[0]
+            q, ln, fl = F.pack_parallel(pool, threads, buf, idx, sel, in_off, T, n_is_base, int(stride))
+            ee[sel] = backend.matrix(q, ln, args.alpha, args.ambigs, args.round, method=method, fast_discard=fd)
+            has_n[sel] = fl
+        return ee, has_n
     ok = False
     try:
-        fused = (backend, (method, fd, T, n_is_base)) if _fused_applies(device_contigs, device_pack, only, backend) else None
-        for chunk in _prefetched(_fast_chunks(args, backend.engine if device_contigs else None, fused)):
+        fused = (backend, (method, fd, T, n_is_base)) if _fused_applies(paths.contigs, paths.pack, only, backend) else None
+        for chunk in _prefetched(_fast_chunks(args, paths, backend.engine if paths.contigs else None, fused)):
             # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context; with
             # --device_pack as well they are filtered where they lie, in the same call)
             buf, idx, aux, filtered = _filtered_where_built(chunk.build() if isinstance(chunk, _DeferredContigs) else chunk)
@@ -1397,30 +1418,7 @@ def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs
             if not only and method == "poisson_binomial" and n and int(lens.max()) > MAX_PB_LEN:
                 k = int(np.argmax(lens))
                 raise ReadTooLongError(F.header_of(buf, idx[k]), int(lens[k]))
-            strides = bucket_of(lens, 64)
-            ee = np.zeros(n, np.float64)                 # --only_contig: process_data returns 0 (moira.py:809-810)
-            has_n = np.zeros(n, bool)
-            packed = False
-            if filtered is not None:
-                ee, has_n = filtered
-                packed = True
-            elif device_pack and not only and n:
-                # --device_pack: the chunk's text goes up as it lies, one call.  A ValueError (a quality character out of range, a
-                # text the entry does not take) sends the chunk through the host path below, which raises what it always raised
-                # -- or takes the chunk; the first such chunk of a run is reported, so that the switch never fails silently.
-                try:
-                    ee, has_n = backend.text(buf, idx, args.alpha, args.ambigs, args.round, in_off, T, n_is_base, method=method,
-                                             fast_discard=fd)
-                    packed = True
-                except ValueError as e:
-                    if not refused_once and not args.nowarnings:
-                        say("--device_pack: the device did not take a chunk (%s): host packing is used for it." % e)
-                    refused_once = True
-            for stride in (np.unique(strides) if not (only or packed) else ()):
-                sel = np.nonzero(strides == stride)[0]
-                q, ln, fl = F.pack_parallel(pool, threads, buf, idx, sel, in_off, T, n_is_base, int(stride))
-                ee[sel] = backend.matrix(q, ln, args.alpha, args.ambigs, args.round, method=method, fast_discard=fd)
-                has_n[sel] = fl
+            ee, has_n = score(buf, idx, lens, filtered)
             nan = np.isnan(ee)
             if nan.any():
                 raise ReturnedNaNError(F.header_of(buf, idx[int(np.argmax(nan))]), int(lens[int(np.argmax(nan))]))
@@ -1519,6 +1517,22 @@ def _run_fast_fastq(args, backend, o, say, t0, device_pack=False, device_contigs
 # ---------------------------------------------------------------------------------------------
 # main (ref: moira/moira.py:264-578)
 # ---------------------------------------------------------------------------------------------
+# the opt-in device paths: switch, what it applies to (on the byte-level path only), and what is said where it does not;
+# resolved and said in this order
+_DEVICE_PATHS = (
+    ("device_pack", _device_pack_eligible,
+     "--device_pack does not apply to this run (it takes FASTQ input through the byte-level parser on one GPU): host packing is used."),
+    ("device_contigs", _device_contigs_eligible,
+     "--device_contigs does not apply to this run (it takes paired input through the byte-level parser on one GPU): "
+     "the host aligner is used."),
+    ("device_compress", _device_compress_eligible,
+     "--device_compress does not apply to this run (it takes -oc gz output of the byte-level parser on one GPU): host zlib is used."),
+    ("device_inflate", _device_inflate_eligible,
+     "--device_inflate does not apply to this run (it takes .gz input of the byte-level parser on one GPU): "
+     "the host inflater is used."),
+)
+
+
 def main(args, backend=None, out=None, _no_fastio=False):
     """`backend(seqs, quals, alpha, ambigs, round) -> ee` defaults to the HIP library; the parameter
     exists so the host logic can be unit-tested on machines without a GPU."""
@@ -1560,40 +1574,34 @@ def main(args, backend=None, out=None, _no_fastio=False):
     if backend is None and needs_gpu:
         backend = make_gpu_backend(getattr(args, "device", None))
     fast = _fast_eligible(args, backend) and not _no_fastio
-    device_pack = bool(getattr(args, "device_pack", False)) and not args.only_contig
-    if device_pack and not (fast and _device_pack_eligible(args, backend)):
-        device_pack = False
-        if not args.nowarnings:
-            say("--device_pack does not apply to this run (it takes FASTQ input through the byte-level parser on one GPU): "
-                "host packing is used.")
-    device_contigs = bool(getattr(args, "device_contigs", False))
-    if device_contigs and not (fast and _device_contigs_eligible(args, backend)):
-        device_contigs = False
-        if not args.nowarnings:
-            say("--device_contigs does not apply to this run (it takes paired input through the byte-level parser on one GPU): "
-                "the host aligner is used.")
-    compressor = None
-    if bool(getattr(args, "device_compress", False)):
-        if fast and _device_compress_eligible(args, backend):
-            compressor = DeviceCompressor(backend.engine.device, None if args.nowarnings else say)
-        elif not args.nowarnings:
-            say("--device_compress does not apply to this run (it takes -oc gz output of the byte-level parser on one GPU): "
-                "host zlib is used.")
-    inflater = None
-    if bool(getattr(args, "device_inflate", False)):
-        if fast and _device_inflate_eligible(args, backend):
-            inflater = DeviceInflater(backend.engine.device, None if args.nowarnings else say, share=compressor)
-        elif not args.nowarnings:
-            say("--device_inflate does not apply to this run (it takes .gz input of the byte-level parser on one GPU): "
-                "the host inflater is used.")
-    args._inflater = inflater
+    warn = None if args.nowarnings else say
+    on = set()
+    for switch, eligible, sentence in _DEVICE_PATHS:
+        if not getattr(args, switch, False) or (switch == "device_pack" and args.only_contig):      # (nothing is packed then)
+            continue
+        if fast and eligible(args, backend):
+            on.add(switch)
+        elif warn is not None:
+            warn(sentence)
+    paths = _DevicePaths(on, getattr(getattr(backend, "engine", None), "device", None), warn)
+    from . import fastio
     try:
-        o = _open_outputs(args, output_name, binary=fast, compressor=compressor)
+        try:
+            return _run(args, backend, output_name, fast, paths, parse, say)
+        finally:
+            paths.close()                  # the auxiliary engine: after the outputs are closed, on every way out of the run
+    except fastio.Unsupported:
+        if not fast:
+            raise
+        # content the byte-level parser does not reproduce: start over with the line parser
+        return main(args, backend=backend, out=out, _no_fastio=True)
+
+
+def _run(args, backend, output_name, fast, paths, parse, say):
+    """main() from the outputs on: 0, or 1 after a message; a fastio.Unsupported of the byte-level path is main()'s to take."""
+    try:
+        o = _open_outputs(args, output_name, fast, paths)
     except IOError as e:
-        if inflater is not None:
-            inflater.close()
-        if compressor is not None:
-            compressor.close()
         say(str(e))
         say()
         return 1
@@ -1630,21 +1638,7 @@ def main(args, backend=None, out=None, _no_fastio=False):
                 say("%d sequences processed in %.1f seconds." % (processed, time.time() - t0))
 
         if fast:
-            from . import fastio
-            try:
-                processed, disc_err, disc_len, disc_ov = _run_fast_fastq(args, backend, o, say, t0, device_pack=device_pack,
-                                                                         device_contigs=device_contigs)
-            except fastio.Unsupported:
-                # content the byte-level parser does not reproduce: start over with the line parser
-                _close(o)
-                if inflater is not None:
-                    inflater.close()
-                    inflater = None
-                if compressor is not None:
-                    compressor.close()
-                    compressor = None
-                args._inflater = None
-                return main(args, backend=backend, out=out, _no_fastio=True)
+            processed, disc_err, disc_len, disc_ov = _run_fast_fastq(args, backend, o, say, t0, paths)
         else:
             for rec in parse:
                 chunk.append(rec)
@@ -1687,11 +1681,6 @@ def main(args, backend=None, out=None, _no_fastio=False):
         return 1
     finally:
         _close(o)
-        if inflater is not None:
-            inflater.close()
-        if compressor is not None:
-            compressor.close()
-        args._inflater = None
     return 0
 
 

@@ -93,16 +93,6 @@ def test_a_batch_the_compressor_refuses_goes_through_the_host_and_is_reported(tm
     assert blob == b"".join(want)
 
 
-def test_the_run_compressor_reports_once(capsys):
-    said = []
-    dc = cli.DeviceCompressor.__new__(cli.DeviceCompressor)                     # (no device: only its reporting is exercised)
-    import threading
-    dc.engine, dc.lock, dc.say, dc.reported = None, threading.Lock(), said.append, False
-    dc.report(RuntimeError("a")); dc.report(RuntimeError("b"))
-    assert len(said) == 1 and "--device_compress" in said[0] and "(a)" in said[0]
-    dc.close()
-
-
 def test_without_a_compressor_and_for_bz2_the_writer_is_unchanged(tmp_path):
     import bz2
     text = text_of(3 * W.BLOCK + 5, 3)

@@ -168,12 +168,12 @@ def test_cli_golden_commands_with_device_compress(tmp_path, paired):
         be = cli.make_gpu_backend(None)
         log = io.StringIO()
         made = []
-        inner = cli.DeviceCompressor.compress
+        inner = cli._DevicePaths.compress
         try:
-            cli.DeviceCompressor.compress = lambda self, data: made.append(len(data)) or inner(self, data)
+            cli._DevicePaths.compress = lambda self, data: made.append(len(data)) or inner(self, data)
             assert cli.main(a, backend=be, out=log) == 0
         finally:
-            cli.DeviceCompressor.compress = inner
+            cli._DevicePaths.compress = inner
             be.engine.close()
         calls.append(sum(made))
         logs.append(log.getvalue())

@@ -192,14 +192,11 @@ def read_all(blob, **kw):
 
 
 def test_gzip_reader_with_the_device_inflater(eng):
-    import threading
     text = B.golden_text()
     blob = cli.bgzf_compress(text, 4) + cli.BGZF_EOF
-
-    class Shared:
-        engine, lock = eng, threading.Lock()
     said = []
-    inf = cli.DeviceInflater(0, said.append, share=Shared)
+    paths = cli._DevicePaths({"device_inflate"}, 0, said.append, make=lambda device: eng)      # (never closed: the fixture's engine)
+    inf = paths.inflater
     got, r = read_all(blob, threads=2, inflater=inf)
     assert got == text and r.inflater_members > len(text) // B.DATA and r.inflater_handed_back == 0 and not said
     # device-written members, and a corrupt one: the host's error, word for word
@@ -212,8 +209,7 @@ def test_gzip_reader_with_the_device_inflater(eng):
     with pytest.raises(OSError) as dev:
         read_all(data, threads=2, inflater=inf)
     assert str(dev.value) == str(host.value) and "BGZF block 2: CRC check failed" in str(dev.value)
-    inf.close()
-    assert Shared.engine is eng
+    assert paths.engine is eng and not said
 
 
 @pytest.mark.parametrize("paired", [False, True], ids=["forward", "paired"])
@@ -235,12 +231,12 @@ def test_cli_on_bgzf_input_with_and_without_device_inflate(tmp_path, paired):
         be = cli.make_gpu_backend(None)
         log = io.StringIO()
         made, engines = [], []
-        inner = cli.DeviceInflater.__call__
+        inner = cli._DevicePaths.inflate
         try:
-            cli.DeviceInflater.__call__ = lambda self, *x: (made.append(len(x[1])), engines.append(self.engine), inner(self, *x))[2]
+            cli._DevicePaths.inflate = lambda self, *x: (made.append(len(x[1])), engines.append(self.engine), inner(self, *x))[2]
             assert cli.main(a, backend=be, out=log) == 0
         finally:
-            cli.DeviceInflater.__call__ = inner
+            cli._DevicePaths.inflate = inner
             be.engine.close()
         calls.append(sum(made))
         logs.append(log.getvalue())
