@@ -157,7 +157,11 @@ extern "C" {
 #define MPB_K_BGZF_SCAN  15  /* ... the prefix of the members' sizes (k_bgzf_scan) */
 #define MPB_K_BGZF_FRAME 16  /* ... header, stream and trailer of every member into the dense output (k_bgzf_frame) */
 #define MPB_K_BGZF_INFLATE 17 /* BGZF .gz input on the device: one member per wave (k_bgzf_inflate) */
-#define MPB_K_COUNT     18
+#define MPB_K_FQ_LINES  18   /* the FASTQ record index on the device: newlines and refusal flags per tile (k_fq_lines) */
+#define MPB_K_FQ_SCAN   19   /* ... the prefix of the tiles' newlines (k_fq_scan) */
+#define MPB_K_FQ_STARTS 20   /* ... the line starts (k_fq_starts) */
+#define MPB_K_FQ_ROWS   21   /* ... one index row, kind and k_pack_text descriptor per record (k_fq_rows) */
+#define MPB_K_COUNT     22
 
 typedef struct mpb_ctx mpb_ctx;
 
@@ -436,6 +440,55 @@ int mpb_filter_text_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, con
                          const mpb_filter_params *params, int32_t poisson,
                          double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out,
                          mpb_filter_counts *counts, int64_t *bad_record);
+
+/*
+ * The FASTQ record index on the device (opt-in; the default indexer stays mio_fastq_index of libmoira_io.so, which is the
+ * yardstick and the only code that defines an error): a chunk of FASTQ TEXT ALONE, in host memory, is uploaded once and indexed
+ * there -- newlines counted per tile, their prefix, the line starts, one row per record (csrc/mpb_index_kernels.hip).
+ *   text, text_bytes   at most 1 GiB
+ *   final              the text ends the file: an unterminated last line counts as a line
+ *   max_records        at most that many records are indexed (>= 0)
+ *   max_len            > 0: k_pack_text's descriptors pack at most that many bases of a record (mio_pack's rule)
+ *   idx_out            int64[idx_cap_rows][MPB_IDX_COLS]: the six columns of mio_fastq_index's row
+ *   n, consumed, bad_kind   what mio_fastq_index returns and stores; rows [0, n + (bad_kind ? 1 : 0)) of idx_out are written
+ * WHEN THE DEVICE TAKES THE TEXT (*why == 0) these equal mio_fastq_index(text, text_bytes, final, max_records, ...)'s, bit for
+ * bit.  When it does not, *why says so and NOTHING ELSE is defined; the caller indexes on the host:
+ *   MPB_FQ_WHY_NON_ASCII   a byte >= 0x80        MPB_FQ_WHY_LONE_CR   a '\r' that no '\n' follows immediately
+ *   MPB_FQ_WHY_LINE_TABLE  the line table of the counted lines would not fit (more than MPB_FQ_INDEX_MAX_BYTES, or no memory)
+ *   MPB_FQ_WHY_ROW_CHECK   a line start the device wrote failed its check against the text (never expected)
+ * The device refuses a superset of what the host calls MIO_E_UNSUPPORTED: it looks at every byte up to the last newline (of a
+ * final text: every byte), also behind the first bad record or behind max_records, where the host would not look.  Bytes behind
+ * the last newline of a non-final text are not looked at by either: a "\r" that ends a block of a CRLF file is no reason.  It
+ * never returns an index the host would not return, and a problem in the text's content never fails the call.
+ * Argument errors are MPB_E_INVALID: a NULL pointer, a negative size, more than 1 GiB of text, and an idx_cap_rows below
+ * min(max_records, the text's lines / 4) + 1 -- known once the lines are counted; *n then holds that number of records, so that
+ * a caller who guessed may ask again.  Device memory is sized from the counted lines (one small read-back after the scan),
+ * never from the worst case of one line per byte.  Synchronous; the staging blocks belong to the context.
+ */
+#define MPB_FQ_WHY_TAKEN      0
+#define MPB_FQ_WHY_NON_ASCII  1
+#define MPB_FQ_WHY_LONE_CR    2
+#define MPB_FQ_WHY_LINE_TABLE 3
+#define MPB_FQ_WHY_ROW_CHECK  4
+#define MPB_FQ_INDEX_MAX_BYTES (4ll << 30)
+int mpb_fastq_index_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
+                         int64_t *idx_out, int64_t idx_cap_rows, int64_t *n, int64_t *consumed, int32_t *bad_kind, int32_t *why);
+
+/*
+ * Text alone in, index and results out: mpb_fastq_index_host's index and mpb_filter_text_host's filter from ONE upload.  In this
+ * order: the text is uploaded; the index is built on the device; {n, first bad record, longest packed length} are read back; the
+ * matrix is laid out at round_up(max(longest, 1), 128); records 0..n-1 are packed and filtered piece by piece from the
+ * device-written descriptors (mpb_filter_text_host's piece loop, MPB_TEXT_PIECE_BYTES included); the results and the index are
+ * copied back.  ee, ns, pass, len_out, flags_out hold idx_cap_rows entries (len_out and flags_out may be NULL); counts and
+ * bad_record may be NULL.  *why != 0: handed back as above, and nothing was filtered.  Otherwise n, consumed, bad_kind and the
+ * rows are mio_fastq_index's and the results are bit-identical to mio_fastq_index + mpb_filter_text_host on the same text;
+ * MPB_E_RANGE with mio_pack's message and *bad_record are as there, and a record longer than 65535 packed bases is MPB_E_INVALID.
+ */
+int mpb_filter_fastq_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
+                          int64_t *idx_out, int64_t idx_cap_rows, int64_t *n, int64_t *consumed, int32_t *bad_kind, int32_t *why,
+                          int32_t fastq_offset, int32_t lower_n_is_base, const mpb_filter_params *params, int32_t poisson,
+                          double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out,
+                          mpb_filter_counts *counts, int64_t *bad_record);
 
 /*
  * Paired-read contigs on the device (opt-in; the default builder stays mct_contigs_from_fastq of libmoira_contig.so): the

@@ -37,6 +37,9 @@ K_BGZF_DEFLATE, K_BGZF_SCAN, K_BGZF_FRAME = 14, 15, 16     # MPB_K_BGZF_*: .gz o
 BGZF_KERNEL_NAMES = {K_BGZF_DEFLATE: "bgzf_deflate", K_BGZF_SCAN: "bgzf_scan", K_BGZF_FRAME: "bgzf_frame"}
 K_BGZF_INFLATE = 17             # MPB_K_BGZF_INFLATE: BGZF .gz input on the device (k_bgzf_inflate)
 INFLATE_KERNEL_NAMES = {K_BGZF_INFLATE: "bgzf_inflate"}
+K_FQ_LINES, K_FQ_SCAN, K_FQ_STARTS, K_FQ_ROWS = 18, 19, 20, 21     # MPB_K_FQ_*: the FASTQ record index on the device
+INDEX_KERNEL_NAMES = {K_FQ_LINES: "fq_lines", K_FQ_SCAN: "fq_scan", K_FQ_STARTS: "fq_starts", K_FQ_ROWS: "fq_rows"}
+FQ_WHY = ("taken", "non-ASCII byte", "lone carriage return", "line table", "row check")     # MPB_FQ_WHY_*
 BGZF_WHY = ("ok", "header", "block type", "stored length", "code-length code", "repeat", "tree", "symbol", "distance", "overrun",
             "short", "truncated", "trailing bytes", "crc")     # MPB_BGZF_WHY_*
 BGZF_DATA = 0xff00             # MPB_BGZF_DATA: text bytes per BGZF member
@@ -128,6 +131,12 @@ PROTOTYPES = {
     "mpb_filter_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP, C.POINTER(FilterCounts),
                                        C.POINTER(C.c_int64)]),
+    "mpb_fastq_index_host": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _VP, C.c_int64, C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mpb_filter_fastq_host": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _VP, C.c_int64, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.c_int32, C.c_int32, C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP,
+                                        C.POINTER(FilterCounts), C.POINTER(C.c_int64)]),
     "mpb_pair_rows": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _VP, C.POINTER(C.c_int64)]),
     "mpb_contig_posterior_tables": (C.c_int, [_VP, _VP]),
     "mpb_contigs_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.POINTER(ContigParams),

@@ -243,6 +243,13 @@ def build_parser():
                         "at a time. Results and output files are identical. Where it does not apply (fasta+qual input, the line "
                         "parser, several GPUs, no GPU) one line says so and host packing is used. With --device_contigs as well, "
                         "the contigs of a paired chunk are packed and filtered where the device built them, in the same call.")
+    f.add_argument("--device_index", action="store_true",
+                   help="(not in moira.py) with --device_pack, single-end FASTQ input on one GPU: build the record index of each "
+                        "block of text on the device too, in the same call that packs and filters it (the text goes up once and "
+                        "the host indexer does not run). A block the device does not take (a lone carriage return, a byte above "
+                        "127) is indexed on the host as always, with one message, so errors and output files are identical. Paired "
+                        "input and fasta+qual input stay on the host indexer; where the switch does not apply one line says so. "
+                        + DEVICE_INDEX_MEASURED)
     f.add_argument("--device_compress", action="store_true",
                    help="(not in moira.py) with -oc gz on one GPU: compress the .gz outputs on the device (BGZF members of 65,280 "
                         "text bytes, one workgroup each, batches of 16 MiB of text per call on a context of its own) instead of "
@@ -802,6 +809,13 @@ DEVICE_INFLATE_MEASURED = ("Measured once on the golden reads tiled to 256 MiB: 
                            "kernel alone 7.0 GB/s), and a run of 468,752 reads took 0.84 s with the switch, 0.61 s without: the host "
                            "inflater is the faster one, and no rate is promised.")
 
+# what tools/device_index_rate.py measured once (profiles/device_index_rate.json), quoted by --device_index's help
+DEVICE_INDEX_MEASURED = ("Measured once on the golden reads tiled to 256 MiB: index and filter from one upload took 6.4 ms against 13.5 ms "
+                         "with the host indexer on 16 threads (the index alone 5.9 ms either way), but one pair of whole runs of 468,752 "
+                         "reads took 0.58 s with the switch and 0.49 s without, where the host indexer runs beside the filter: no rate "
+                         "is promised.")
+
+
 class _SaidOnce:
     """A message of a run that is said the first time it applies (a batch or a chunk that went through the host after all),
     from whichever thread meets it; say: None keeps it quiet (--nowarnings)."""
@@ -830,7 +844,7 @@ class _Role:
 
 
 class _DevicePaths:
-    """The opt-in device paths of one run, resolved (`on`: the switches in force): .pack, .contigs, and .compressor / .inflater
+    """The opt-in device paths of one run, resolved (`on`: the switches in force): .pack, .contigs, .index, and .compressor / .inflater
     (a _Role or None).  It owns the run's ONE auxiliary Engine on the filter's device (--device_compress, --device_inflate, or
     both: no third context), behind ONE lock: calls on one context must not overlap (include/moira_pb.h), and the writers' pool
     threads and the read-ahead threads (two for a paired run) run beside the filtering thread.  make: the engine's constructor."""
@@ -838,6 +852,8 @@ class _DevicePaths:
     def __init__(self, on=(), device=None, say=None, make=None):
         self.pack, self.contigs = "device_pack" in on, "device_contigs" in on
         self.pack_refused = _SaidOnce(say, "--device_pack: the device did not take a chunk (%s): host packing is used for it.")
+        self.index = "device_index" in on
+        self.index_refused = _SaidOnce(say, "--device_index: the device did not take a block (%s): the host indexer is used for it.")
         self.engine = self.compressor = self.inflater = None
         if "device_compress" in on or "device_inflate" in on:
             import threading
@@ -1052,6 +1068,12 @@ def _device_pack_eligible(args, backend):
     return bool(args.forward_fastq and getattr(backend, "text", None) is not None and 0 <= args.fastq_offset <= 255)
 
 
+def _device_index_eligible(args, backend):
+    """--device_index applies to single-end FASTQ input that --device_pack takes, on a backend whose engine indexes text on its device."""
+    return bool(_device_pack_eligible(args, backend) and not args.paired and not args.only_contig
+                and hasattr(getattr(backend, "engine", None), "filter_fastq"))
+
+
 def _device_compress_eligible(args, backend):
     """--device_compress applies to a run with -oc gz that the byte-level path takes, on a GPU backend with one device."""
     eng = getattr(backend, "engine", None)
@@ -1165,6 +1187,66 @@ class _DeferredContigs:
         return _chunk_contigs(*self.a)
 
 
+DEVICE_INDEX_BLOCK = 1 << 26      # --device_index: bytes of text per read, hence per call (a text call takes at most 1 GiB)
+
+
+class _DeferredBlock:
+    """A block of FASTQ text that is still to be indexed, by whoever takes it off the queue (--device_index).  The producer thread
+    only reads: calls on one context must not overlap (include/moira_pb.h), and the consumer thread is the one that filters on
+    that context, so it makes the call that indexes and filters the block too (_DeviceIndexer).  eof: nothing follows."""
+
+    def __init__(self, data, eof):
+        self.data, self.eof = data, eof
+
+
+def _read_blocks(fh, block_bytes):
+    """The stream as _DeferredBlocks; the last one is empty and says that the text has ended."""
+    while True:
+        data = fh.read(block_bytes)
+        if not data:
+            break
+        yield _DeferredBlock(data, False)
+    yield _DeferredBlock(b"", True)
+
+
+class _DeviceIndexer:
+    """The consumer's side of --device_index: it owns the partial record carried from one block to the next, and makes of every
+    block the chunks FastqChunks would have made of it -- (buf, idx, None, (ee, has_n)) -- with one engine.filter_fastq call per
+    chunk: index, pack and filter from one upload.  The order of effects is FastqChunks': the records before an offending one
+    are yielded first, then its error is raised; trailing lines that do not make a record are dropped at the end of the file.
+    A block the device hands back (engine.NotTaken), or whose call ends in a ValueError, is indexed by fastio.index and comes
+    without results: the caller filters it as any chunk (--device_pack's text call); the first such block is reported.  A
+    fastio.Unsupported of the host indexer is the run's to take (it starts over with the line parser)."""
+
+    def __init__(self, engine, filter_kw, max_records, refused, threads=1, not_taken=None):
+        if not_taken is None:
+            from .engine import NotTaken as not_taken
+        self.engine, self.kw, self.max_records, self.refused, self.threads = engine, filter_kw, max_records, refused, threads
+        self.not_taken, self.carry = not_taken, b""
+
+    def take(self, block):
+        from . import fastio as F
+        data = self.carry + block.data if self.carry else block.data
+        self.carry = b""
+        while data:
+            filtered = None
+            try:
+                r = self.engine.filter_fastq(data, final=block.eof, max_records=self.max_records, **self.kw)
+                idx, consumed, err, filtered = r.idx, r.consumed, r.bad, (r.ee, r.has_n)
+            except (self.not_taken, ValueError) as e:
+                self.refused(e)
+                idx, consumed, err = F.index(data, block.eof, self.max_records, self.threads)
+            if len(idx):
+                yield data, idx, None, filtered
+            if err is not None:
+                raise err
+            data = data[consumed:]
+            if len(idx) < self.max_records:
+                break                                   # the rest is an incomplete record: it waits for the next block
+        if not block.eof:
+            self.carry = data
+
+
 def _fast_chunks(args, paths, contig_engine=None, fused=None):
     """(buf, idx, aux) per chunk: reads as they are in the file, or contigs built from the two files.  With contig_engine
     (--device_contigs) a paired chunk comes as a _DeferredContigs instead: its consumer builds the contigs, on its own thread
@@ -1176,6 +1258,9 @@ def _fast_chunks(args, paths, contig_engine=None, fused=None):
     if not args.paired:
         fh = open_input_binary(args.forward_fastq, _text_threads(args), paths.inflater)
         try:
+            if paths.index:
+                yield from _read_blocks(fh, DEVICE_INDEX_BLOCK)      # (--device_index: the consumer indexes, on its own thread)
+                return
             for buf, idx in F.FastqChunks(fh, CHUNK_READS, threads=_text_threads(args)):
                 yield buf, idx, None
         except F.RecordError as e:
@@ -1409,10 +1494,25 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
     ok = False
     try:
         fused = (backend, (method, fd, T, n_is_base)) if _fused_applies(paths.contigs, paths.pack, only, backend) else None
-        for chunk in _prefetched(_fast_chunks(args, paths, backend.engine if paths.contigs else None, fused)):
+        indexer = None
+        if paths.index:
+            indexer = _DeviceIndexer(backend.engine, dict(fastq_offset=in_off, max_len=T, lower_n_is_base=n_is_base,
+                                                          **backend.text_choice(args.alpha, args.ambigs, args.round, method, fd)),
+                                     CHUNK_READS, paths.index_refused, threads)
+
+        def chunks():
             # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context; with
-            # --device_pack as well they are filtered where they lie, in the same call)
-            buf, idx, aux, filtered = _filtered_where_built(chunk.build() if isinstance(chunk, _DeferredContigs) else chunk)
+            # --device_pack as well they are filtered where they lie, in the same call.  --device_index: the same for a block
+            # of text, which may hold several chunks, or none)
+            for chunk in _prefetched(_fast_chunks(args, paths, backend.engine if paths.contigs else None, fused)):
+                if isinstance(chunk, _DeferredBlock):
+                    try:
+                        yield from indexer.take(chunk)
+                    except F.RecordError as e:
+                        raise _record_error(0, e, args)
+                else:
+                    yield _filtered_where_built(chunk.build() if isinstance(chunk, _DeferredContigs) else chunk)
+        for buf, idx, aux, filtered in chunks():
             n = len(idx)
             lens = np.minimum(idx[:, F.SEQ_LEN], T) if T else idx[:, F.SEQ_LEN].copy()
             if not only and method == "poisson_binomial" and n and int(lens.max()) > MAX_PB_LEN:
@@ -1525,6 +1625,9 @@ _DEVICE_PATHS = (
     ("device_contigs", _device_contigs_eligible,
      "--device_contigs does not apply to this run (it takes paired input through the byte-level parser on one GPU): "
      "the host aligner is used."),
+    ("device_index", _device_index_eligible,
+     "--device_index does not apply to this run (it takes single-end FASTQ input of the byte-level parser on one GPU, with "
+     "--device_pack): the host indexer is used."),
     ("device_compress", _device_compress_eligible,
      "--device_compress does not apply to this run (it takes -oc gz output of the byte-level parser on one GPU): host zlib is used."),
     ("device_inflate", _device_inflate_eligible,
@@ -1579,7 +1682,7 @@ def main(args, backend=None, out=None, _no_fastio=False):
     for switch, eligible, sentence in _DEVICE_PATHS:
         if not getattr(args, switch, False) or (switch == "device_pack" and args.only_contig):      # (nothing is packed then)
             continue
-        if fast and eligible(args, backend):
+        if fast and eligible(args, backend) and (switch != "device_index" or "device_pack" in on):
             on.add(switch)
         elif warn is not None:
             warn(sentence)

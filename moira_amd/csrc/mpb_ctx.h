@@ -1,6 +1,6 @@
 // mpb_ctx.h -- the context of the C ABI (struct mpb_ctx) and what the GPU-facing host units share: the error macros, the owner of
 // a growable block (Buf), the carver that lays a block out (Carver), the timing span, and the few functions that cross units
-// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp, mpb_text.cpp).  Not installed.
+// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp, mpb_text.cpp, mpb_index.cpp).  Not installed.
 #ifndef MPB_CTX_H
 #define MPB_CTX_H
 
@@ -107,6 +107,8 @@ struct PinWords {
     unsigned long long pt_kept;                          // ... and the reads it kept
     long long ovf_total;                                 // host pipeline: overflow re-runs of all chunks
     int64_t text_status[2];                              // mpb_filter_text_host: k_pack_text's status, both ways
+    uint32_t fq_head[4];                                 // the device index: k_fq_scan's head words {newlines, refusal flags, lines, 0}
+    int64_t fq_status[4];                                // ... k_fq_rows' status, both ways; [3]: the first byte behind the last record
 };
 
 struct TimedSpan { int kid; hipEvent_t a, b; };
@@ -177,6 +179,8 @@ struct mpb_ctx {
     bool contig_tabs_ready = false;
     Buf bgzf_stage{BUF_DEVICE};          // mpb_bgzf_compress_host: one piece of text | tokens | slots | sizes | offsets | CRCs | the framed output
     Buf inflate_stage{BUF_DEVICE};       // mpb_bgzf_inflate_host: one piece of compressed bytes | rows | status rows | the piece's text
+    Buf fastq_stage{BUF_DEVICE};         // mpb_fastq_index_host / mpb_filter_fastq_host: text | tile table | prefix | head | status
+    Buf fastq_index{BUF_DEVICE};         // ... and, sized from the counted lines: line starts | index rows | kinds | descriptors
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)
@@ -239,6 +243,11 @@ struct TextStage {
     {
         k.take(text, align_up(text_bytes > 0 ? text_bytes : 1, 16));
         k.take(rows, n);
+        layout_results(k, n, piece_rows, stride);
+    }
+    // ... of a call whose text and descriptors lie elsewhere on the device (mpb_filter_fastq_host): text and rows stay null
+    void layout_results(Carver &k, int64_t n, int64_t piece_rows, int64_t stride)
+    {
         k.take(status, 2);
         k.take(q, piece_rows * stride);
         k.take(len, n); k.take(flags, n);
@@ -254,6 +263,10 @@ int64_t text_piece_rows(int64_t n, int64_t stride);
 int filter_text_pieces(mpb_ctx *c, const uint8_t *d_text, int64_t text_bytes, const mpb_text_row *d_rows, int64_t n, int64_t stride,
                        int64_t piece_rows, int32_t fastq_offset, int32_t lower_n_is_base, const mpb_filter_params *params,
                        int32_t poisson, const TextStage &st, int64_t *n_pass, int64_t *n_overflow, int64_t *bad_record);
+// What follows the piece loop: the results of n rows copied out of st (len_out / flags_out may be null), and -- poisson without
+// the device tail -- the reference's scalar tail on the host; *n_pass is the piece loop's count going in, the call's going out.
+int text_results_out(mpb_ctx *c, const TextStage &st, int64_t n, const mpb_filter_params *params, int32_t poisson, double *ee,
+                     int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, int64_t *n_pass);
 // mpb_perread.cpp: the per-read entry's resident kernel leaves (before anything is freed: the runtime waits for the whole
 // device there); ... and its stream and blocks go
 void serve_quiesce(mpb_ctx *c);

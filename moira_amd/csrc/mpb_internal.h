@@ -264,6 +264,20 @@ void mpb_launch_bgzf_frame(const uint8_t *slots, const uint32_t *size, const int
 #define MPB_INFLATE_MSTAT 8
 void mpb_launch_bgzf_inflate(const uint8_t *in, int64_t in_bytes, const mpb_bgzf_member_row *rows, int64_t n_members, uint8_t *text,
                              int64_t text_bytes, uint32_t *mstat, hipStream_t s);
+// The FASTQ record index on the device (mpb_index_kernels.hip; what a lane does: mpb_index_lane.inc).  text[text_bytes] lies in an
+// allocation rounded up to 16 bytes; a tile is MPB_FQ_TILE bytes of it.
+// k_fq_lines: info[n_tiles] = a tile's newlines and its flags.  k_fq_scan (one block): prefix[n_tiles] = the newlines before a tile,
+// head[4] = {newlines, refusal flags (bit 0: a non-ASCII byte, bit 1: a lone carriage return), lines, 0}.  k_fq_starts:
+// start[k] = the first byte of line k, for k < n_start.  k_fq_rows: records 0..n-1 from start[] -> idx[n][6], kinds[n], desc[n];
+// status[4] (set to {INT64_MAX, 0, 0, 0} by the caller) = {first bad record, longest packed length of a good one, a line check failed}.
+#define MPB_FQ_TILE 16384
+void mpb_launch_fq_lines(const uint8_t *text, int64_t text_bytes, int64_t n_tiles, uint32_t *info, hipStream_t s);
+void mpb_launch_fq_scan(const uint8_t *text, int64_t text_bytes, bool final_text, const uint32_t *info, int64_t n_tiles,
+                        uint32_t *prefix, uint32_t *head, hipStream_t s);
+void mpb_launch_fq_starts(const uint8_t *text, int64_t text_bytes, int64_t n_tiles, const uint32_t *prefix, const uint32_t *head,
+                          uint32_t *start, int64_t n_start, hipStream_t s);
+void mpb_launch_fq_rows(const uint8_t *text, int64_t text_bytes, const uint32_t *start, int64_t n_start, int64_t n, int32_t max_len,
+                        int64_t *idx, uint8_t *kinds, mpb_text_row *desc, int64_t *status, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

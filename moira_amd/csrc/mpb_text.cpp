@@ -107,6 +107,38 @@ int filter_text_pieces(mpb_ctx *c, const uint8_t *d_text, int64_t text_bytes, co
     return MPB_OK;
 }
 
+int text_results_out(mpb_ctx *c, const TextStage &st, int64_t n, const mpb_filter_params *params, int32_t poisson, double *ee,
+                     int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, int64_t *n_pass_io)
+{
+    const bool device_tail = poisson && params && (params->flags & MPB_FLAG_POISSON_DEVICE_TAIL);
+    hipStream_t s = c->stream;
+    int rc;
+    int64_t n_pass = *n_pass_io;
+    // the results, whole
+    hipError_t e_out = hipMemcpyAsync(ee, st.ee, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e_out == hipSuccess) e_out = hipMemcpyAsync(ns, st.ns, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e_out == hipSuccess && !(poisson && !device_tail)) e_out = hipMemcpyAsync(pass, st.pass, (size_t)n, hipMemcpyDeviceToHost, s);
+    std::vector<int32_t> len_tmp;
+    int32_t *len_host = len_out;
+    if (poisson && !device_tail && !len_host) {
+        try { len_tmp.resize((size_t)n); } catch (const std::bad_alloc &) { (void)hipStreamSynchronize(s); return fail(MPB_E_NOMEM, "out of host memory"); }
+        len_host = len_tmp.data();
+    }
+    if (e_out == hipSuccess && len_host) e_out = hipMemcpyAsync(len_host, st.len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e_out == hipSuccess && flags_out) e_out = hipMemcpyAsync(flags_out, st.flags, (size_t)n, hipMemcpyDeviceToHost, s);
+    const hipError_t e_sync = hipStreamSynchronize(s);
+    HIPCHK_KEPT("hipMemcpyAsync (results)", e_out);
+    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    if (poisson && !device_tail) {
+        // the reference's scalar tail with the host's libm, in place: ee holds lambda (mpb_filter_poisson_host's arithmetic)
+        if ((rc = mpb_poisson_finish_host(ee, ns, len_host, 0, n, params, ee, pass))) return rc;
+        n_pass = 0;
+        for (int64_t i = 0; i < n; i++) n_pass += pass[i];
+    }
+    *n_pass_io = n_pass;
+    return MPB_OK;
+}
+
 int mpb_filter_text_host(mpb_ctx *c, const char *text, int64_t text_bytes, const int64_t *idx, int64_t n_records,
                          const int64_t *sel, int64_t n, int32_t fastq_offset, int32_t max_len, int32_t lower_n_is_base,
                          const mpb_filter_params *params, int32_t poisson, double *ee, int32_t *ns, uint8_t *pass,
@@ -114,7 +146,6 @@ int mpb_filter_text_host(mpb_ctx *c, const char *text, int64_t text_bytes, const
 {
     CTXCHK(c);
     if (bad_record) *bad_record = -1;
-    const bool device_tail = poisson && params && (params->flags & MPB_FLAG_POISSON_DEVICE_TAIL);
     int rc = check_params(params);
     if (rc) return rc;
     if (n < 0 || text_bytes < 0 || (text_bytes > 0 && !text)) return fail(MPB_E_INVALID, "mpb_filter_text_host: bad arguments");
@@ -150,27 +181,7 @@ int mpb_filter_text_host(mpb_ctx *c, const char *text, int64_t text_bytes, const
     int64_t n_pass = 0, n_overflow = 0;
     if ((rc = filter_text_pieces(c, st.text, text_bytes, st.rows, n, stride, piece_rows, fastq_offset, lower_n_is_base, params, poisson,
                                  st, &n_pass, &n_overflow, bad_record))) return rc;
-    // the results, whole
-    hipError_t e_out = hipMemcpyAsync(ee, st.ee, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (e_out == hipSuccess) e_out = hipMemcpyAsync(ns, st.ns, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e_out == hipSuccess && !(poisson && !device_tail)) e_out = hipMemcpyAsync(pass, st.pass, (size_t)n, hipMemcpyDeviceToHost, s);
-    std::vector<int32_t> len_tmp;
-    int32_t *len_host = len_out;
-    if (poisson && !device_tail && !len_host) {
-        try { len_tmp.resize((size_t)n); } catch (const std::bad_alloc &) { (void)hipStreamSynchronize(s); return fail(MPB_E_NOMEM, "out of host memory"); }
-        len_host = len_tmp.data();
-    }
-    if (e_out == hipSuccess && len_host) e_out = hipMemcpyAsync(len_host, st.len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e_out == hipSuccess && flags_out) e_out = hipMemcpyAsync(flags_out, st.flags, (size_t)n, hipMemcpyDeviceToHost, s);
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    HIPCHK_KEPT("hipMemcpyAsync (results)", e_out);
-    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
-    if (poisson && !device_tail) {
-        // the reference's scalar tail with the host's libm, in place: ee holds lambda (mpb_filter_poisson_host's arithmetic)
-        if ((rc = mpb_poisson_finish_host(ee, ns, len_host, 0, n, params, ee, pass))) return rc;
-        n_pass = 0;
-        for (int64_t i = 0; i < n; i++) n_pass += pass[i];
-    }
+    if ((rc = text_results_out(c, st, n, params, poisson, ee, ns, pass, len_out, flags_out, &n_pass))) return rc;
     if (counts) { counts->n_pass = n_pass; counts->n_fail = n - n_pass; counts->n_overflow = n_overflow; }
     return MPB_OK;
 }

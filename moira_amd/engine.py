@@ -67,6 +67,25 @@ class TextFilterResult(FilterResult):
         self.lens, self.has_n = lens, has_n
 
 
+class NotTaken(Exception):
+    """The device did not take a text for indexing (Engine.fastq_index, Engine.filter_fastq): .why is MPB_FQ_WHY_* (1 a byte
+    >= 0x80, 2 a lone carriage return, 3 the line table would not fit, 4 a row check failed), str() names it.  The caller
+    indexes on the host (fastio.index), which raises whatever there is to raise."""
+
+    def __init__(self, why):
+        Exception.__init__(self, L.FQ_WHY[why] if 0 <= why < len(L.FQ_WHY) else "reason %d" % why)
+        self.why = why
+
+
+class FastqFilterResult(TextFilterResult):
+    """TextFilterResult of Engine.filter_fastq, with the record index the device built next to it: idx, consumed, bad as
+    fastio.index returns them."""
+
+    def __init__(self, idx, consumed, bad, *a):
+        TextFilterResult.__init__(self, *a)
+        self.idx, self.consumed, self.bad = idx, consumed, bad
+
+
 TEXT_ROW_DTYPE = np.dtype([("seq_off", "<i8"), ("qual_off", "<i8"), ("len", "<i4"), ("pad", "<i4")])     # mpb_text_row
 
 
@@ -94,6 +113,16 @@ def _check_text(rc, bad):
     except ValueError as e:
         e.bad_record = bad.value
         raise
+
+
+def _record_error(buf, idx, n, kind):
+    """fastio.index's third value from a device-built index: None, or the RecordError of row n (.row: its six columns)."""
+    if not kind:
+        return None
+    from . import fastio
+    err = fastio.RecordError(kind, fastio.header_of(buf, idx[n]))
+    err.row = idx[n].copy()
+    return err
 
 
 def text_rows(idx, sel=None, text_bytes=0, max_len=0, stride=0):
@@ -345,6 +374,66 @@ class Engine:
         del keep
         _check_text(rc, bad)
         return TextFilterResult(ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), counts.n_pass, counts.n_overflow)
+
+    # ---- the FASTQ record index on the device (k_fq_lines / _scan / _starts / _rows) --------------
+    def _fastq_call(self, buf, final, max_records, max_len, call):
+        """One call of either text-alone entry: call(addr, nbytes, final, max_records, max_len, idx, cap, n, consumed, bad, why)
+        -> rc.  max_records None: no limit; the index is sized by a guess of the records (64 bytes each) and, where the text
+        holds more, once more by what the entry counted.  -> (idx rows, n, consumed, bad kind)."""
+        keep, addr, nbytes = _text_ptr(buf)
+        limit = (1 << 62) if max_records is None else int(max_records)
+        if limit < 0:
+            raise ValueError("max_records must not be negative")
+        cap = min(limit, nbytes // 64 + 64) + 1
+        while True:
+            idx = np.empty((cap, 6), np.int64)
+            n, consumed, bad, why = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+            rc = call(addr, nbytes, 1 if final else 0, limit, int(max_len), idx.ctypes.data, cap, C.byref(n), C.byref(consumed),
+                      C.byref(bad), C.byref(why))
+            if rc == L.E_INVALID and n.value + 1 > cap and cap < limit + 1:
+                cap = n.value + 1                            # the text holds more records than the guess: their number is known now
+                continue
+            break
+        del keep
+        return rc, idx, n.value, consumed.value, bad.value, why.value
+
+    def fastq_index(self, buf, final=True, max_records=None):
+        """The record index of a chunk of FASTQ text in host memory, built on the device from the text alone
+        (mpb_fastq_index_host) -> (idx int64[n, 6], consumed, bad) as fastio.index returns them: bad is None or a
+        fastio.RecordError (.kind, .header, and .row = the six columns of the offending record).  NotTaken(why) when the device
+        hands the text back (a lone carriage return, a byte >= 0x80, ...): the caller indexes it on the host."""
+        call = lambda *a: self.lib.mpb_fastq_index_host(self.ctx, *a)
+        rc, idx, n, consumed, bad, why = self._fastq_call(buf, final, max_records, 0, call)
+        L.check(rc)
+        if why:
+            raise NotTaken(why)
+        return idx[:n], consumed, _record_error(buf, idx, n, bad)
+
+    def filter_fastq(self, buf, final=True, max_records=None, fastq_offset=33, max_len=0, lower_n_is_base=False, poisson=False, **kw):
+        """A chunk of FASTQ text ALONE -> FastqFilterResult: one upload, the index built on the device, the records before the
+        first bad one packed and filtered there (mpb_filter_fastq_host).  .idx, .consumed, .bad are fastio.index's and the
+        results are filter_text's on that index, bit for bit.  NotTaken(why) when the device hands the text back; ValueError
+        with the library's message for a quality character out of range (.bad_record = the record's position).  `kw` as
+        filter()'s."""
+        params = kw.pop("params", None) or self.params(**kw)
+        counts, badrec = L.FilterCounts(), C.c_int64(-1)
+        out = {}
+
+        def call(addr, nbytes, final_, limit, max_len_, idx_ptr, cap, n, consumed, bad, why):
+            out["a"] = (np.empty(cap, np.float64), np.empty(cap, np.int32), np.empty(cap, np.uint8), np.empty(cap, np.int32),
+                        np.empty(cap, np.uint8))
+            ee, ns, ps, lens, flags = out["a"]
+            return self.lib.mpb_filter_fastq_host(self.ctx, addr, nbytes, final_, limit, max_len_, idx_ptr, cap, n, consumed, bad, why,
+                                                  int(fastq_offset), 1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0,
+                                                  ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data, flags.ctypes.data,
+                                                  C.byref(counts), C.byref(badrec))
+        rc, idx, n, consumed, bad, why = self._fastq_call(buf, final, max_records, max_len, call)
+        _check_text(rc, badrec)
+        if why:
+            raise NotTaken(why)
+        ee, ns, ps, lens, flags = out["a"]
+        return FastqFilterResult(idx[:n], consumed, _record_error(buf, idx, n, bad), ee[:n], ns[:n], ps[:n].view(bool), lens[:n],
+                                 flags[:n].view(bool), counts.n_pass, counts.n_overflow)
 
     # ---- paired-read contigs on the device (mpb_pair_rows, k_contig) ------------------------------
     @staticmethod
@@ -662,7 +751,7 @@ class Engine:
         """{name: (total_ms, launches)} since the last reset (synchronises)."""
         out = {}
         for kid, name in (list(L.KERNEL_NAMES.items()) + list(L.CONTIG_KERNEL_NAMES.items()) + list(L.BGZF_KERNEL_NAMES.items())
-                          + list(L.INFLATE_KERNEL_NAMES.items())):
+                          + list(L.INFLATE_KERNEL_NAMES.items()) + list(L.INDEX_KERNEL_NAMES.items())):
             ms, cnt = C.c_double(), C.c_int64()
             L.check(self.lib.mpb_kernel_time(self.ctx, kid, C.byref(ms), C.byref(cnt)))
             out[name] = (ms.value, cnt.value)
