@@ -1,5 +1,6 @@
 """Inputs shared by the CPU model test of the device compressor's lane code (tests/test_bgzf_lane_model.py) and the GPU test of
-the kernels (tests/test_gpu_bgzf.py): the smallest shapes at which k_bgzf_deflate can go wrong.  Everything is seeded."""
+the kernels (tests/test_gpu_bgzf.py): the smallest shapes at which k_bgzf_deflate can go wrong.  Everything is seeded: the
+model's streams of all of them are a fixture (tests/helpers/bgzf_model.py), so a changed input needs it written again."""
 import functools
 import gzip
 import os
@@ -114,6 +115,94 @@ def named_inputs():
     # the minimum match as the member's last three bytes: a text without a repeat, then three new bytes twice
     cases.append(("min_match_at_end", de_bruijn_prefix()[:700] + b"xyzxyz"))
     return cases
+
+
+FIB16 = (1, 2, 3, 5, 8, 13, 21, 34, 55, 89, 144, 233, 377, 610, 987, 1597)
+
+
+def codes_of_15_bits():
+    """A member whose literal/length code reaches 15 bits: the whole de Bruijn sequence B(36, 3) over the bytes 48..83 (no
+    3-gram twice, about 1,300 of each symbol), then 4,179 units [u v w c] with (u, v, w) distinct triples of the same symbols and
+    c one of 16 other bytes with the counts FIB16: nearly every byte is a literal and the rare bytes form a chain in the tree."""
+    rng = np.random.default_rng(15)
+    head = de_bruijn_prefix(36, 3, 36 ** 3)
+    units = sum(FIB16)
+    triples = rng.permutation(36 ** 3)[:units]
+    c = rng.permutation(np.repeat(np.arange(100, 116), FIB16)).astype(np.uint8)
+    body = np.empty((units, 4), np.uint8)
+    body[:, 0], body[:, 1], body[:, 2], body[:, 3] = 48 + triples // 1296, 48 + triples // 36 % 36, 48 + triples % 36, c
+    return head + body.tobytes()
+
+
+def length_limit_binds():
+    """A member for which bz_build_lengths must halve: 6,763 units [u v c] and no match at all.  (u, v) are distinct pairs of
+    150 filler bytes, so no 4-gram comes twice and no 3-gram at a distance of 1..4; c is one of 17 other bytes with the counts
+    1, 2, 3, 5, ..., 2584.  With the end-of-block count of 1 these are a Fibonacci chain 16 deep, and the fillers (about 90
+    each) only lengthen it.  (A bucket collision could still verify three equal bytes far away; with this seed none does.)"""
+    counts, k = [1, 2], 150
+    while len(counts) < 17:
+        counts.append(counts[-1] + counts[-2])
+    rng = np.random.default_rng(7)
+    units = sum(counts)
+    pairs = rng.permutation(k * k)[:units]
+    c = rng.permutation(np.repeat(np.arange(k, k + len(counts)), counts)).astype(np.uint8)
+    body = np.empty((units, 3), np.uint8)
+    body[:, 0], body[:, 1], body[:, 2] = pairs // k, pairs % k, c
+    return body.tobytes()
+
+
+# byte values per literal/length code length of code_length_limit_binds (the end-of-block symbol is the second of length 15)
+CL_LIMIT_SHAPE = {7: 89, 8: 55, 9: 34, 10: 21, 11: 5, 12: 1, 13: 1, 14: 1, 15: 1}
+
+
+def code_length_limit_binds():
+    """A member whose code-length code would be 8 deep without its limit of 7: 32,767 bytes in which a byte value with a
+    literal/length code of L bits occurs 2^(15 - L) times (CL_LIMIT_SHAPE: 89 values 256 times each, ... one value once, and the
+    end of the block once), so the lengths are forced, and so are the counts of the lengths in the header: 1, 1, 1, 2 (the two
+    distance codes), 2, 5, 21, 34, 48 (unused), 55, 89.  The bytes are placed in a seeded order in which no 3-gram comes twice:
+    there is no match, and the histogram is exactly this one."""
+    rng = np.random.default_rng(77)
+    pool, value = [], 0
+    for bits, values in CL_LIMIT_SHAPE.items():
+        for _ in range(values):
+            pool += [value] * (1 << (15 - bits))
+            value += 1
+    out, seen, waiting = [], set(), []
+
+    def place(s):
+        gram = (out[-2], out[-1], s) if len(out) >= 2 else len(out)
+        if gram in seen:
+            return False
+        seen.add(gram)
+        out.append(s)
+        return True
+
+    for s in rng.permutation(np.asarray(pool, np.int64)).tolist():
+        if not place(s):
+            waiting.append(s)
+        waiting = [w for w in waiting if not place(w)]
+    assert not waiting
+    return bytes(out)
+
+
+@functools.lru_cache(None)
+def model_inputs():
+    """[(name, text)]: the directed members at which the kernel's own parts (the workgroup scan, the LDS atomics, the bit buffer)
+    can differ from the host lane model; the precondition of each is asserted on the model by tests/test_bgzf_model_streams.py."""
+    rng = np.random.default_rng(4242)
+    db = de_bruijn_prefix()
+    return [
+        # a dynamic block nearly as long as a stored one: the highest words of the bit buffer
+        ("buffer_nearly_full", rng.integers(0, 252, DATA).astype(np.uint8).tobytes()),
+        ("codes_of_15_bits", codes_of_15_bits()),
+        ("length_limit_binds", length_limit_binds()),
+        ("code_length_limit_binds", code_length_limit_binds()),
+        # hundreds of positions of one step in one bucket; a period below and one above BZ_DIRECT
+        ("period2_member", (b"AB" * DATA)[:DATA]),
+        ("period5_member", (b"ACGTN" * DATA)[:DATA]),
+        # a text without a repeat, then 258 random bytes of other values, then the same 258 again as the member's last bytes
+        ("match_258_ends_the_member", db[:1000] + 2 * rng.integers(128, 256, 258).astype(np.uint8).tobytes()),
+    ]
 
 
 def members(text):

@@ -3,6 +3,10 @@
 // then the verified matches, the greedy walk, the tokens; the plan; the header and the tokens at their scanned bit offsets), with
 // every load of the text checked against the member's bounds, and the Huffman length builder runs alone on given histograms.
 // Built with -fsanitize=address,undefined by tests/test_bgzf_lane_model.py and run as a program.
+// Three compile-time switches, for tests/test_bgzf_model_streams.py alone (none set: the kernel's order and the format below):
+//   -DBZ_CHECK_INSERT_FIRST    a step's insertions precede its look-ups (what a missing barrier could give)
+//   -DBZ_CHECK_SMALLEST_WINS   of a step's positions in one bucket the smallest wins (what another order of plain stores could give)
+//   -DBZ_CHECK_HISTOGRAMS      after a member's stream: its 286 literal/length and 30 distance counts as uint32
 //
 //   in : int32 cases, then per case  int32 kind, int32 n,  kind 0: n text bytes;  kind 1: int32 limit, n uint32 counts
 //   out: per case  kind 0: int32 btype, bytes, literals, matches, matched, loads out of bounds, hlit, hdist; 288 + 32 + 19 code
@@ -36,6 +40,24 @@ static inline uint64_t ld64_checked(const uint8_t *text, int i, int n)
 
 static void put32(std::vector<uint8_t> &o, int32_t v) { uint8_t b[4]; memcpy(b, &v, 4); o.insert(o.end(), b, b + 4); }
 
+// the insertions of one step: every bucket ends with the largest position + 1 of the step that fell into it (the kernel's atomic
+// max; positions grow from step to step, so a bucket never holds more than a step's largest)
+static void insert_step(std::vector<uint32_t> &hash, const uint32_t *ha, const uint32_t *hb, int base)
+{
+#ifdef BZ_CHECK_SMALLEST_WINS
+    for (int t = BZ_STEP - 1; t >= 0; t--) {                 // plain stores, the smallest position last
+        if (ha[t] != BZ_NO_HASH) hash[ha[t]] = (uint32_t)(base + t) + 1u;
+        if (hb[t] != BZ_NO_HASH) hash[hb[t]] = (uint32_t)(base + t) + 1u;
+    }
+#else
+    for (int t = 0; t < BZ_STEP; t++) {
+        const uint32_t v = (uint32_t)(base + t) + 1u;
+        if (ha[t] != BZ_NO_HASH && hash[ha[t]] < v) hash[ha[t]] = v;
+        if (hb[t] != BZ_NO_HASH && hash[hb[t]] < v) hash[hb[t]] = v;
+    }
+#endif
+}
+
 static bool member(const uint8_t *text, int n, std::vector<uint8_t> &out)
 {
     if (n < 1 || n > MPB_BGZF_DATA) return false;
@@ -51,14 +73,17 @@ static bool member(const uint8_t *text, int n, std::vector<uint8_t> &out)
             const int p = base + t;
             ha[t] = p < n ? bz_hash_a(text, n, p) : BZ_NO_HASH;
             hb[t] = p < n ? bz_hash_b(text, n, p) : BZ_NO_HASH;
+        }
+#ifdef BZ_CHECK_INSERT_FIRST
+        insert_step(hash, ha, hb, base);
+#endif
+        for (int t = 0; t < BZ_STEP; t++) {
             ca[t] = ha[t] != BZ_NO_HASH ? hash[ha[t]] : 0;
             cb[t] = hb[t] != BZ_NO_HASH ? hash[hb[t]] : 0;
         }
-        for (int t = 0; t < BZ_STEP; t++) {
-            const int p = base + t;
-            if (ha[t] != BZ_NO_HASH && hash[ha[t]] < (uint32_t)p + 1u) hash[ha[t]] = (uint32_t)p + 1u;
-            if (hb[t] != BZ_NO_HASH && hash[hb[t]] < (uint32_t)p + 1u) hash[hb[t]] = (uint32_t)p + 1u;
-        }
+#ifndef BZ_CHECK_INSERT_FIRST
+        insert_step(hash, ha, hb, base);
+#endif
         for (int t = 0; t < BZ_STEP; t++) {
             const int p = base + t;
             len[t] = 0; dist[t] = 0;
@@ -84,6 +109,10 @@ static bool member(const uint8_t *text, int n, std::vector<uint8_t> &out)
     // the dynamic trees as built, for the Kraft sums (bz_plan_block overwrites them when it chooses the fixed code)
     uint8_t ll[BZ_NLL] = {0}, dl[BZ_ND] = {0};
     cd.ll_freq[BZ_EOB] = 1;
+#ifdef BZ_CHECK_HISTOGRAMS
+    std::vector<uint32_t> hist(cd.ll_freq, cd.ll_freq + 286);
+    hist.insert(hist.end(), cd.d_freq, cd.d_freq + 30);
+#endif
     bz_build_lengths(cd.ll_freq, 286, 15, ll, &cd.tree);
     bz_build_lengths(cd.d_freq, 30, 15, dl, &cd.tree);
     bz_plan_block(&cd, n);
@@ -115,6 +144,9 @@ static bool member(const uint8_t *text, int n, std::vector<uint8_t> &out)
     put32(out, (int32_t)cd.matched); put32(out, (int32_t)g_oob); put32(out, cd.hlit); put32(out, cd.hdist);
     out.insert(out.end(), ll, ll + BZ_NLL); out.insert(out.end(), dl, dl + BZ_ND); out.insert(out.end(), cd.cl_len, cd.cl_len + BZ_NCL);
     out.insert(out.end(), stream.begin(), stream.end());
+#ifdef BZ_CHECK_HISTOGRAMS
+    for (uint32_t f : hist) put32(out, (int32_t)f);
+#endif
     return true;
 }
 

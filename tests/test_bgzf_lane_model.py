@@ -2,61 +2,25 @@
 built with -fsanitize=address,undefined and run as a program): whole members go through it in the kernel's order with checked
 loads, zlib inflates what it wrote, and the Huffman length builder runs alone on adversarial histograms.  Every tree's Kraft sum
 is checked.  The kernels themselves: tests/test_gpu_bgzf.py."""
-import os
 import shutil
-import struct
-import subprocess
 from fractions import Fraction
 
-import numpy as np
 import pytest
 
 from helpers import bgzf_inputs as B
+from helpers import bgzf_model as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STORED, FIXED, DYNAMIC = 0, 1, 2
+STORED, FIXED, DYNAMIC = M.STORED, M.FIXED, M.DYNAMIC
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("bgzf_model") / "check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "moira_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "helpers", "bgzf_lane_check.cpp"), "-o", exe])
-    return exe
+    return M.build(str(tmp_path_factory.mktemp("bgzf_model") / "check"), M.SANITIZED)
 
 
-def run(exe, tmp, cases):
-    """cases: [("member", bytes) | ("hist", limit, counts)] -> [dict | code lengths]."""
-    blob = [struct.pack("<i", len(cases))]
-    for c in cases:
-        if c[0] == "member":
-            blob += [struct.pack("<ii", 0, len(c[1])), c[1]]
-        else:
-            blob += [struct.pack("<iii", 1, len(c[2]), c[1]), np.asarray(c[2], np.uint32).tobytes()]
-    fin, fout = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "out.bin")
-    with open(fin, "wb") as f:
-        f.write(b"".join(blob))
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert " 0 loads out of bounds" in r.stdout, r.stdout
-    raw, pos, out = open(fout, "rb").read(), 0, []
-    for c in cases:
-        if c[0] == "member":
-            btype, nbytes, nlit, nmatch, matched, oob, hlit, hdist = struct.unpack_from("<8i", raw, pos)
-            pos += 32
-            ll, dl, cl = raw[pos:pos + 288], raw[pos + 288:pos + 320], raw[pos + 320:pos + 339]
-            pos += 339
-            out.append(dict(btype=btype, stream=raw[pos:pos + nbytes], literals=nlit, matches=nmatch, matched=matched, oob=oob,
-                            hlit=hlit, hdist=hdist, ll=ll, dl=dl, cl=cl))
-            pos += nbytes
-        else:
-            out.append(raw[pos:pos + len(c[2])])
-            pos += len(c[2])
-    assert pos == len(raw)
-    return out
+run = M.run
 
 
 def kraft(lens):
