@@ -14,6 +14,11 @@
 //   case is damaged in way `corrupt` before the run; the pair must then be handed back without a single checked load failing.
 // Output (argv[2]): per case  int32 done, aln_len, score, clen, overlap, gaps, mism;  aln_len bytes aln1, aln_len bytes aln2,
 //   clen bytes contig, clen bytes q + offset.
+// `check --lds out.bin` writes int32 MPB_CONTIG_LDS_MAX, CD_MAX_LEN and cd_lds_bytes(l1, l2) for l1, l2 = 1 .. CD_MAX_LEN (row l1),
+//   so that a test can pick pairs on the size-class boundaries of mpb_contig.cpp without restating the layout.
+// -DCD_CHECK_VARIANT=1 / 2 / 3 builds a deliberately WRONG model, to show that a fixture notices (tests/
+//   test_contig_device_model.py): 1 the column wins the fix-up on cs >= rs, 2 the FIRST maximum of the last column / row instead
+//   of the last, 3 the posterior tables clamped to qualities of 41 or less.  The lane code itself has no such switch.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -32,6 +37,19 @@ static inline int cd_gload8(const uint8_t *p)
     return *p;
 }
 #include "mpb_contig_args.h"
+
+#ifndef CD_CHECK_VARIANT
+#define CD_CHECK_VARIANT 0
+#endif
+
+#if CD_CHECK_VARIANT == 2
+static uint32_t first_max_key(const int16_t *a, int n)
+{
+    int best = 0;
+    for (int k = 1; k < n; k++) if (a[k] > a[best]) best = k;
+    return ((uint32_t)((int)a[best] + 32768) << 16) | (uint32_t)best;
+}
+#endif
 
 struct Result {
     int done = 0, aln_len = 0, score = 0, clen = 0, overlap = 0, gaps = 0, mism = 0;
@@ -72,8 +90,14 @@ static void run_pair(const mpb_pair_row &r, const uint8_t *ftext, const uint8_t 
         const uint32_t a = cd_scan_key(lastcol, sh.l1 + 1, lane), b = cd_scan_key(lastrow, sh.l2 + 1, lane);
         ck = a > ck ? a : ck; rk = b > rk ? b : rk;
     }
+#if CD_CHECK_VARIANT == 2
+    ck = first_max_key(lastcol, sh.l1 + 1); rk = first_max_key(lastrow, sh.l2 + 1);
+#endif
     int bci, bri;
-    const int fix = cd_fixup(sh, ck, rk, &bci, &bri);
+    int fix = cd_fixup(sh, ck, rk, &bci, &bri);
+#if CD_CHECK_VARIANT == 1
+    if (fix) fix = (ck >> 16) >= (rk >> 16) ? 1 : 2;
+#endif
     cd_traceback<C>(sh, prm, s1, s2, ptr, lastcol, lastrow, fix, bci, bri, col, hdr);
     const int K = hdr[0], score = hdr[1], fstart = hdr[2], fend = hdr[3], rstart = hdr[4], rend = hdr[5];
     if (K < 1 || K > sh.l1 + sh.l2) return;
@@ -120,12 +144,27 @@ static int32_t rd32(FILE *f) { int32_t v = 0; if (fread(&v, 4, 1, f) != 1) { fpr
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: check cases.bin out.bin\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: check cases.bin out.bin | check --lds out.bin\n"); return 2; }
+    if (!strcmp(argv[1], "--lds")) {
+        FILE *f = fopen(argv[2], "wb");
+        if (!f) { fprintf(stderr, "cannot open files\n"); return 2; }
+        const int32_t head[2] = {MPB_CONTIG_LDS_MAX, CD_MAX_LEN};
+        fwrite(head, 4, 2, f);
+        for (int l1 = 1; l1 <= CD_MAX_LEN; l1++)
+            for (int l2 = 1; l2 <= CD_MAX_LEN; l2++) { const int32_t v = cd_lds_bytes(l1, l2); fwrite(&v, 4, 1, f); }
+        fclose(f);
+        return 0;
+    }
     FILE *in = fopen(argv[1], "rb"), *outf = fopen(argv[2], "wb");
     if (!in || !outf) { fprintf(stderr, "cannot open files\n"); return 2; }
     std::vector<int32_t> tabs((size_t)2 * 65536);
     // the tables come from the library in the test (written in front of the cases)
     if (fread(tabs.data(), 4, tabs.size(), in) != tabs.size()) { fprintf(stderr, "short tables\n"); return 2; }
+#if CD_CHECK_VARIANT == 3
+    for (int t = 0; t < 2; t++)
+        for (int a = 0; a < 256; a++)
+            for (int b = 0; b < 256; b++) tabs[(size_t)t * 65536 + a * 256 + b] = tabs[(size_t)t * 65536 + std::min(a, 41) * 256 + std::min(b, 41)];
+#endif
     const int n_cases = rd32(in);
     long handed = 0, differ = 0;
     for (int cs = 0; cs < n_cases; cs++) {

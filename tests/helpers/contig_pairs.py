@@ -1,6 +1,6 @@
-"""Read pairs for the device contig tests (tests/test_contig_device_model.py, tests/test_gpu_contigs.py): the two reference
-fixtures as FASTQ-like texts with record indexes, generated pairs of chosen lengths and kinds, and the host's answers
-(moira_amd.contig: mct_nw_align / mct_contigs_from_fastq)."""
+"""Read pairs for the device contig tests (tests/test_contig_device_model.py, tests/test_gpu_contigs.py): the reference
+fixtures (nw_pairs / nw_contigs, and nw_domain: the edges of the domain) as FASTQ-like texts with record indexes, generated pairs
+of chosen lengths and kinds, and the host's answers (moira_amd.contig: mct_nw_align / mct_contigs_from_fastq)."""
 import numpy as np
 
 import golden_io as G
@@ -89,6 +89,50 @@ def fixture_settings():
     """The five (consensus, cap, trim) settings of nw_contigs.npz."""
     c = G.load_set("nw_contigs")
     return [(str(m), int(cap), bool(t)) for m, cap, t in zip(c["modes"], c["caps"], c["trims"])]
+
+
+class DomainCase:
+    """One case of tests/golden/nw_domain.npz: the pair as the FASTQ files hold it (qualities at the case's offset), every
+    parameter, and the REFERENCE's answers -- aln1 / aln2 / score (the Cython aligner), contig / cq (quality bytes at the offset;
+    None where a quality leaves its byte) / stats (make_contig).  built: the device must build it; cause: 0, or why it must hand
+    the pair back (1 the 16-bit predicate, 2 a contig quality above its byte, 3 below zero, 4 the reference raised); part and
+    fixup: see tests/golden/make_nw_domain.py."""
+
+    def group(self):
+        """What one device call fixes: (scoring, consensus, cap, trim, insert, deltaq, offset)."""
+        return (self.prm, self.mode, self.cap, self.trim, self.insert, self.deltaq, self.offset)
+
+
+def fixture_domain():
+    """tests/golden/nw_domain.npz -> [DomainCase]: the edges of the domain (scoring up to the 16-bit predicate, zero / negative /
+    positive parameters, every IUPAC letter, offsets 0 / 33 / 64, qualities up to 128, every consensus setting), from the reference."""
+    if "domain" not in _cache:
+        z = G.load_set("nw_domain")
+        fwd, mate, contig = _strings(z["fwd"], z["foff"]), _strings(z["mate"], z["moff"]), _strings(z["contig"], z["coff"])
+        out = []
+        for k in range(len(fwd)):
+            c = DomainCase()
+            c.k, c.part, c.fixup, c.built, c.cause, c.raised = k, int(z["part"][k]), int(z["fixup"][k]), bool(z["built"][k]), int(z["cause"][k]), bool(z["raised"][k])
+            c.prm = tuple(int(v) for v in z["prm"][k])
+            mode, c.cap, trim, c.insert, c.deltaq, c.offset = (int(v) for v in z["setting"][k])
+            c.mode, c.trim = ("best", "sum", "posterior")[mode], bool(trim)
+            c.q1 = z["q1"][z["foff"][k]:z["foff"][k + 1]].astype(np.int64)
+            c.q2 = z["q2"][z["moff"][k]:z["moff"][k + 1]].astype(np.int64)               # along the mate as it aligns
+            c.mate = mate[k]
+            c.pair = Pair(fwd[k], (c.q1 + c.offset).astype(np.uint8).tobytes(), revcomp(mate[k]), (c.q2[::-1] + c.offset).astype(np.uint8).tobytes())
+            a1, a2, u, v = [], [], 0, 0
+            for mv in z["moves"][z["aoff"][k]:z["aoff"][k + 1]]:                         # 0 both reads, 1 the forward read alone, 2 the mate alone
+                a1.append(fwd[k][u] if mv != 2 else "-"); u += mv != 2
+                a2.append(mate[k][v] if mv != 1 else "-"); v += mv != 1
+            assert (u, v) == (len(fwd[k]), len(mate[k]))
+            c.aln1, c.aln2, c.score = "".join(a1), "".join(a2), int(z["score"][k])
+            c.contig, c.stats = contig[k], tuple(int(v) for v in z["stats"][k])
+            c.cq_ints = z["cq"][z["coff"][k]:z["coff"][k + 1]].astype(np.int64)
+            fits = len(c.cq_ints) == 0 or (c.cq_ints.min() >= 0 and c.cq_ints.max() + c.offset <= 255)
+            c.cq = (c.cq_ints + c.offset).astype(np.uint8).tobytes() if fits else None
+            out.append(c)
+        _cache["domain"] = out
+    return _cache["domain"]
 
 
 def make_pair(rng, l1, l2, kind, qlo=2, qhi=42):

@@ -249,3 +249,94 @@ def test_nw_align_dropin_module_is_the_references(kat):
         a2 = z["aln2"][z["aoff2"][k]:z["aoff2"][k + 1]].tobytes().decode()
         m, mm, g = (int(v) for v in params[z["param"][k]])
         assert nw.nw_align(s1, s2, m, mm, g) == (a1, a2, int(z["score"][k]))
+
+
+# ---- the edges of the domain: tests/golden/nw_domain.npz (tests/golden/make_nw_domain.py) ---------------------------------------
+
+def test_nw_align_on_the_edges_of_the_domain():
+    """Every case of nw_domain.npz -- seventeen scoring sets up to the 16-bit predicate, zero / negative / sign-reversed
+    parameters, lengths on the predicate's boundary and on both sides of it (the 32-bit walk), every outcome of the 3' fix-up,
+    fifteen IUPAC letters -- through both walks of the library: the reference's aligned strings and score."""
+    from helpers import contig_pairs as P
+    fx = P.fixture_domain()
+    assert len({c.prm for c in fx}) >= 19 and sum(c.cause == 1 for c in fx) >= 9
+    bad = []
+    for c in fx:
+        want = (c.aln1, c.aln2, c.score)
+        if CT.nw_align(c.pair.fwd, c.mate, *c.prm) != want:
+            bad.append(("fast", c.k))
+        if CT.nw_align(c.pair.fwd, c.mate, *c.prm, scalar=True) != want:
+            bad.append(("scalar", c.k))
+    assert not bad, bad[:10]
+
+
+def test_contigs_from_fastq_on_the_edges_of_the_domain():
+    """Every case of nw_domain.npz through mct_contigs_from_fastq, one call per (scoring, consensus, cap, trim, insert, deltaq,
+    offset) group: the reference's contig, quality bytes and overlap / gaps / mismatches -- offsets 0 / 33 / 64, qualities
+    0..128, the posterior expressions far outside the 40 x 40 corner of the older fixtures.  Where a contig quality leaves its
+    byte or falls below zero (the reference, working on ints, returns it; it never raised on this fixture) the host raises
+    QualityRange and names the pair."""
+    from helpers import contig_pairs as P
+    fx = P.fixture_domain()
+    assert not any(c.raised for c in fx)
+    groups = {}
+    for c in fx:
+        groups.setdefault(c.group(), []).append(c)
+    bad, refused = [], 0
+    for (prm, mode, cap, trim, insert, deltaq, offset), cs in groups.items():
+        good = [c for c in cs if c.cq is not None]
+        if good:
+            _, _, _, _, cbuf, cidx, aux = P.host_contigs([c.pair for c in good], offset, *prm, insert, deltaq, mode, cap, trim)
+            for c, rec, st in zip(good, P.records(cbuf, cidx), aux):
+                if (rec[1].decode("latin-1"), rec[2], tuple(int(v) for v in st)) != (c.contig, c.cq, c.stats):
+                    bad.append(c.k)
+        for c in cs:
+            if c.cq is None:
+                assert not c.built and c.cause in (1, 2, 3)
+                with pytest.raises(CT.QualityRange, match="a quality of contig 0 does not fit one byte"):
+                    P.host_contigs([c.pair], offset, *prm, insert, deltaq, mode, cap, trim)
+                refused += 1
+    assert not bad, bad[:10]
+    assert refused == sum(c.cq is None for c in fx) >= 10
+
+
+def _cpu_has(isa):
+    flags = set()
+    try:
+        for line in open("/proc/cpuinfo"):
+            if line.startswith("flags"):
+                flags = set(line.split(":", 1)[1].split())
+                break
+    except OSError:
+        pass
+    need = {"generic": set(), "avx2": {"avx2"}, "avx512": {"avx512f", "avx512bw", "avx512vl"}}[isa]
+    return need <= flags
+
+
+@pytest.mark.parametrize("isa", ["generic", "avx2", "avx512"])
+def test_every_fill_variant_reproduces_the_domain_alignments(isa):
+    """The three fills of the 16-bit walk (MOIRA_CONTIG_ISA; chosen once per process, so each runs in a child of its own) on every
+    case of nw_domain.npz: scores close to +-30,000 in 16-bit lanes, saturating or wrapping arithmetic would show here.  A fill
+    this CPU cannot run is skipped, not replaced by another."""
+    import os
+    import subprocess
+    import sys
+    if not _cpu_has(isa):
+        pytest.skip("this CPU lacks the %s instructions: that fill variant cannot run here" % isa)
+    code = r"""
+import sys
+sys.path[:0] = [%r, %r]
+from helpers import contig_pairs as P
+from moira_amd import contig as CT
+fx = P.fixture_domain()
+bad = [c.k for c in fx if CT.nw_align(c.pair.fwd, c.mate, *c.prm) != (c.aln1, c.aln2, c.score)]
+print("checked", len(fx), "bad", len(bad), bad[:10])
+""" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, MOIRA_CONTIG_ISA=isa), timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert " bad 0 " in out.stdout and "checked %d " % _domain_size() in out.stdout, out.stdout
+
+
+def _domain_size():
+    from helpers import contig_pairs as P
+    return len(P.fixture_domain())

@@ -1,7 +1,8 @@
 """k_contig on the GPU, through the C ABI (include/moira_pb.h: mpb_contigs_text_host; Engine.contigs_text,
 moira_amd.contig.contigs_from_fastq(engine=...), the CLI's --device_contigs).  The contract is byte identity with the host
-library (mct_nw_align, mct_contigs_from_fastq), which tests/test_contig.py pins to the reference's fixtures; both fixtures are
-also run here directly.  A slot's bytes past hdr_len + 2 clen are undefined on both sides and are not compared.
+library (mct_nw_align, mct_contigs_from_fastq), which tests/test_contig.py pins to the reference's fixtures; the fixtures
+(nw_pairs / nw_contigs, and nw_domain: the edges of the domain) are also run here directly.  A slot's bytes past
+hdr_len + 2 clen are undefined on both sides and are not compared.
 The per-lane code on the host, with checked loads and damaged descriptors: tests/test_contig_device_model.py."""
 import os
 
@@ -165,6 +166,11 @@ def handback_batch():
     add(good(), True)
     add(P.Pair("ACGTACGTAC", b"IIIIIIIIII", "", b""), False)                        # an empty read: "an aligned read has no bases" on the host
     add(good(), True)
+    p = good(); p.fwd = p.fwd[:-5] + "-" + p.fwd[-4:]                               # a '-' in the forward read, inside the overlap: the host
+    add(p, False)                                                                    # takes it for a gap of the alignment and builds the pair
+    p = good(); p.rev = p.rev[:-5] + "-" + p.rev[-4:]                               # ... in the reverse read
+    add(p, False)
+    add(good(), True)
     return pairs, done
 
 
@@ -172,7 +178,7 @@ def test_hand_back(eng):
     """done is 0 exactly at the pairs the device does not take; every neighbour's slot is the host's."""
     pairs, done = handback_batch()
     assert_equals_host(eng, pairs, mode="sum", cap=0, expect_done=done)
-    assert done.count(False) == 5 and len(pairs) == 12
+    assert done.count(False) == 7 and len(pairs) == 15
     # the same batch under parameters whose scores could leave 16 bits: every pair goes back
     _, r = device(eng, pairs, (500, -700, -900), mode="sum", cap=0)
     assert not r.done.any() and r.n_handed_back == len(pairs)
@@ -204,6 +210,154 @@ def test_contigs_from_fastq_with_an_engine_returns_or_raises_what_the_host_does(
     assert len(seen) == 4 and "an aligned read has no bases" in seen                 # four different errors, each the host's own
     with pytest.raises(ValueError, match="insert must be a positive integer"):
         CT.contigs_from_fastq(*P.texts(pairs[:1]), 33, insert=0, engine=eng)
+
+
+# ---- the edges of the domain: tests/golden/nw_domain.npz, the REFERENCE's answers (tests/golden/make_nw_domain.py) -------------
+
+def assert_index_layout(r, sel, fidx, clens):
+    """The index rows of the built pairs `sel`, as assert_equals_host checks them: the header's length, the contig's twice, and
+    the three pieces back to back at the start of the pair's own slot."""
+    rows = r.cidx[sel]
+    assert np.array_equal(rows[:, 1], fidx[sel, 1]) and np.array_equal(rows[:, 3], clens) and np.array_equal(rows[:, 5], clens)
+    assert np.array_equal(rows[:, 0], sel * r.rec_cap)
+    assert np.array_equal(rows[:, 2], rows[:, 0] + rows[:, 1]) and np.array_equal(rows[:, 4], rows[:, 2] + rows[:, 3])
+
+
+def assert_equals_reference(eng, cases):
+    """One group of nw_domain.npz (one scoring and consensus setting, one offset) in one call with alignments: done is the
+    fixture's `built`, and every built pair carries the reference's aligned strings, score, contig, quality bytes and overlap /
+    gaps / mismatches; a second call without alignments returns the same slots and statistics."""
+    prm, mode, cap, trim, insert, deltaq, offset = cases[0].group()
+    pairs = [c.pair for c in cases]
+    (fbuf, fidx, _, _), r = device(eng, pairs, prm, insert, deltaq, mode, cap, trim, offset)
+    assert r.done.tolist() == [c.built for c in cases], (cases[0].group(), [c.k for c, d in zip(cases, r.done) if d != c.built][:10])
+    sel = np.nonzero(r.done)[0]
+    assert (r.n_done, r.n_handed_back) == (len(sel), len(cases) - len(sel))
+    if not len(sel):
+        return
+    recs, text = P.records(r.cbuf, r.cidx[sel]), fbuf.tobytes()
+    bad = [cases[i].k for n, i in enumerate(sel)
+           if alignment_of(r, i) != (cases[i].aln1, cases[i].aln2, cases[i].score) or
+           (recs[n][1].decode("latin-1"), recs[n][2], tuple(r.aux[i])) != (cases[i].contig, cases[i].cq, cases[i].stats) or
+           recs[n][0] != text[fidx[i, 0]:fidx[i, 0] + fidx[i, 1]]]
+    assert not bad, (cases[0].group(), bad[:10])
+    assert_index_layout(r, sel, fidx, np.array([len(cases[i].contig) for i in sel]))
+    _, q = device(eng, pairs, prm, insert, deltaq, mode, cap, trim, offset, alignments=False)
+    assert np.array_equal(q.done, r.done) and np.array_equal(q.cidx[sel], r.cidx[sel]) and np.array_equal(q.aux[sel], r.aux[sel])
+    assert P.records(q.cbuf, q.cidx[sel]) == recs and q.rec_cap == r.rec_cap
+
+
+DOMAIN_SLICES = {"alignments": lambda c: c.part <= 2, "contigs_offset_33": lambda c: c.part >= 3 and c.offset == 33,
+                 "contigs_offset_64": lambda c: c.part >= 3 and c.offset == 64, "contigs_offset_0": lambda c: c.part >= 3 and c.offset == 0}
+
+
+@pytest.mark.parametrize("which", list(DOMAIN_SLICES))
+def test_reference_domain_fixture(eng, which):
+    """The whole of nw_domain.npz, one call per (scoring, consensus, cap, trim, insert, deltaq, offset) group: scoring sets up to
+    the 16-bit predicate (scores near +-30,000 in the fix-up's packed keys), zero / negative / sign-reversed parameters, every
+    outcome of the 3' fix-up, fifteen IUPAC letters, offsets 0 / 33 / 64, qualities 0..128 (the posterior tables far outside their
+    40 x 40 corner), contig qualities that leave their byte or fall below zero (handed back)."""
+    groups = {}
+    for c in P.fixture_domain():
+        if DOMAIN_SLICES[which](c):
+            groups.setdefault(c.group(), []).append(c)
+    assert len(groups) >= 19 and sum(len(g) for g in groups.values()) >= 250
+    for cases in groups.values():
+        assert_equals_reference(eng, cases)
+
+
+def test_predicate_boundary(eng):
+    """(l1 + l2 + 2) * max|param| against 30,000, four values of max|param|: the fixture's pair just below (29,900..29,999; built,
+    the reference's alignment) and the one at or just above (30,000..30,100; handed back) between ordinary pairs in one call,
+    whose slots are the host's."""
+    rows = [c for c in P.fixture_domain() if c.part == 1]
+    assert len(rows) == 8
+    rng = np.random.default_rng(30000)
+    for below, above in zip(rows[0::2], rows[1::2]):
+        prm, m = below.prm, max(abs(v) for v in below.prm)
+        assert above.prm == prm and below.built and not above.built
+        assert 29900 <= (len(below.pair.fwd) + len(below.pair.rev) + 2) * m <= 29999
+        assert 30000 <= (len(above.pair.fwd) + len(above.pair.rev) + 2) * m <= 30100
+        plain = lambda: P.make_pair(rng, int(rng.integers(20, 60)), int(rng.integers(20, 60)), "overlap")
+        pairs = [plain(), below.pair, plain(), above.pair, plain()]
+        r = assert_equals_host(eng, pairs, prm, expect_done=[True, True, True, False, True])
+        assert alignment_of(r, 1) == (below.aln1, below.aln2, below.score)
+        assert (P.records(r.cbuf, r.cidx[1:2])[0][1:], tuple(r.aux[1])) == ((below.contig.encode("latin-1"), below.cq), below.stats)
+
+
+def lds_size_classes(tmp_path):
+    """(the class caps of mpb_contig.cpp, cd_lds_bytes as an int32[384, 384] of (l1 - 1, l2 - 1)): the caps from the source's
+    own table, the sizes from the model checker's --lds mode, so that nothing of the layout is restated here."""
+    import re
+    import subprocess
+    from test_contig_device_model import build_checker
+    exe, out = build_checker(str(tmp_path / "check")), str(tmp_path / "lds.bin")
+    subprocess.check_call([exe, "--lds", out])
+    raw = np.fromfile(out, np.int32)
+    lds_max, max_len = int(raw[0]), int(raw[1])
+    src = open(os.path.join(ROOT, "moira_amd", "csrc", "mpb_contig.cpp")).read()
+    caps = [lds_max if t.strip() == "MPB_CONTIG_LDS_MAX" else int(t) for t in re.search(r"k_lds_class\[\] = \{([^}]*)\}", src).group(1).split(",")]
+    return caps, raw[2:].reshape(max_len, max_len)
+
+
+def test_lds_size_class_boundaries(eng, tmp_path):
+    """The ten LDS size classes (one launch each): for every cap the pair with the largest cd_lds_bytes not above it and the one
+    with the smallest above it -- the last pair of one launch and the first of the next -- in one call, in shuffled order,
+    each between a C = 1 pair and a C = 6 pair on either side.  Every pair is built and is the host's."""
+    caps, size = lds_size_classes(tmp_path)
+    assert len(caps) == 10 and caps == sorted(caps) and size.max() <= caps[-1] and size.min() <= caps[0]
+    edge = []
+    for cap in caps:
+        fits = np.where(size <= cap, size, -1)
+        edge.append(np.unravel_index(int(fits.argmax()), size.shape))
+        if (size > cap).any():
+            edge.append(np.unravel_index(int(np.where(size > cap, size, 1 << 30).argmin()), size.shape))
+    assert len(edge) == 19                               # no pair of 384 bases or fewer lies above the last cap
+    rng = np.random.default_rng(4096)
+    pairs = []
+    for n in rng.permutation(len(edge)):
+        l1, l2 = int(edge[n][0]) + 1, int(edge[n][1]) + 1
+        small = lambda: P.make_pair(rng, int(rng.integers(1, 385)), int(rng.integers(1, 65)), KINDS[int(rng.integers(0, 5))])
+        large = lambda: P.make_pair(rng, int(rng.integers(1, 385)), int(rng.integers(321, 385)), KINDS[int(rng.integers(0, 5))])
+        pairs += [small(), large(), P.make_pair(rng, l1, l2, KINDS[n % 5]), large(), small()]
+    classes = {int(np.searchsorted(caps, size[len(p.fwd) - 1, len(p.rev) - 1])) for p in pairs}
+    assert classes == set(range(10))
+    assert_equals_host(eng, pairs, mode="posterior")
+
+
+LETTERS = "ACGTNWSRYMKBVDH"
+
+
+def test_bytes_of_the_reads(eng):
+    """One call: a '-' in the forward read and one in the reverse read (handed back: make_contig reads a '-' as a gap of the
+    alignment, only the host reproduces that), a '.' in either read (it has a complement and aligns as a letter of its own: built,
+    as the host library builds it -- the reference itself refuses a '.' in a read that has qualities, its reverse_complement
+    raises LengthMismatchError; nothing is changed here), and each of the fifteen letters as the first and the last base of both
+    reads (the complement of the reverse read's two ends: R <-> Y, M <-> K, B <-> V, D <-> H)."""
+    rng = np.random.default_rng(15)
+    good = lambda: P.make_pair(rng, int(rng.integers(30, 200)), int(rng.integers(30, 200)), "overlap")
+    put = lambda s, at, ch: s[:at] + ch + s[at + 1:]
+    pairs, done = [], []
+    def add(p, d):
+        pairs.append(p); done.append(d)
+    add(good(), True)
+    p = good(); p.fwd = put(p.fwd, len(p.fwd) - 6, "-"); add(p, False)
+    add(good(), True)
+    p = good(); p.rev = put(p.rev, len(p.rev) - 6, "-"); add(p, False)
+    p = good(); p.fwd = put(p.fwd, len(p.fwd) - 6, "."); add(p, True)
+    p = good(); p.rev = put(p.rev, len(p.rev) - 6, "."); add(p, True)
+    p = good(); p.fwd = put(put(p.fwd, 0, "."), len(p.fwd) - 1, "."); p.rev = put(put(p.rev, 0, "."), len(p.rev) - 1, "."); add(p, True)
+    for ch in LETTERS:
+        p = good()
+        p.fwd, p.rev = put(put(p.fwd, 0, ch), len(p.fwd) - 1, ch), put(put(p.rev, 0, ch), len(p.rev) - 1, ch)
+        add(p, True)
+    add(good(), True)
+    for mode in ("best", "posterior"):
+        r = assert_equals_host(eng, pairs, mode=mode, expect_done=done)
+    recs = P.records(r.cbuf, r.cidx)
+    for n, ch in enumerate(LETTERS):                     # the contig begins with the forward read's first base and ends with the
+        contig = recs[7 + n][1].decode("latin-1")        # complement of the reverse record's first
+        assert contig[0] == ch and contig[-1] == P.COMP[ch], (ch, contig)
 
 
 # ---- the CLI ---------------------------------------------------------------------------------------------------------------------

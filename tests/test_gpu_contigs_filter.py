@@ -84,13 +84,14 @@ def test_lengths(eng):
 
 def test_hand_back_interleaved(eng):
     """The mixed batch of tests/test_gpu_contigs.py (reads of 0 and 385 bases, a base without a complement, a quality below the
-    offset, a contig quality past its byte, among eligible pairs): filtered == done, values equal on the built pairs; and through
-    contigs_from_fastq_filtered every pair -- of the sub-batch the host can build at all -- is the all-host path's."""
+    offset, a contig quality past its byte, a '-' in either read, among eligible pairs): filtered == done, values equal on the
+    built pairs; and through contigs_from_fastq_filtered every pair -- of the sub-batch the host can build at all -- is the
+    all-host path's."""
     from test_gpu_contigs import handback_batch
     pairs, done = handback_batch()
     ckw = dict(consensus=P.MODES["sum"], qscore_cap=0)
     g, _ = assert_fused_equals_two_calls(eng, pairs, ckw=ckw, all_built=False)
-    assert g.done.tolist() == done and g.n_handed_back == 5
+    assert g.done.tolist() == done and g.n_handed_back == 7
     buildable = [p for k, p in enumerate(pairs) if k not in (4, 6, 8, 10)]           # (the four the host raises for)
     texts = P.texts(buildable)
     hbuf, hidx, haux = CT.contigs_from_fastq(*texts, 33, consensus_qscore="sum", qscore_cap=0, threads=4)
@@ -205,6 +206,39 @@ def test_filter_refusal(eng):
     assert isinstance(g.filter_error, ValueError) and str(g.filter_error) == str(want.value) and g.filter_error.bad_record == 3
     # ... and the same engine filters the next chunk
     assert_fused_equals_two_calls(eng, [good() for _ in range(5)], 0, ckw)
+
+
+@pytest.mark.parametrize("offset", [33, 64, 0])
+def test_reference_domain_fixture(eng, offset):
+    """The contig cases of tests/golden/nw_domain.npz (qualities 0..128, every consensus setting, exotic scoring, hand-backs in
+    between) at one offset, one fused call per (scoring, consensus, cap, trim, insert, deltaq) group against the two calls it
+    joins: done, slots, ee, ns, pass and the counts are equal; where filter_text refuses the built contigs for a quality out of
+    range, the fused call reports the same error for the same record and counts nothing as filtered."""
+    groups = {}
+    for c in P.fixture_domain():
+        if c.part >= 3 and c.offset == offset:
+            groups.setdefault(c.group(), []).append(c)
+    assert len(groups) >= 50 and sum(len(g) for g in groups.values()) >= 250
+    refused = 0
+    for (prm, mode, cap, trim, insert, deltaq, _), cases in groups.items():
+        ckw = dict(match=prm[0], mismatch=prm[1], gap=prm[2], insert=insert, deltaq=deltaq, consensus=P.MODES[mode], qscore_cap=cap,
+                   trim_overlap=trim)
+        texts = P.texts([c.pair for c in cases])
+        r = eng.contigs_text(*texts, offset, **ckw)
+        assert r.done.tolist() == [c.built for c in cases]
+        sel = np.nonzero(r.done)[0]
+        try:
+            f = eng.filter_text(r.cbuf, r.cidx, sel=sel, fastq_offset=offset)
+        except ValueError as want:
+            g = eng.contigs_filter_text(*texts, offset, **ckw)
+            assert np.array_equal(g.done, r.done) and not g.filtered.any() and g.n_pass == 0
+            assert isinstance(g.filter_error, ValueError) and str(g.filter_error) == str(want)
+            assert g.filter_error.bad_record == want.bad_record and 0 <= want.bad_record < len(sel)
+            assert P.records(g.cbuf, g.cidx[sel]) == P.records(r.cbuf, r.cidx[sel])
+            refused += 1
+            continue
+        assert_fused_equals_two_calls(eng, [c.pair for c in cases], offset, ckw, all_built=False, ref=(r, sel, f))
+    assert (refused >= 1) == (offset == 0)               # the fixture's two contigs with the byte 255 (127 + 128 at offset 0)
 
 
 def test_reuse(eng):
