@@ -660,6 +660,47 @@ int mpb_bgzf_inflate_host(mpb_ctx *ctx, const uint8_t *in, int64_t in_len, const
                           mpb_bgzf_inflate_stats *stats);
 
 /*
+ * RFC 1952's CRC-32 on the device (k_bgzf_crc32, csrc/mpb_crc_kernels.hip): what lets text that the device inflated be trusted
+ * where it lies.  mpb_crc32_ranges_host is the kernel's own entry -- one upload of text[text_bytes] (at most 1 GiB), the kernel,
+ * one read-back: crc_out[k] = the CRC-32 of text[offs[k], offs[k] + lens[k]), equal to zlib's crc32, for n ranges of 0 .. 65536
+ * bytes each at any offset; ranges may overlap, an empty range's CRC is 0.  Argument errors (said before the context is looked
+ * at) are MPB_E_INVALID: a NULL pointer, n or text_bytes negative, a range that does not lie inside the text or is longer than
+ * 65536 bytes (the message names the first such range).  n == 0 launches nothing.  The kernel has no MPB_K_* id of its own: its
+ * launches are timed under MPB_K_BGZF_INFLATE, so after this call alone that slot holds the CRC kernel alone.  Synchronous.
+ */
+int mpb_crc32_ranges_host(mpb_ctx *ctx, const uint8_t *text, int64_t text_bytes, const int64_t *offs, const int32_t *lens, int64_t n,
+                          uint32_t *crc_out);
+
+/*
+ * BGZF FASTQ filtered where it inflates: mpb_bgzf_inflate_host's members in, mpb_filter_fastq_host's results out, and the text
+ * never crosses the link upwards.  The text of the call is `carry` (the partial record the previous call left; may be empty)
+ * followed by the members' text: T = carry_len + out_offs[n_members] bytes, at most 1 GiB; out_offs[0] must be 0.  in, in_len,
+ * offs, sizes, out_offs, n_members, done, member_why (may be NULL), stats (may be NULL) are mpb_bgzf_inflate_host's; everything
+ * from `final` on, except text_out / text_cap, is mpb_filter_fastq_host's, with idx_out, consumed and bad_kind relative to the
+ * call's text, carry included.  In this order: the arguments are checked (with or without a device); mpb_bgzf_member_rows
+ * vouches for the members; the text is carved from the device index's stage; carry and the members' one contiguous range of
+ * compressed bytes are uploaded; k_bgzf_inflate writes every member's text to its place behind the carry; k_bgzf_crc32 computes
+ * the CRC-32 of every vouched-for member's range; status rows and CRC words come back.  done[k] = 1 only when the device took
+ * member k and the CRC equals its trailer's; otherwise member_why[k] is its MPB_BGZF_WHY_* (MPB_BGZF_WHY_CRC: a mismatch).
+ * ALL OR NOTHING: when any member has done = 0, *first_back is the lowest such member, *n = 0, no result and no text is written
+ * and MPB_OK is returned -- the caller inflates the batch on the host and goes through mpb_filter_fastq_host, so every error in
+ * a member's content stays the host decoder's.  When every member was taken (*first_back = -1) the index is built, the records
+ * packed and filtered over the text where it lies, exactly as mpb_filter_fastq_host does from its upload (*why: the index's own
+ * MPB_FQ_WHY_* refusals; MPB_E_RANGE and *bad_record as there), and text_out (may be NULL: no text comes back; else text_cap >= T)
+ * receives the T bytes.  An idx_cap_rows that proves too small is MPB_E_INVALID with *n = the records, as there; asking again
+ * repeats the whole call, inflation included.  k_bgzf_crc32 runs inside MPB_K_BGZF_INFLATE's timing span: after this call that
+ * slot is inflate + CRC.  Synchronous; the staging blocks belong to the context.
+ */
+int mpb_filter_bgzf_fastq_host(mpb_ctx *ctx, const char *carry, int64_t carry_len, const uint8_t *in, int64_t in_len,
+                               const int64_t *offs, const int32_t *sizes, const int64_t *out_offs, int64_t n_members, int32_t final,
+                               int64_t max_records, int32_t max_len, uint8_t *text_out, int64_t text_cap, uint8_t *done,
+                               uint8_t *member_why, int64_t *first_back, mpb_bgzf_inflate_stats *stats, int64_t *idx_out,
+                               int64_t idx_cap_rows, int64_t *n, int64_t *consumed, int32_t *bad_kind, int32_t *why,
+                               int32_t fastq_offset, int32_t lower_n_is_base, const mpb_filter_params *params, int32_t poisson,
+                               double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out,
+                               mpb_filter_counts *counts, int64_t *bad_record);
+
+/*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is
  * cut into n_ctx contiguous, balanced shards in read order, one host thread per context runs mpb_filter_host
  * (poisson == 0) or mpb_filter_poisson_host (poisson != 0) on its shard, and every shard's results land in the

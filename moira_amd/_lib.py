@@ -152,6 +152,12 @@ PROTOTYPES = {
     "mpb_bgzf_member_rows": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "mpb_bgzf_inflate_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
                                         C.POINTER(BgzfInflateStats)]),
+    "mpb_crc32_ranges_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP]),
+    "mpb_filter_bgzf_fastq_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int64,
+                                             C.c_int32, _VP, C.c_int64, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(BgzfInflateStats),
+                                             _VP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(FilterParams), C.c_int32,
+                                             _VP, _VP, _VP, _VP, _VP, C.POINTER(FilterCounts), C.POINTER(C.c_int64)]),
     "mpb_encode_ascii_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP]),
     "mpb_decode_classify_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
                                              C.POINTER(FilterParams), _VP, _VP, _VP, _VP, _VP]),

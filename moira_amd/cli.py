@@ -854,6 +854,9 @@ class _DevicePaths:
         self.pack_refused = _SaidOnce(say, "--device_pack: the device did not take a chunk (%s): host packing is used for it.")
         self.index = "device_index" in on
         self.index_refused = _SaidOnce(say, "--device_index: the device did not take a block (%s): the host indexer is used for it.")
+        self.members_refused = _SaidOnce(say, "--device_inflate with --device_index: the device did not take a batch of members (%s): "
+                                         "it is inflated by the two-call path.")
+        self.members = False                          # the fused BGZF call is taken (set by the run once it knows the filter's engine)
         self.engine = self.compressor = self.inflater = None
         if "device_compress" in on or "device_inflate" in on:
             import threading
@@ -1209,6 +1212,38 @@ def _read_blocks(fh, block_bytes):
     yield _DeferredBlock(b"", True)
 
 
+class _DeferredMembers:
+    """A batch of BGZF members (fastio.GzipReader.read_members) that is still to be inflated, indexed and filtered, by whoever
+    takes it off the queue: with --device_inflate, --device_index and --device_pack together the consumer makes ONE call of it
+    (engine.filter_bgzf_fastq).  The producer thread only reads.  reader: the GzipReader, whose inflate_batch is the way back
+    (it touches nothing the reading thread uses: the batch is a copy).  eof: nothing follows."""
+
+    def __init__(self, batch, reader, eof):
+        self.batch, self.reader, self.eof = batch, reader, eof
+
+
+def _read_members(reader, block_bytes):
+    """The stream as _DeferredMembers while the reader yields batches of BGZF members, as _DeferredBlocks afterwards (or from the
+    start: a gzip file that is not BGZF).  The last item says that the text has ended; one batch is held back to know it."""
+    pending = None
+    while True:
+        batch = reader.read_members(block_bytes)
+        if batch is None:
+            break
+        if pending is not None:
+            yield _DeferredMembers(pending, reader, False)
+        pending = batch
+    data = reader.read(block_bytes)
+    if pending is not None:
+        yield _DeferredMembers(pending, reader, not data)
+        if not data:
+            return
+    while data:
+        yield _DeferredBlock(data, False)
+        data = reader.read(block_bytes)
+    yield _DeferredBlock(b"", True)
+
+
 class _DeviceIndexer:
     """The consumer's side of --device_index: it owns the partial record carried from one block to the next, and makes of every
     block the chunks FastqChunks would have made of it -- (buf, idx, None, (ee, has_n)) -- with one engine.filter_fastq call per
@@ -1216,26 +1251,55 @@ class _DeviceIndexer:
     are yielded first, then its error is raised; trailing lines that do not make a record are dropped at the end of the file.
     A block the device hands back (engine.NotTaken), or whose call ends in a ValueError, is indexed by fastio.index and comes
     without results: the caller filters it as any chunk (--device_pack's text call); the first such block is reported.  A
-    fastio.Unsupported of the host indexer is the run's to take (it starts over with the line parser)."""
+    fastio.Unsupported of the host indexer is the run's to take (it starts over with the line parser).
+    take_members: the same for a batch of BGZF members, with one engine.filter_bgzf_fastq call -- inflate, CRC, index, pack and
+    filter from one upload of compressed bytes; the carry goes along as host bytes.  A batch the device hands back because of a
+    member (engine.MembersNotTaken) is inflated by the reader (so a corrupt member raises the host decoder's OSError, word for
+    word) and goes on through take; the first such batch is reported through members_refused."""
 
-    def __init__(self, engine, filter_kw, max_records, refused, threads=1, not_taken=None):
+    def __init__(self, engine, filter_kw, max_records, refused, threads=1, not_taken=None, members_not_taken=None, members_refused=None):
         if not_taken is None:
             from .engine import NotTaken as not_taken
+        if members_not_taken is None:
+            from .engine import MembersNotTaken as members_not_taken
         self.engine, self.kw, self.max_records, self.refused, self.threads = engine, filter_kw, max_records, refused, threads
         self.not_taken, self.carry = not_taken, b""
+        self.members_not_taken, self.members_refused = members_not_taken, members_refused or refused
 
     def take(self, block):
-        from . import fastio as F
         data = self.carry + block.data if self.carry else block.data
         self.carry = b""
+        yield from self._chunks(data, block.eof)
+
+    def take_members(self, item):
+        carry, self.carry = self.carry, b""
+        first, on_host = None, False
+        try:
+            first = self.engine.filter_bgzf_fastq(*item.batch, carry=carry, final=item.eof, max_records=self.max_records, **self.kw)
+            data = first.text.tobytes()
+        except self.members_not_taken as e:
+            self.members_refused(e)
+            data = carry + item.reader.inflate_batch(item.batch)
+        except (self.not_taken, ValueError) as e:
+            self.refused(e)
+            data, on_host = carry + item.reader.inflate_batch(item.batch), True
+        yield from self._chunks(data, item.eof, first, on_host)
+
+    def _chunks(self, data, eof, first=None, on_host=False):
+        """first: what the fused call made of `data` (its first chunk); on_host: the device refused `data` already."""
+        from . import fastio as F
         while data:
-            filtered = None
-            try:
-                r = self.engine.filter_fastq(data, final=block.eof, max_records=self.max_records, **self.kw)
+            filtered, r = None, first
+            if r is None and not on_host:
+                try:
+                    r = self.engine.filter_fastq(data, final=eof, max_records=self.max_records, **self.kw)
+                except (self.not_taken, ValueError) as e:
+                    self.refused(e)
+            if r is not None:
                 idx, consumed, err, filtered = r.idx, r.consumed, r.bad, (r.ee, r.has_n)
-            except (self.not_taken, ValueError) as e:
-                self.refused(e)
-                idx, consumed, err = F.index(data, block.eof, self.max_records, self.threads)
+            else:
+                idx, consumed, err = F.index(data, eof, self.max_records, self.threads)
+            first, on_host = None, False
             if len(idx):
                 yield data, idx, None, filtered
             if err is not None:
@@ -1243,8 +1307,19 @@ class _DeviceIndexer:
             data = data[consumed:]
             if len(idx) < self.max_records:
                 break                                   # the rest is an incomplete record: it waits for the next block
-        if not block.eof:
+        if not eof:
             self.carry = data
+
+
+def _members_reader(filename, threads, inflater):
+    """The file's GzipReader when it is a gzip file that the package's own reader takes, else None (the fused BGZF call reads
+    members, not text: no read-ahead thread stands between)."""
+    with io.open(filename, "rb") as fh:
+        start = fh.read(3)
+    if not start.startswith(b"\x1f\x8b\x08") or os.environ.get("MOIRA_ZLIB_INPUT"):
+        return None
+    from . import fastio as F
+    return F.GzipReader(io.open(filename, "rb", buffering=0), threads=threads, inflater=inflater)
 
 
 def _fast_chunks(args, paths, contig_engine=None, fused=None):
@@ -1256,6 +1331,14 @@ def _fast_chunks(args, paths, contig_engine=None, fused=None):
         yield from _fast_chunks_fasta_qual(args, paths, contig_engine)
         return
     if not args.paired:
+        # --device_inflate, --device_index and --device_pack together: BGZF members go to the consumer as they are (one fused call)
+        fh = _members_reader(args.forward_fastq, _text_threads(args), paths.inflater) if paths.members else None
+        if fh is not None:
+            try:
+                yield from _read_members(fh, DEVICE_INDEX_BLOCK)
+            finally:
+                fh.close()
+            return
         fh = open_input_binary(args.forward_fastq, _text_threads(args), paths.inflater)
         try:
             if paths.index:
@@ -1498,16 +1581,17 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
         if paths.index:
             indexer = _DeviceIndexer(backend.engine, dict(fastq_offset=in_off, max_len=T, lower_n_is_base=n_is_base,
                                                           **backend.text_choice(args.alpha, args.ambigs, args.round, method, fd)),
-                                     CHUNK_READS, paths.index_refused, threads)
+                                     CHUNK_READS, paths.index_refused, threads, members_refused=paths.members_refused)
+            paths.members = paths.inflater is not None and hasattr(backend.engine, "filter_bgzf_fastq")
 
         def chunks():
             # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context; with
             # --device_pack as well they are filtered where they lie, in the same call.  --device_index: the same for a block
             # of text, which may hold several chunks, or none)
             for chunk in _prefetched(_fast_chunks(args, paths, backend.engine if paths.contigs else None, fused)):
-                if isinstance(chunk, _DeferredBlock):
+                if isinstance(chunk, (_DeferredBlock, _DeferredMembers)):
                     try:
-                        yield from indexer.take(chunk)
+                        yield from (indexer.take(chunk) if isinstance(chunk, _DeferredBlock) else indexer.take_members(chunk))
                     except F.RecordError as e:
                         raise _record_error(0, e, args)
                 else:

@@ -1,6 +1,7 @@
 // mpb_ctx.h -- the context of the C ABI (struct mpb_ctx) and what the GPU-facing host units share: the error macros, the owner of
 // a growable block (Buf), the carver that lays a block out (Carver), the timing span, and the few functions that cross units
-// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp, mpb_text.cpp, mpb_index.cpp).  Not installed.
+// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp, mpb_text.cpp, mpb_index.cpp,
+// mpb_bgzf_fastq.cpp).  Not installed.
 #ifndef MPB_CTX_H
 #define MPB_CTX_H
 
@@ -267,6 +268,46 @@ int filter_text_pieces(mpb_ctx *c, const uint8_t *d_text, int64_t text_bytes, co
 // the device tail -- the reference's scalar tail on the host; *n_pass is the piece loop's count going in, the call's going out.
 int text_results_out(mpb_ctx *c, const TextStage &st, int64_t n, const mpb_filter_params *params, int32_t poisson, double *ee,
                      int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, int64_t *n_pass);
+// mpb_index.cpp: the device FASTQ index, shared with mpb_bgzf_fastq.cpp (which inflates the text into the index's own stage)
+const int64_t k_text_max_bytes = 1ll << 30;                 // the text of one call (mpb_filter_text_host's limit)
+
+// text | tile table | prefix | head | status: sized from the text alone
+struct FastqStage {
+    uint8_t *text; uint32_t *info, *prefix, *head; int64_t *status;
+    void layout(Carver &k, int64_t text_bytes, int64_t n_tiles)
+    {
+        k.take(text, align_up(text_bytes > 0 ? text_bytes : 1, 16));
+        k.take(info, n_tiles > 0 ? n_tiles : 1);
+        k.take(prefix, n_tiles > 0 ? n_tiles : 1);
+        k.take(head, 4);
+        k.take(status, 4);
+    }
+};
+
+// line starts | index rows | kinds | descriptors: sized from the counted lines
+struct FastqIndex {
+    uint32_t *start; int64_t *idx; uint8_t *kinds; mpb_text_row *desc;
+    void layout(Carver &k, int64_t n_start, int64_t rows)
+    {
+        k.take(start, n_start);
+        k.take(idx, rows * MPB_IDX_COLS);
+        k.take(kinds, rows);
+        k.take(desc, rows);
+    }
+};
+
+struct Indexed {                                             // what the device made of a text it took
+    FastqStage st{};
+    FastqIndex ix{};
+    int64_t n = 0, rows = 0, longest = 0;                    // records; rows of the index (n, or n + 1: the offender's); longest packed length
+};
+// k_fq_lines, k_fq_scan and the copy of the head words to the pinned block, queued over the text that lies in out.st.text; after
+// the caller's synchronisation fastq_index_finish does the rest (*why != 0: handed back; the stream is synchronised when it
+// returns); queue_index_out queues the copies of the index's rows, the offender's kind and the first byte behind the last record
+hipError_t fastq_index_queue_head(mpb_ctx *c, Indexed &out, int64_t text_bytes, int32_t final);
+int fastq_index_finish(mpb_ctx *c, int64_t text_bytes, int64_t max_records, int32_t max_len, int64_t idx_cap_rows, int64_t *n_needed,
+                       Indexed &out, int32_t *why);
+hipError_t queue_index_out(mpb_ctx *c, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8);
 // mpb_perread.cpp: the per-read entry's resident kernel leaves (before anything is freed: the runtime waits for the whole
 // device there); ... and its stream and blocks go
 void serve_quiesce(mpb_ctx *c);

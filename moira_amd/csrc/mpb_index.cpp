@@ -10,39 +10,6 @@
 
 namespace {
 
-const int64_t k_text_max_bytes = 1ll << 30;                 // the text of one call (mpb_filter_text_host's limit)
-
-// text | tile table | prefix | head | status: sized from the text alone
-struct FastqStage {
-    uint8_t *text; uint32_t *info, *prefix, *head; int64_t *status;
-    void layout(Carver &k, int64_t text_bytes, int64_t n_tiles)
-    {
-        k.take(text, align_up(text_bytes > 0 ? text_bytes : 1, 16));
-        k.take(info, n_tiles > 0 ? n_tiles : 1);
-        k.take(prefix, n_tiles > 0 ? n_tiles : 1);
-        k.take(head, 4);
-        k.take(status, 4);
-    }
-};
-
-// line starts | index rows | kinds | descriptors: sized from the counted lines
-struct FastqIndex {
-    uint32_t *start; int64_t *idx; uint8_t *kinds; mpb_text_row *desc;
-    void layout(Carver &k, int64_t n_start, int64_t rows)
-    {
-        k.take(start, n_start);
-        k.take(idx, rows * MPB_IDX_COLS);
-        k.take(kinds, rows);
-        k.take(desc, rows);
-    }
-};
-
-struct Indexed {                                             // what the device made of a text it took
-    FastqStage st{};
-    FastqIndex ix{};
-    int64_t n = 0, rows = 0, longest = 0;                    // records; rows of the index (n, or n + 1: the offender's); longest packed length
-};
-
 int check_args(const char *text, int64_t text_bytes, int64_t max_records, int32_t max_len, const int64_t *idx_out, int64_t idx_cap_rows,
                const int64_t *n, const int64_t *consumed, const int32_t *bad_kind, const int32_t *why, const char *who)
 {
@@ -55,31 +22,35 @@ int check_args(const char *text, int64_t text_bytes, int64_t max_records, int32_
     return MPB_OK;
 }
 
-// Upload, the four kernels and the two small read-backs.  *why != 0: handed back.  The index stays on the device (out.ix); the
+}  // namespace
+
+// k_fq_lines, k_fq_scan and the copy of the head words to the pinned block, queued over the text that lies in out.st.text
+hipError_t fastq_index_queue_head(mpb_ctx *c, Indexed &out, int64_t text_bytes, int32_t final)
+{
+    hipStream_t s = c->stream;
+    const int64_t n_tiles = (text_bytes + MPB_FQ_TILE - 1) / MPB_FQ_TILE;
+    FastqStage &st = out.st;
+    { Span t(c, MPB_K_FQ_LINES); mpb_launch_fq_lines(st.text, text_bytes, n_tiles, st.info, s); }
+    { Span t(c, MPB_K_FQ_SCAN); mpb_launch_fq_scan(st.text, text_bytes, final != 0, st.info, n_tiles, st.prefix, st.head, s); }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pin->fq_head, st.head, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    return e;
+}
+
+// What follows the synchronisation behind fastq_index_queue_head: the head words' verdict, the blocks sized from the counted
+// lines, k_fq_starts, k_fq_rows and its small read-back.  *why != 0: handed back.  The index stays on the device (out.ix); the
 // stream is synchronised when this returns, whatever it returns.
-int index_on_device(mpb_ctx *c, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
-                    int64_t idx_cap_rows, int64_t *n_needed, Indexed &out, int32_t *why)
+int fastq_index_finish(mpb_ctx *c, int64_t text_bytes, int64_t max_records, int32_t max_len, int64_t idx_cap_rows, int64_t *n_needed,
+                       Indexed &out, int32_t *why)
 {
     *why = MPB_FQ_WHY_TAKEN;
     hipStream_t s = c->stream;
     const int64_t n_tiles = (text_bytes + MPB_FQ_TILE - 1) / MPB_FQ_TILE;
     FastqStage &st = out.st;
-    int rc;
-    if ((rc = carve(c, c->fastq_stage, [&](Carver &k) { st.layout(k, text_bytes, n_tiles); }))) return rc;
-    uint32_t *head = c->pin->fq_head;
+    const uint32_t *head = c->pin->fq_head;
     int64_t *status = c->pin->fq_status;
-    // (everything below is queued on one stream; the host blocks it reads from -- the caller's text, the pinned words -- outlive
-    // the synchronisation that every path out of here passes)
-    hipError_t e = hipSuccess;
-    if (text_bytes > 0) e = hipMemcpyAsync(st.text, text, (size_t)text_bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (text upload)", e); }
-    { Span t(c, MPB_K_FQ_LINES); mpb_launch_fq_lines(st.text, text_bytes, n_tiles, st.info, s); }
-    { Span t(c, MPB_K_FQ_SCAN); mpb_launch_fq_scan(st.text, text_bytes, final != 0, st.info, n_tiles, st.prefix, st.head, s); }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(head, st.head, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    hipError_t e_sync = hipStreamSynchronize(s);
-    HIPCHK_KEPT("k_fq_lines / k_fq_scan", e);
-    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    hipError_t e = hipSuccess, e_sync = hipSuccess;
+    int rc;
     if (head[1] & 2u) { *why = MPB_FQ_WHY_LONE_CR; return MPB_OK; }
     if (head[1] & 1u) { *why = MPB_FQ_WHY_NON_ASCII; return MPB_OK; }
     // the counted lines size the rest
@@ -127,6 +98,33 @@ int index_on_device(mpb_ctx *c, const char *text, int64_t text_bytes, int32_t fi
     return MPB_OK;
 }
 
+namespace {
+
+// Upload, the four kernels and the two small read-backs.  *why != 0: handed back.  The index stays on the device (out.ix); the
+// stream is synchronised when this returns, whatever it returns.
+int index_on_device(mpb_ctx *c, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
+                    int64_t idx_cap_rows, int64_t *n_needed, Indexed &out, int32_t *why)
+{
+    *why = MPB_FQ_WHY_TAKEN;
+    hipStream_t s = c->stream;
+    const int64_t n_tiles = (text_bytes + MPB_FQ_TILE - 1) / MPB_FQ_TILE;
+    FastqStage &st = out.st;
+    int rc;
+    if ((rc = carve(c, c->fastq_stage, [&](Carver &k) { st.layout(k, text_bytes, n_tiles); }))) return rc;
+    // (everything below is queued on one stream; the host blocks it reads from -- the caller's text, the pinned words -- outlive
+    // the synchronisation that every path out of here passes)
+    hipError_t e = hipSuccess;
+    if (text_bytes > 0) e = hipMemcpyAsync(st.text, text, (size_t)text_bytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (text upload)", e); }
+    e = fastq_index_queue_head(c, out, text_bytes, final);
+    const hipError_t e_sync = hipStreamSynchronize(s);
+    HIPCHK_KEPT("k_fq_lines / k_fq_scan", e);
+    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    return fastq_index_finish(c, text_bytes, max_records, max_len, idx_cap_rows, n_needed, out, why);
+}
+
+}  // namespace
+
 // the rows of the index, the offender's kind and the first byte behind the last record, queued for the caller's arrays
 hipError_t queue_index_out(mpb_ctx *c, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8)
 {
@@ -137,8 +135,6 @@ hipError_t queue_index_out(mpb_ctx *c, const Indexed &in, int64_t *idx_out, uint
     if (e == hipSuccess && in.rows > in.n) e = hipMemcpyAsync(kind8, in.ix.kinds + in.n, 1, hipMemcpyDeviceToHost, s);
     return e;
 }
-
-}  // namespace
 
 int mpb_fastq_index_host(mpb_ctx *c, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
                          int64_t *idx_out, int64_t idx_cap_rows, int64_t *n, int64_t *consumed, int32_t *bad_kind, int32_t *why)

@@ -278,6 +278,13 @@ void mpb_launch_fq_starts(const uint8_t *text, int64_t text_bytes, int64_t n_til
                           uint32_t *start, int64_t n_start, hipStream_t s);
 void mpb_launch_fq_rows(const uint8_t *text, int64_t text_bytes, const uint32_t *start, int64_t n_start, int64_t n, int32_t max_len,
                         int64_t *idx, uint8_t *kinds, mpb_text_row *desc, int64_t *status, hipStream_t s);
+// RFC 1952's CRC-32 on the device (mpb_crc_kernels.hip; what a lane does: mpb_crc_lane.inc).  k_bgzf_crc32: one wave per range of
+// ranges[n] over text[text_bytes] (a 16-byte aligned block; 0 <= len <= MPB_CRC_RANGE_MAX, any off) -> crc[k], bad[k] = 0; a range
+// that does not lie inside the text is checked again in the kernel: crc[k] = 0, bad[k] = 1, nothing read
+#define MPB_CRC_RANGE_MAX 65536
+struct mpb_crc_range { int64_t off; int32_t len, pad; };     // 16 bytes
+void mpb_launch_bgzf_crc32(const uint8_t *text, int64_t text_bytes, const mpb_crc_range *ranges, int64_t n, uint32_t *crc,
+                           uint32_t *bad, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

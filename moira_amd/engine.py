@@ -86,6 +86,27 @@ class FastqFilterResult(TextFilterResult):
         self.idx, self.consumed, self.bad = idx, consumed, bad
 
 
+class MembersNotTaken(Exception):
+    """Engine.filter_bgzf_fastq handed a batch back because of one of its members: .first is the lowest member that was not
+    taken, .done (uint8 per member) is 1 where the device took the member and its CRC-32 matched, .why (uint8 per member) is
+    MPB_BGZF_WHY_* (names: _lib.BGZF_WHY).  Nothing was filtered: the caller inflates the batch on the host, whose decoder raises
+    whatever there is to raise, and goes on through Engine.filter_fastq."""
+
+    def __init__(self, first, done, why):
+        w = int(why[first])
+        Exception.__init__(self, "member %d: %s" % (first, L.BGZF_WHY[w] if 0 <= w < len(L.BGZF_WHY) else "reason %d" % w))
+        self.first, self.done, self.why = first, done, why
+
+
+class BgzfFastqFilterResult(FastqFilterResult):
+    """FastqFilterResult of Engine.filter_bgzf_fastq, with .text (a uint8 array: the carry followed by the inflated members, or
+    None when the caller did not ask for it) and .member_stats (the call's mpb_bgzf_inflate_stats as a dict)."""
+
+    def __init__(self, text, member_stats, *a):
+        FastqFilterResult.__init__(self, *a)
+        self.text, self.member_stats = text, member_stats
+
+
 TEXT_ROW_DTYPE = np.dtype([("seq_off", "<i8"), ("qual_off", "<i8"), ("len", "<i4"), ("pad", "<i4")])     # mpb_text_row
 
 
@@ -116,11 +137,12 @@ def _check_text(rc, bad):
 
 
 def _record_error(buf, idx, n, kind):
-    """fastio.index's third value from a device-built index: None, or the RecordError of row n (.row: its six columns)."""
+    """fastio.index's third value from a device-built index: None, or the RecordError of row n (.row: its six columns; the
+    header is None where the caller holds no text)."""
     if not kind:
         return None
     from . import fastio
-    err = fastio.RecordError(kind, fastio.header_of(buf, idx[n]))
+    err = fastio.RecordError(kind, fastio.header_of(buf, idx[n]) if buf is not None else None)
     err.row = idx[n].copy()
     return err
 
@@ -434,6 +456,83 @@ class Engine:
         ee, ns, ps, lens, flags = out["a"]
         return FastqFilterResult(idx[:n], consumed, _record_error(buf, idx, n, bad), ee[:n], ns[:n], ps[:n].view(bool), lens[:n],
                                  flags[:n].view(bool), counts.n_pass, counts.n_overflow)
+
+    # ---- BGZF FASTQ filtered where it inflates (k_bgzf_inflate, k_bgzf_crc32, the index, the pack) ----
+    def crc32_ranges(self, buf, offs, lens):
+        """The CRC-32 (zlib.crc32's) of buf[offs[k] : offs[k] + lens[k]] for every k, computed on the device (mpb_crc32_ranges_host:
+        one upload, k_bgzf_crc32, one read-back) -> a uint32 array.  A range holds 0 .. 65536 bytes at any offset; ranges may
+        overlap.  ValueError for a range outside the text.  The kernel is timed under kernel_times()["bgzf_inflate"]."""
+        keep, addr, nbytes = _text_ptr(buf)
+        offs = np.ascontiguousarray(offs, np.int64)
+        lens = np.ascontiguousarray(lens, np.int32)
+        if offs.ndim != 1 or offs.shape != lens.shape:
+            raise ValueError("crc32_ranges: offs and lens must be one-dimensional and equally long")
+        out = np.zeros(len(offs), np.uint32)
+        L.check(self.lib.mpb_crc32_ranges_host(self.ctx, addr, nbytes, offs.ctypes.data, lens.ctypes.data, len(offs), out.ctypes.data))
+        del keep
+        return out
+
+    def filter_bgzf_fastq(self, data, offs, sizes, out_offs, carry=b"", final=True, max_records=None, fastq_offset=33, max_len=0,
+                          lower_n_is_base=False, poisson=False, text=True, **kw):
+        """The BGZF members of `data` (bgzf_inflate's arguments) holding FASTQ text, behind `carry` (the partial record the call
+        before left) -> BgzfFastqFilterResult: compressed bytes go up, the members are inflated into the buffer the device
+        indexes, their CRC-32 is checked there, and the records are packed and filtered where they lie
+        (mpb_filter_bgzf_fastq_host).  Results are filter_fastq's on carry + the inflated text, bit for bit; .idx, .consumed and
+        .bad are relative to that text, which comes back as .text unless text=False (.bad then has no header); text may also be
+        a uint8 array to write it into (.text is then a view of it).
+        MembersNotTaken when a member is handed back (nothing was filtered); NotTaken(why) when the index hands the text back;
+        ValueError for a quality character out of range (.bad_record).  `kw` as filter()'s."""
+        params = kw.pop("params", None) or self.params(**kw)
+        src = data if isinstance(data, np.ndarray) else np.frombuffer(memoryview(data).cast("B"), np.uint8)
+        offs = np.ascontiguousarray(offs, np.int64)
+        sizes = np.ascontiguousarray(sizes, np.int32)
+        out_offs = np.ascontiguousarray(out_offs, np.int64)
+        m = len(offs)
+        if src.dtype != np.uint8 or not src.flags.c_contiguous or len(sizes) != m or len(out_offs) != m + 1:
+            raise ValueError("filter_bgzf_fastq: data must be contiguous bytes, sizes as long as offs, out_offs one longer")
+        ckeep, caddr, clen = _text_ptr(carry)
+        total = clen + int(out_offs[m])
+        if isinstance(text, np.ndarray):                     # the caller's own buffer (one that earlier calls have touched is
+            tbuf = text                                       # filled several times faster than fresh pages are)
+            if tbuf.dtype != np.uint8 or not tbuf.flags.c_contiguous or tbuf.ndim != 1 or len(tbuf) < total:
+                raise ValueError("filter_bgzf_fastq: text must be a contiguous uint8 array of at least %d bytes" % total)
+            text = True
+        else:
+            tbuf = np.empty(max(total, 1), np.uint8) if text else None
+        done, mwhy, st = np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.uint8), L.BgzfInflateStats()
+        first = C.c_int64(-1)
+        counts, badrec = L.FilterCounts(), C.c_int64(-1)
+        limit = (1 << 62) if max_records is None else int(max_records)
+        if limit < 0:
+            raise ValueError("max_records must not be negative")
+        cap = min(limit, total // 64 + 64) + 1                # (_fastq_call's guess, and its single retry)
+        while True:
+            idx = np.empty((cap, 6), np.int64)
+            ee, ns, ps, lens, flags = (np.empty(cap, np.float64), np.empty(cap, np.int32), np.empty(cap, np.uint8),
+                                       np.empty(cap, np.int32), np.empty(cap, np.uint8))
+            n, consumed, bad, why = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+            rc = self.lib.mpb_filter_bgzf_fastq_host(
+                self.ctx, caddr if clen else None, clen, src.ctypes.data, len(src), offs.ctypes.data, sizes.ctypes.data,
+                out_offs.ctypes.data, m, 1 if final else 0, limit, int(max_len), tbuf.ctypes.data if text else None,
+                len(tbuf) if text else 0, done.ctypes.data, mwhy.ctypes.data, C.byref(first), C.byref(st), idx.ctypes.data, cap,
+                C.byref(n), C.byref(consumed), C.byref(bad), C.byref(why), int(fastq_offset), 1 if lower_n_is_base else 0,
+                C.byref(params), 1 if poisson else 0, ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data,
+                flags.ctypes.data, C.byref(counts), C.byref(badrec))
+            if rc == L.E_INVALID and first.value < 0 and n.value + 1 > cap and cap < limit + 1:
+                cap = n.value + 1                            # the text holds more records than the guess: the whole call once more
+                continue
+            break
+        del ckeep
+        _check_text(rc, badrec)
+        stats = {k: int(getattr(st, k)) for k, _ in L.BgzfInflateStats._fields_}
+        if first.value >= 0:
+            raise MembersNotTaken(first.value, done[:m], mwhy[:m])
+        if why.value:
+            raise NotTaken(why.value)
+        n = n.value
+        tout = tbuf[:total] if text else None
+        return BgzfFastqFilterResult(tout, stats, idx[:n], consumed.value, _record_error(tout, idx, n, bad.value), ee[:n], ns[:n],
+                                     ps[:n].view(bool), lens[:n], flags[:n].view(bool), counts.n_pass, counts.n_overflow)
 
     # ---- paired-read contigs on the device (mpb_pair_rows, k_contig) ------------------------------
     @staticmethod

@@ -429,8 +429,10 @@ class GzipReader:
             out, self.ready = self.ready[:n], self.ready[n:]
         return out
 
-    def _decode_bgzf(self, n):
-        """Up to about n bytes from whole BGZF members, or None once the input is not (or no longer) BGZF."""
+    def _scan_bgzf(self, n):
+        """The next batch of whole BGZF members holding up to about n bytes of text: the number of members, which the arrays
+        of self._bg describe over inbuf[in_pos:in_len] (nothing is consumed yet); b"" when the input ended on a member
+        boundary; None once the input is not (or no longer) BGZF."""
         if not hasattr(self, "_bg"):
             m = self.MAX_BGZF
             self._bg = (np.empty(m, np.int64), np.empty(m, np.int32), np.empty(m + 1, np.int64), C.c_int32(0))
@@ -447,7 +449,7 @@ class GzipReader:
             if nb < 0:
                 raise OSError("gzip input: " + self.L.mio_inflate_error().decode())
             if nb > 0:
-                break
+                return nb
             if why.value == 0 and self._more_input():
                 continue                                       # the member at the end of the buffer was incomplete
             self.bgzf = False                                  # not BGZF, or a truncated tail: the serial decoder says which
@@ -460,17 +462,21 @@ class GzipReader:
                     self.done = True
                     return b""
             return None
+
+    def _inflate_members(self, data, offs, sizes, out_offs, nb):
+        """The text of nb scanned members: `data` is a uint8 array that starts at the first member and has eight readable bytes
+        behind its end (the host decoder reads whole words); the inflater first when there is one, then the host decoder."""
         total = int(out_offs[nb])
         out = np.empty(max(total, 1), np.uint8)
         done = None
         if self.inflater is not None:
             try:
-                done = self.inflater(self.inbuf[self.in_pos:self.in_len], offs[:nb], sizes[:nb], out_offs[:nb + 1], out)
+                done = self.inflater(data, offs[:nb], sizes[:nb], out_offs[:nb + 1], out)
             except Exception as e:                             # noqa: B902 -- the whole batch goes to the host decoder
                 if hasattr(self.inflater, "report"):
                     self.inflater.report(e)
         if done is None:
-            rc = self.L.mio_bgzf_inflate_mt(self.inbuf.ctypes.data + self.in_pos, offs.ctypes.data, sizes.ctypes.data,
+            rc = self.L.mio_bgzf_inflate_mt(data.ctypes.data, offs.ctypes.data, sizes.ctypes.data,
                                             out_offs.ctypes.data, nb, out.ctypes.data, self.threads)
             if rc < 0:
                 raise OSError("gzip input: " + self.L.mio_inflate_error().decode())
@@ -478,16 +484,50 @@ class GzipReader:
             self.inflater_members += nb
             for k in np.flatnonzero(np.asarray(done[:nb]) == 0).tolist():      # in order: the lowest bad member's error
                 self.inflater_handed_back += 1
-                rc = self.L.mio_bgzf_inflate_mt(self.inbuf.ctypes.data + self.in_pos, offs[k:].ctypes.data, sizes[k:].ctypes.data,
+                rc = self.L.mio_bgzf_inflate_mt(data.ctypes.data, offs[k:].ctypes.data, sizes[k:].ctypes.data,
                                                 out_offs[k:].ctypes.data, 1, out.ctypes.data, 1)
                 if rc < 0:
                     msg = self.L.mio_inflate_error().decode()
                     if msg.startswith("BGZF block 0:"):        # (that call saw one member: its number in the batch)
                         msg = "BGZF block %d:%s" % (k, msg[len("BGZF block 0:"):])
                     raise OSError("gzip input: " + msg)
+        return out[:total].tobytes()
+
+    def _decode_bgzf(self, n):
+        """Up to about n bytes from whole BGZF members, or None once the input is not (or no longer) BGZF."""
+        nb = self._scan_bgzf(n)
+        if nb is None or nb == b"":
+            return nb
+        offs, sizes, out_offs, _ = self._bg
+        text = self._inflate_members(self.inbuf[self.in_pos:self.in_len], offs, sizes, out_offs, nb)
         self.in_pos += int(offs[nb - 1]) + int(sizes[nb - 1])
         self.bgzf_batches += 1
-        return out[:total].tobytes()
+        return text
+
+    def read_members(self, n=1 << 25):
+        """The next batch of whole BGZF members holding up to about n bytes of text, NOT inflated: (data, offs, sizes, out_offs),
+        mio_bgzf_scan's arrays over the uint8 array `data` (copies: they stay valid).  None once the input is not, or no longer,
+        BGZF (or when text decoded ahead is waiting): from then on read() serves the text as ever -- the first-member check, zero
+        padding and a truncated tail are decided by the code that decides them for read().  inflate_batch() turns a batch into
+        the text read() would have returned for it."""
+        if not self.bgzf or self.ready or self.done:
+            return None
+        nb = self._scan_bgzf(n)
+        if nb is None or nb == b"":
+            return None
+        offs, sizes, out_offs, _ = self._bg
+        end = int(offs[nb - 1]) + int(sizes[nb - 1])
+        data = np.zeros(end + 8, np.uint8)                     # (eight readable bytes behind the end: _inflate_members)
+        data[:end] = self.inbuf[self.in_pos:self.in_pos + end]
+        self.in_pos += end
+        self.bgzf_batches += 1
+        return data[:end], offs[:nb].copy(), sizes[:nb].copy(), out_offs[:nb + 1].copy()
+
+    def inflate_batch(self, batch):
+        """The text of a batch read_members() returned: the inflater when there is one, then the host decoder, with read()'s
+        errors word for word."""
+        data, offs, sizes, out_offs = batch
+        return self._inflate_members(data, offs, sizes, out_offs, len(offs))
 
     def _decode(self, n):
         while self.bgzf:
