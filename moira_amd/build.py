@@ -31,6 +31,7 @@ CRC_KERNELS = os.path.join(CSRC, "mpb_crc_kernels.hip")            # k_bgzf_crc3
 SOURCES = [os.path.join(CSRC, "mpb_kernels.hip"), CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS] + HOST_SOURCES
 DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_host_internal.h"),
                   os.path.join(CSRC, "mpb_shared.h"), os.path.join(CSRC, "mpb_hostonly.h"), os.path.join(CSRC, "mpb_ctx.h"),
+                  os.path.join(CSRC, "mpb_queue.h"),
                   os.path.join(CSRC, "mpb_dp_tiles.inc"),
                   os.path.join(CSRC, "mpb_narrow_ring.inc"), os.path.join(CSRC, "mpb_narrow_rs.inc"),
                   os.path.join(CSRC, "mpb_narrow_rg.inc"),

@@ -2,12 +2,12 @@
 // that takes compressed members and returns the filter's results (mpb_filter_bgzf_fastq_host: k_bgzf_inflate writes the text
 // straight into the device index's stage, k_bgzf_crc32 vouches for it there, and mpb_index.cpp's kernels and mpb_text.cpp's piece
 // loop go on from it), and the CRC-32 of ranges of a text (mpb_crc32_ranges_host: the CRC kernel's own entry).  Both launch
-// k_bgzf_crc32 (mpb_crc_kernels.hip) inside the timing span of MPB_K_BGZF_INFLATE: the kernel has no id of its own.
+// k_bgzf_crc32 (mpb_crc_kernels.hip) inside the timing span of MPB_K_BGZF_INFLATE: the kernel has no id of its own.  Each entry
+// queues on one StreamQueue (mpb_queue.h); the members' verdict is mpb_hostonly.cpp's, the filter tail mpb_index.cpp's.
 // (Every mpb_* function defined here has C linkage: include/moira_pb.h declares it inside extern "C".)
 
 #include "mpb_ctx.h"
 
-#include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -65,17 +65,12 @@ int mpb_crc32_ranges_host(mpb_ctx *c, const uint8_t *text, int64_t text_bytes, c
     int rc;
     if ((rc = carve(c, c->inflate_stage, [&](Carver &k) { st.layout(k, text_bytes, n); }))) return rc;
     hipStream_t s = c->stream;
-    // (everything below is queued on one stream; the host blocks it reads from outlive the synchronisation)
-    hipError_t e = text_bytes > 0 ? hipMemcpyAsync(st.text, text, (size_t)text_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpyAsync(st.ranges, ranges.data(), (size_t)n * sizeof(mpb_crc_range), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        { Span t(c, MPB_K_BGZF_INFLATE); mpb_launch_bgzf_crc32(st.text, text_bytes, st.ranges, n, st.crcw, st.crcw + n, s); }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(crcw.data(), st.crcw, (size_t)n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    HIPCHK_KEPT("k_bgzf_crc32 / hipMemcpyAsync (crc ranges)", e);
-    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    StreamQueue q(c);
+    q.up(st.text, text, text_bytes);
+    q.up(st.ranges, ranges.data(), n * (int64_t)sizeof(mpb_crc_range));
+    q.run(MPB_K_BGZF_INFLATE, [&] { mpb_launch_bgzf_crc32(st.text, text_bytes, st.ranges, n, st.crcw, st.crcw + n, s); });
+    q.down(crcw.data(), st.crcw, n * 2 * (int64_t)sizeof(uint32_t));
+    if ((rc = q.wait("k_bgzf_crc32 / hipMemcpyAsync (crc ranges)"))) return rc;
     for (int64_t k = 0; k < n; k++)
         if (crcw[(size_t)(n + k)] != 0)
             return fail(MPB_E_INVALID, "mpb_crc32_ranges_host: the kernel refused range %lld (never expected)", (long long)k);
@@ -107,9 +102,7 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *c, const char *carry, int64_t carry_len,
     const int64_t T = carry_len + out_offs[n_members];
     if (text_out && text_cap < T)
         return fail(MPB_E_INVALID, "mpb_filter_bgzf_fastq_host: text_cap %lld is below the %lld bytes of text", (long long)text_cap, (long long)T);
-    if (fastq_offset < 0 || fastq_offset > 255)
-        return fail(MPB_E_INVALID, "mpb_filter_bgzf_fastq_host: fastq_offset %d: the device pack takes offsets 0..255 (beyond them no "
-                    "character is a quality)", fastq_offset);
+    if ((rc = check_fastq_offset(fastq_offset, "mpb_filter_bgzf_fastq_host"))) return rc;
     // 2. the rows: the only place a member's offsets are trusted from
     std::vector<mpb_bgzf_member_row> rows;
     std::vector<mpb_crc_range> ranges;
@@ -126,14 +119,7 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *c, const char *carry, int64_t carry_len,
     if (stats) { memset(stats, 0, sizeof(*stats)); stats->members = n_members; stats->handed_back = n_members; }
     if (n_members > 0) memset(done, 0, (size_t)n_members);
     int64_t in_lo = 0, in_hi = 0;                            // the one range of `in` that holds every vouched-for stream
-    bool any = false;
-    for (int64_t k = 0; k < n_members; k++) {
-        const mpb_bgzf_member_row &r = rows[(size_t)k];
-        if (r.out_len < 0) continue;
-        in_lo = any ? std::min(in_lo, r.stream_off) : r.stream_off;
-        in_hi = any ? std::max(in_hi, r.stream_off + r.stream_len) : r.stream_off + r.stream_len;
-        any = true;
-    }
+    bgzf_stream_range(rows.data(), n_members, false, &in_lo, &in_hi);
     for (int64_t k = 0; k < n_members; k++) {               // ... relative to that range, and to the text behind the carry
         mpb_bgzf_member_row &r = rows[(size_t)k];
         ranges[(size_t)k] = mpb_crc_range{0, 0, 0};
@@ -149,74 +135,44 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *c, const char *carry, int64_t carry_len,
     if ((rc = carve(c, c->inflate_stage, [&](Carver &k) { fs.layout(k, in_bytes, n_members); }))) return rc;
     hipStream_t s = c->stream;
     uint8_t *d_text = ind.st.text;
-    // 4. - 6. upload, inflate, CRC; the index's first two kernels behind them, so that one synchronisation serves members and head
-    // words (everything is queued on one stream; the host blocks it reads from outlive the synchronisation)
-    hipError_t e = carry_len > 0 ? hipMemcpyAsync(d_text, carry, (size_t)carry_len, hipMemcpyHostToDevice, s) : hipSuccess;
-    if (e == hipSuccess && in_bytes > 0) e = hipMemcpyAsync(fs.in, in + in_lo, (size_t)in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_members > 0) e = hipMemcpyAsync(fs.rows, rows.data(), (size_t)n_members * sizeof(mpb_bgzf_member_row), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_members > 0) e = hipMemcpyAsync(fs.ranges, ranges.data(), (size_t)n_members * sizeof(mpb_crc_range), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_members > 0) {
-        { Span t(c, MPB_K_BGZF_INFLATE);
-          mpb_launch_bgzf_inflate(fs.in, in_bytes, fs.rows, n_members, d_text, T, fs.mstat, s);
-          // (over every vouched-for member, taken or not: the range of one that was not taken holds whatever the block held, and
-          // its CRC word is not looked at)
-          mpb_launch_bgzf_crc32(d_text, T, fs.ranges, n_members, fs.crcw, fs.crcw + n_members, s); }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(mstat.data(), fs.mstat, (size_t)n_members * MPB_INFLATE_MSTAT * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(crcw.data(), fs.crcw, (size_t)n_members * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    // 4. - 6. upload, inflate, CRC; the index's first two kernels behind them, so that one wait serves members and head words
+    // (the queue leaves before the vectors and `res`, which it copies from and into)
+    TextResults res{ee, ns, pass, len_out, flags_out, {}};
+    StreamQueue q(c);
+    q.up(d_text, carry, carry_len);
+    q.up(fs.in, in + in_lo, in_bytes);
+    q.up(fs.rows, rows.data(), n_members * (int64_t)sizeof(mpb_bgzf_member_row));
+    q.up(fs.ranges, ranges.data(), n_members * (int64_t)sizeof(mpb_crc_range));
+    if (n_members > 0) {
+        q.run(MPB_K_BGZF_INFLATE, [&] {
+            mpb_launch_bgzf_inflate(fs.in, in_bytes, fs.rows, n_members, d_text, T, fs.mstat, s);
+            // (over every vouched-for member, taken or not: the range of one that was not taken holds whatever the block held, and
+            // its CRC word is not looked at)
+            mpb_launch_bgzf_crc32(d_text, T, fs.ranges, n_members, fs.crcw, fs.crcw + n_members, s); });
+        q.down(mstat.data(), fs.mstat, n_members * MPB_INFLATE_MSTAT * (int64_t)sizeof(uint32_t));
+        q.down(crcw.data(), fs.crcw, n_members * 2 * (int64_t)sizeof(uint32_t));
     }
-    if (e == hipSuccess) e = fastq_index_queue_head(c, ind, T, final);
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    HIPCHK_KEPT("k_bgzf_inflate / k_bgzf_crc32 / k_fq_lines / k_fq_scan", e);
-    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    fastq_index_queue_head(q, ind, T, final);
+    if ((rc = q.wait("k_bgzf_inflate / k_bgzf_crc32 / k_fq_lines / k_fq_scan"))) return rc;
     // 7. the decision: all or nothing
-    int64_t taken = 0;
     mpb_bgzf_inflate_stats acc;
     memset(&acc, 0, sizeof(acc));
     for (int64_t k = 0; k < n_members; k++) {
         if (rows[(size_t)k].out_len < 0) { if (*first_back < 0) *first_back = k; continue; }       // (reason: MPB_BGZF_WHY_HEADER)
         const uint32_t *ms = &mstat[(size_t)k * MPB_INFLATE_MSTAT];
-        const uint32_t w = ms[0];
-        reason[(size_t)k] = (uint8_t)(w <= MPB_BGZF_WHY_TRAILING_BYTES ? w : MPB_BGZF_WHY_HEADER);
-        if (w == MPB_BGZF_WHY_OK && (crcw[(size_t)(n_members + k)] != 0 || crcw[(size_t)k] != crc[(size_t)k])) reason[(size_t)k] = MPB_BGZF_WHY_CRC;
+        reason[(size_t)k] = bgzf_member_reason(ms[0]);
+        if (ms[0] == MPB_BGZF_WHY_OK && (crcw[(size_t)(n_members + k)] != 0 || crcw[(size_t)k] != crc[(size_t)k])) reason[(size_t)k] = MPB_BGZF_WHY_CRC;
         if (reason[(size_t)k] != MPB_BGZF_WHY_OK) { if (*first_back < 0) *first_back = k; continue; }
         done[k] = 1;
-        taken++;
-        acc.stored_blocks += ms[1]; acc.fixed_blocks += ms[2]; acc.dynamic_blocks += ms[3];
-        acc.literals += ms[4]; acc.matches += ms[5]; acc.matched_bytes += ms[6];
-        acc.longest_code = std::max(acc.longest_code, (int64_t)ms[7]);
+        bgzf_stats_add(&acc, ms);
     }
     if (member_why && n_members > 0) memcpy(member_why, reason.data(), (size_t)n_members);
-    if (stats) { *stats = acc; stats->members = n_members; stats->taken = taken; stats->handed_back = n_members - taken; }
+    if (stats) { *stats = acc; stats->members = n_members; stats->handed_back = n_members - acc.taken; }
     if (*first_back >= 0) return MPB_OK;                     // (what k_fq_lines / k_fq_scan made of the text is dropped with it)
     // 8. index, pack, filter over the text where it lies: mpb_filter_fastq_host's steps
-    if ((rc = fastq_index_finish(c, T, max_records, max_len, idx_cap_rows, n, ind, why))) return rc;
+    if ((rc = fastq_index_finish(q, T, max_records, max_len, idx_cap_rows, n, ind, why))) return rc;
     *n = 0;
     if (*why) return MPB_OK;
-    if (ind.n > 0x7fffffffll - 4096) return fail(MPB_E_INVALID, "batch of %lld reads exceeds 2^31; split it", (long long)ind.n);
-    if (ind.longest > MPB_MAX_LEN)
-        return fail(MPB_E_INVALID, "reads longer than 65535 bases are not supported; length (%lld)", (long long)ind.longest);
-    int64_t n_pass = 0, n_overflow = 0;
-    TextStage st{};
-    if (ind.n > 0) {
-        const int64_t stride = align_up(ind.longest > 1 ? ind.longest : 1, 128);
-        const int64_t piece_rows = text_piece_rows(ind.n, stride);
-        if ((rc = carve(c, c->text_stage, [&](Carver &k) { st.layout_results(k, ind.n, piece_rows, stride); }))) return rc;
-        if ((rc = filter_text_pieces(c, d_text, T, ind.ix.desc, ind.n, stride, piece_rows, fastq_offset, lower_n_is_base, params, poisson, st,
-                                     &n_pass, &n_overflow, bad_record))) return rc;
-    }
-    uint32_t *consumed32 = &c->pin->fq_head[0];
-    uint8_t *kind8 = (uint8_t *)&c->pin->fq_head[1];
-    *consumed32 = 0; *kind8 = 0;
-    e = queue_index_out(c, ind, idx_out, consumed32, kind8);
-    if (e == hipSuccess && text_out && T > 0) e = hipMemcpyAsync(text_out, d_text, (size_t)T, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (index, text)", e); }
-    if (ind.n > 0) {
-        if ((rc = text_results_out(c, st, ind.n, params, poisson, ee, ns, pass, len_out, flags_out, &n_pass))) return rc;
-    } else {
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    *n = ind.n; *consumed = (int64_t)*consumed32; *bad_kind = (int32_t)*kind8;
-    if (counts) { counts->n_reads = ind.n; counts->n_pass = n_pass; counts->n_fail = ind.n - n_pass; counts->n_overflow = n_overflow; }
-    return MPB_OK;
+    return filter_indexed(q, ind, T, text_out, idx_out, n, consumed, bad_kind,
+                          FastqFilterAsk{fastq_offset, lower_n_is_base, params, poisson, counts, bad_record}, res);
 }

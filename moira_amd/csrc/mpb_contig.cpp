@@ -3,7 +3,9 @@
 // pointer matrix needs, launches k_contig (mpb_contig_kernels.hip) once per size class and brings the slots and arrays back.
 // A pair the device does not take is handed back (done = 0); the caller builds it with libmoira_contig.so.
 // mpb_contigs_filter_text_host is the same chunk call with the filter behind it: k_contig_rows hands the device's own index to
-// k_pack_text, and mpb_filter_text_host's piece loop (filter_text_pieces, mpb_text.cpp) runs over the slots where they lie.
+// k_pack_text, and mpb_filter_text_host's piece loop (filter_text_pieces, mpb_text.cpp) runs over the slots where they lie; the
+// filter's results are queued (text_results_queue) with the contigs' own copies on the chunk's one StreamQueue (mpb_queue.h),
+// behind one wait, and text_results_tail follows it.
 // (Every mpb_* function defined here has C linkage: include/moira_pb.h declares it inside extern "C".)
 
 #include "mpb_ctx.h"
@@ -142,16 +144,18 @@ int contigs_chunk(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int6
     }
     hipStream_t s = c->stream;
     const int64_t fcap = align_up(ftext_bytes > 0 ? ftext_bytes : 1, 16), rcap = align_up(rtext_bytes > 0 ? rtext_bytes : 1, 16);
-    // (everything below is queued on one stream; the host blocks it reads from outlive the synchronisation every path passes)
-    hipError_t e = hipSuccess;
-    if (fcap > ftext_bytes) e = hipMemsetAsync(st.ftext + ftext_bytes, 0, (size_t)(fcap - ftext_bytes), s);
-    if (e == hipSuccess && rcap > rtext_bytes) e = hipMemsetAsync(st.rtext + rtext_bytes, 0, (size_t)(rcap - rtext_bytes), s);
-    if (e == hipSuccess) e = hipMemsetAsync(st.done, 0, (size_t)n, s);
-    if (e == hipSuccess && ftext_bytes > 0) e = hipMemcpyAsync(st.ftext, ftext, (size_t)ftext_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && rtext_bytes > 0) e = hipMemcpyAsync(st.rtext, rtext, (size_t)rtext_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(st.rows, rows.data(), (size_t)n * sizeof(mpb_pair_row), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(st.list, list.data(), (size_t)listed * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (contig upload)", e); }
+    // (the queue leaves before the vectors above and `fres`, which it copies from and into)
+    TextResults fres{};
+    if (fa) { fres.ee = fa->ee; fres.ns = fa->ns; fres.pass = fa->pass; fres.len = fa->len_out; fres.flags = fa->flags_out; }
+    StreamQueue q(c);
+    q.zero(st.ftext + ftext_bytes, fcap - ftext_bytes);
+    q.zero(st.rtext + rtext_bytes, rcap - rtext_bytes);
+    q.zero(st.done, n);
+    q.up(st.ftext, ftext, ftext_bytes);
+    q.up(st.rtext, rtext, rtext_bytes);
+    q.up(st.rows, rows.data(), n * (int64_t)sizeof(mpb_pair_row));
+    q.up(st.list, list.data(), listed * (int64_t)sizeof(int32_t));
+    if (!q.ok()) return q.wait("hipMemcpyAsync (contig upload)");
     MpbContigArgs a{};
     a.ftext = st.ftext; a.fbytes = ftext_bytes; a.rtext = st.rtext; a.rbytes = rtext_bytes;
     a.rows = st.rows; a.n = n;
@@ -167,54 +171,36 @@ int contigs_chunk(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int6
     for (int k = 0; k < k_n_class; k++) {
         if (!per_class[k]) continue;
         a.list = st.list + first[k]; a.count = per_class[k]; a.lds_cap = k_lds_class[k];
-        Span t(c, MPB_K_CONTIG);
-        mpb_launch_contigs(a, s);
+        q.run(MPB_K_CONTIG, [&] { mpb_launch_contigs(a, s); });
     }
-    e = hipGetLastError();
     // 5b. the filter of the slots where they lie: the device's own index becomes k_pack_text's descriptors (k_contig_rows, behind
     // the launches above on the same stream), then mpb_filter_text_host's piece loop over the slot buffer.  A quality out of
     // range or a filter call that fails leaves the contigs valid: it is reported beside them, and nothing counts as filtered.
     int frc = MPB_OK;
     int64_t f_pass = 0, f_overflow = 0, f_bad = -1;
     char f_msg[MPB_ERR_LEN] = "";
-    if (fa && e == hipSuccess) {
-        { Span t(c, MPB_K_CONTIG_ROWS);
-          mpb_launch_contig_rows(st.out_idx, st.done, n, rec_cap, fa->max_len, stride, ts.rows, s); }
-        e = hipGetLastError();
-        if (e == hipSuccess) {
-            frc = filter_text_pieces(c, st.out_buf, n * rec_cap, ts.rows, n, stride, piece_rows, fastq_offset, fa->lower_n_is_base,
-                                     fa->params, fa->poisson, ts, &f_pass, &f_overflow, &f_bad);
-            if (frc != MPB_OK && frc != MPB_E_RANGE && frc != MPB_E_INVALID) return frc;      // (the stream is synchronised)
-            if (frc) { strncpy(f_msg, mpb_last_error(), sizeof(f_msg) - 1); }
-        }
-    }
-    const bool host_tail = fa && fa->poisson && !(fa->params->flags & MPB_FLAG_POISSON_DEVICE_TAIL);
-    std::vector<int32_t> len_tmp;
-    int32_t *len_host = fa ? fa->len_out : nullptr;
-    if (host_tail && !len_host) {
-        try { len_tmp.resize((size_t)n); } catch (const std::bad_alloc &) { (void)hipStreamSynchronize(s); return fail(MPB_E_NOMEM, "out of host memory"); }
-        len_host = len_tmp.data();
+    const bool host_tail = fa && text_host_tail(fa->params, fa->poisson);
+    if (fa) q.run(MPB_K_CONTIG_ROWS, [&] { mpb_launch_contig_rows(st.out_idx, st.done, n, rec_cap, fa->max_len, stride, ts.rows, s); });
+    if (fa && q.ok()) {
+        frc = filter_text_pieces(q, st.out_buf, n * rec_cap, ts.rows, n, stride, piece_rows, fastq_offset, fa->lower_n_is_base,
+                                 fa->params, fa->poisson, ts, &f_pass, &f_overflow, &f_bad);
+        if (frc != MPB_OK && frc != MPB_E_RANGE && frc != MPB_E_INVALID) return frc;
+        if (frc) { strncpy(f_msg, mpb_last_error(), sizeof(f_msg) - 1); }
     }
     // 6. the slots and arrays
-    if (fa && frc == MPB_OK) {
-        if (e == hipSuccess) e = hipMemcpyAsync(fa->ee, ts.ee, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(fa->ns, ts.ns, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && !host_tail) e = hipMemcpyAsync(fa->pass, ts.pass, (size_t)n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && len_host) e = hipMemcpyAsync(len_host, ts.len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && fa->flags_out) e = hipMemcpyAsync(fa->flags_out, ts.flags, (size_t)n, hipMemcpyDeviceToHost, s);
+    if (fa && frc == MPB_OK && (rc = text_results_queue(q, ts, n, host_tail, fres))) return rc;
+    q.down(out_buf, st.out_buf, n * rec_cap);
+    q.down(out_idx, st.out_idx, n * 6 * (int64_t)sizeof(int64_t));
+    q.down(overlap, st.overlap, n * (int64_t)sizeof(int32_t));
+    q.down(gaps, st.gaps, n * (int64_t)sizeof(int32_t));
+    q.down(mismatches, st.mism, n * (int64_t)sizeof(int32_t));
+    q.down(done, st.done, n);
+    if (aln_out) {
+        q.down(aln_out, st.aln, 2 * n * aln_cap);
+        q.down(aln_len_out, st.aln_len, n * (int64_t)sizeof(int32_t));
+        q.down(score_out, st.score, n * (int64_t)sizeof(int32_t));
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_buf, st.out_buf, (size_t)(n * rec_cap), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_idx, st.out_idx, (size_t)n * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(overlap, st.overlap, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(gaps, st.gaps, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(mismatches, st.mism, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(done, st.done, (size_t)n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && aln_out) e = hipMemcpyAsync(aln_out, st.aln, (size_t)(2 * n * aln_cap), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && aln_out) e = hipMemcpyAsync(aln_len_out, st.aln_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && aln_out) e = hipMemcpyAsync(score_out, st.score, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    HIPCHK_KEPT("k_contig / hipMemcpyAsync (contig results)", e);
-    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    if ((rc = q.wait("k_contig / hipMemcpyAsync (contig results)"))) return rc;
     int64_t nd = 0;
     for (int64_t i = 0; i < n; i++) nd += done[i] != 0;
     if (n_done) *n_done = nd;
@@ -232,10 +218,7 @@ int contigs_chunk(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int6
         (void)fail(frc, "%s", f_msg);                    // mpb_last_error() holds the filter's message
         return MPB_OK;
     }
-    if (host_tail) {
-        // the reference's scalar tail with the host's libm, in place: ee holds lambda (mpb_filter_text_host's arithmetic)
-        if ((rc = mpb_poisson_finish_host(fa->ee, fa->ns, len_host, 0, n, fa->params, fa->ee, fa->pass))) return rc;
-    }
+    if ((rc = text_results_tail(n, fa->params, host_tail, fres, nullptr))) return rc;
     int64_t np = 0;
     for (int64_t i = 0; i < n; i++) {
         fa->filtered[i] = done[i] != 0;

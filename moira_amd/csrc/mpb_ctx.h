@@ -1,7 +1,7 @@
 // mpb_ctx.h -- the context of the C ABI (struct mpb_ctx) and what the GPU-facing host units share: the error macros, the owner of
-// a growable block (Buf), the carver that lays a block out (Carver), the timing span, and the few functions that cross units
-// (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp, mpb_poisson.cpp, mpb_text.cpp, mpb_index.cpp,
-// mpb_bgzf_fastq.cpp).  Not installed.
+// a growable block (Buf), the carver that lays a block out (Carver), the timing span, the queue of a staged entry (StreamQueue,
+// mpb_queue.h) and the few functions that cross units (mpb_context.cpp, mpb_resident.cpp, mpb_hostfed.cpp, mpb_perread.cpp,
+// mpb_poisson.cpp, mpb_text.cpp, mpb_contig.cpp, mpb_index.cpp, mpb_bgzf_fastq.cpp).  Not installed.
 #ifndef MPB_CTX_H
 #define MPB_CTX_H
 
@@ -214,6 +214,9 @@ struct Span {
     }
 };
 
+// the calls one staged entry queues on c->stream and its one wait (written against the names above; includes no HIP header)
+#include "mpb_queue.h"
+
 // The kernels of one call run on a private copy of the table; the context's own is back in place when the call returns.
 struct PrivateTable {
     mpb_ctx *c;
@@ -259,17 +262,31 @@ struct TextStage {
 int64_t text_piece_rows(int64_t n, int64_t stride);
 // The piece loop of a text call: n rows described by d_rows over d_text (both on the device; k_pack_text's contract) are packed
 // into st.q and filtered piece by piece into st.len / flags / ee / ns / pass, with mpb_filter_text_host's three poisson forms and
-// its order of errors (a quality out of range: MPB_E_RANGE and *bad_record, a position in row order; else the first filter call
-// that failed).  The stream is synchronised when it returns, whatever it returns.
-int filter_text_pieces(mpb_ctx *c, const uint8_t *d_text, int64_t text_bytes, const mpb_text_row *d_rows, int64_t n, int64_t stride,
+// its order of errors (an upload the caller queued that failed; a quality out of range: MPB_E_RANGE and *bad_record, a position
+// in row order; else the first filter call that failed).  It waits for the queue once per piece.
+int filter_text_pieces(StreamQueue &q, const uint8_t *d_text, int64_t text_bytes, const mpb_text_row *d_rows, int64_t n, int64_t stride,
                        int64_t piece_rows, int32_t fastq_offset, int32_t lower_n_is_base, const mpb_filter_params *params,
                        int32_t poisson, const TextStage &st, int64_t *n_pass, int64_t *n_overflow, int64_t *bad_record);
-// What follows the piece loop: the results of n rows copied out of st (len_out / flags_out may be null), and -- poisson without
-// the device tail -- the reference's scalar tail on the host; *n_pass is the piece loop's count going in, the call's going out.
-int text_results_out(mpb_ctx *c, const TextStage &st, int64_t n, const mpb_filter_params *params, int32_t poisson, double *ee,
-                     int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, int64_t *n_pass);
+// What follows the piece loop.  Where the results of n rows go on the host (len / flags may be null), and the lengths of the
+// host tail when the caller wants none: declared before the queue that copies into it.
+struct TextResults {
+    double *ee; int32_t *ns; uint8_t *pass; int32_t *len; uint8_t *flags;
+    std::vector<int32_t> len_tmp;
+    int32_t *len_host() const { return len ? len : len_tmp.empty() ? nullptr : const_cast<int32_t *>(len_tmp.data()); }
+};
+// poisson without the device tail: the reference's scalar tail runs on the host, behind the wait
+static inline bool text_host_tail(const mpb_filter_params *params, int32_t poisson)
+{
+    return poisson && !(params && (params->flags & MPB_FLAG_POISSON_DEVICE_TAIL));
+}
+// ... queued: the five copies out of st (`pass` only when the device wrote it; the lengths into len_tmp when the host tail needs
+// them and r.len is null); after the wait: the host tail, and *n_pass (may be null) counted again from what it wrote
+int text_results_queue(StreamQueue &q, const TextStage &st, int64_t n, bool host_tail, TextResults &r);
+int text_results_tail(int64_t n, const mpb_filter_params *params, bool host_tail, const TextResults &r, int64_t *n_pass);
+// ... queue, wait, tail: *n_pass is the piece loop's count going in, the call's going out
+int text_results_out(StreamQueue &q, const TextStage &st, int64_t n, const mpb_filter_params *params, int32_t poisson, TextResults &r,
+                     int64_t *n_pass);
 // mpb_index.cpp: the device FASTQ index, shared with mpb_bgzf_fastq.cpp (which inflates the text into the index's own stage)
-const int64_t k_text_max_bytes = 1ll << 30;                 // the text of one call (mpb_filter_text_host's limit)
 
 // text | tile table | prefix | head | status: sized from the text alone
 struct FastqStage {
@@ -302,12 +319,21 @@ struct Indexed {                                             // what the device 
     int64_t n = 0, rows = 0, longest = 0;                    // records; rows of the index (n, or n + 1: the offender's); longest packed length
 };
 // k_fq_lines, k_fq_scan and the copy of the head words to the pinned block, queued over the text that lies in out.st.text; after
-// the caller's synchronisation fastq_index_finish does the rest (*why != 0: handed back; the stream is synchronised when it
-// returns); queue_index_out queues the copies of the index's rows, the offender's kind and the first byte behind the last record
-hipError_t fastq_index_queue_head(mpb_ctx *c, Indexed &out, int64_t text_bytes, int32_t final);
-int fastq_index_finish(mpb_ctx *c, int64_t text_bytes, int64_t max_records, int32_t max_len, int64_t idx_cap_rows, int64_t *n_needed,
+// the caller's wait fastq_index_finish does the rest (*why != 0: handed back; it waits for what it queues); queue_index_out
+// queues the copies of the index's rows, the offender's kind and the first byte behind the last record
+void fastq_index_queue_head(StreamQueue &q, Indexed &out, int64_t text_bytes, int32_t final);
+int fastq_index_finish(StreamQueue &q, int64_t text_bytes, int64_t max_records, int32_t max_len, int64_t idx_cap_rows, int64_t *n_needed,
                        Indexed &out, int32_t *why);
-hipError_t queue_index_out(mpb_ctx *c, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8);
+void queue_index_out(StreamQueue &q, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8);
+// The filter tail of an indexed text that lies on the device (in.st.text), shared by mpb_filter_fastq_host and
+// mpb_filter_bgzf_fastq_host: the two size refusals, the text call's stage, the piece loop, the index's rows and the results
+// copied out behind one wait (text_out: the whole text too, or null), the out-parameters and the counts.
+struct FastqFilterAsk {
+    int32_t fastq_offset, lower_n_is_base; const mpb_filter_params *params; int32_t poisson;
+    mpb_filter_counts *counts; int64_t *bad_record;
+};
+int filter_indexed(StreamQueue &q, const Indexed &in, int64_t text_bytes, uint8_t *text_out, int64_t *idx_out, int64_t *n,
+                   int64_t *consumed, int32_t *bad_kind, const FastqFilterAsk &ask, TextResults &r);
 // mpb_perread.cpp: the per-read entry's resident kernel leaves (before anything is freed: the runtime waits for the whole
 // device there); ... and its stream and blocks go
 void serve_quiesce(mpb_ctx *c);

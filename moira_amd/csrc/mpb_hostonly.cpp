@@ -316,6 +316,27 @@ int check_params(const mpb_filter_params *p)
     return MPB_OK;
 }
 
+int check_text_bytes(int64_t text_bytes)
+{
+    if (text_bytes <= k_text_max_bytes) return MPB_OK;
+    return fail(MPB_E_INVALID, "text of %lld bytes: one call takes at most %lld bytes (1 GiB) of text; split the chunk",
+                (long long)text_bytes, (long long)k_text_max_bytes);
+}
+
+int check_fastq_offset(int32_t fastq_offset, const char *who)
+{
+    if (fastq_offset >= 0 && fastq_offset <= 255) return MPB_OK;
+    return fail(MPB_E_INVALID, "%s%sfastq_offset %d: the device pack takes offsets 0..255 (beyond them no character is a quality)",
+                who ? who : "", who ? ": " : "", fastq_offset);
+}
+
+int64_t env_int64(const char *name, int64_t lo, int64_t hi, int64_t fallback)
+{
+    const char *e = getenv(name);
+    const long long v = e ? atoll(e) : 0;
+    return e && v >= lo && v <= hi ? (int64_t)v : fallback;
+}
+
 // The choice, from the sample's histogram of rows.  Costs per read in units of 0.083 ms per 10 M reads of 300 bases, fitted to
 // measured steps (profiles/r05_narrow_rate.txt; round 6: profiles/r06_narrow_mix.txt, r06_ragged_mix.txt): the narrow pass 4 + 3 R for
 // every read whatever it needs; the sorted pipeline 9 (classification + sort: its second read of the matrix) + 3.9 per row of the
@@ -800,4 +821,30 @@ int mpb_bgzf_member_rows(const uint8_t *in, int64_t in_len, const int64_t *offs,
         if (why_out) why_out[k] = MPB_BGZF_WHY_OK;
     }
     return MPB_OK;
+}
+
+// ---- ... and what the inflating entries make of a member behind the kernel -------------------------------------------------------
+uint8_t bgzf_member_reason(uint32_t status_word)
+{
+    return (uint8_t)(status_word <= MPB_BGZF_WHY_TRAILING_BYTES ? status_word : MPB_BGZF_WHY_HEADER);
+}
+
+void bgzf_stats_add(mpb_bgzf_inflate_stats *acc, const uint32_t *ms)
+{
+    acc->taken++;
+    acc->stored_blocks += ms[1]; acc->fixed_blocks += ms[2]; acc->dynamic_blocks += ms[3];
+    acc->literals += ms[4]; acc->matches += ms[5]; acc->matched_bytes += ms[6];
+    if (acc->longest_code < (int64_t)ms[7]) acc->longest_code = (int64_t)ms[7];
+}
+
+bool bgzf_stream_range(const mpb_bgzf_member_row *rows, int64_t n, bool any, int64_t *lo, int64_t *hi)
+{
+    for (int64_t k = 0; k < n; k++) {
+        if (rows[k].out_len < 0) continue;
+        const int64_t a = rows[k].stream_off, b = a + rows[k].stream_len;
+        if (!any || a < *lo) *lo = a;
+        if (!any || b > *hi) *hi = b;
+        any = true;
+    }
+    return any;
 }

@@ -1,5 +1,6 @@
 // mpb_hostonly.h -- the part of the C-ABI layer that needs no GPU (mpb_hostonly.cpp): error state, the table arithmetic, the
-// packers, argument checks, the narrow pass' cost model, the host Poisson tail, the NUMA parser.  Includes no HIP header: the
+// packers, argument checks and the refusals several entries share, the narrow pass' cost model, the host Poisson tail, the NUMA
+// parser, the environment's integers, what the inflating entries make of a BGZF member.  Includes no HIP header: the
 // unit builds with a plain C++ compiler (tools/asan_api.sh, tools/tsan_poisson.sh run it under the host sanitizers).  C++
 // linkage throughout, so the version script, which exports `mpb_*` only, keeps all of it inside the library.
 #ifndef MPB_HOSTONLY_H
@@ -23,6 +24,12 @@ int pack_one_read(const char *contig, const int32_t *quals, int32_t len, bool po
                   MpbPair *h, bool *priv);
 
 int check_params(const mpb_filter_params *p);
+// the refusals several entries share, each with its one message (who: the entry's name as a prefix, or null)
+const int64_t k_text_max_bytes = 1ll << 30;              // the text of one call, in every entry that takes text
+int check_text_bytes(int64_t text_bytes);
+int check_fastq_offset(int32_t fastq_offset, const char *who = nullptr);
+// the integer in environment variable `name` when it lies in lo..hi, else (unset, empty, no number, out of range) `fallback`
+int64_t env_int64(const char *name, int64_t lo, int64_t hi, int64_t fallback);
 double inv_norm_cdf(double p);
 // the parameters of a per-read call (bernoulli's calculate_errors_PB / calculate_errors_poisson): alpha, the rest moira's defaults
 static inline mpb_filter_params per_read_params(double alpha)
@@ -40,6 +47,13 @@ int poisson_finish_marked(const mpb_filter_params *p, const int32_t *ns, const i
 // CRC-32 of every BGZF member of a text (member m = bytes [m * MPB_BGZF_DATA, ...)), on a few threads
 uint32_t bgzf_crc32(const uint8_t *p, size_t n);          // RFC 1952 section 8, eight bytes per step
 void bgzf_member_crcs(const uint8_t *text, int64_t text_bytes, int64_t n_members, uint32_t *crc_out);
+// What the inflating entries make of a member.  The reason of k_bgzf_inflate's status word (one the kernel never writes:
+// MPB_BGZF_WHY_HEADER); a taken member's status row (eight words) added to the call's stats, longest_code as a maximum; and the one
+// range [*lo, *hi) of `in` that holds the streams of the vouched-for rows (out_len >= 0) among n -- widening the range that is
+// there when `any`, returning whether there is one now.
+uint8_t bgzf_member_reason(uint32_t status_word);
+void bgzf_stats_add(mpb_bgzf_inflate_stats *acc, const uint32_t *mstat_row);
+bool bgzf_stream_range(const mpb_bgzf_member_row *rows, int64_t n, bool any, int64_t *lo, int64_t *hi);
 
 bool parse_cpulist(const char *s, cpu_set_t *set, int *count);
 int staging_threads();

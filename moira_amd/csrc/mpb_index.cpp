@@ -1,7 +1,8 @@
 // mpb_index.cpp -- the FASTQ record index on the device, behind the C ABI of libmoira_pb.so (include/moira_pb.h): the entry that
 // takes a chunk of FASTQ text alone and returns mio_fastq_index's index (mpb_fastq_index_host), and the one that filters the
 // chunk from the same upload (mpb_filter_fastq_host: the index's device-written descriptors go straight into mpb_text.cpp's
-// piece loop).  The kernels are mpb_index_kernels.hip; a text the device does not take is handed back with a reason.
+// piece loop; filter_indexed, the tail it shares with mpb_bgzf_fastq.cpp).  The kernels are mpb_index_kernels.hip; a text the
+// device does not take is handed back with a reason.  Each entry queues on one StreamQueue (mpb_queue.h).
 // (Every mpb_* function defined here has C linkage: include/moira_pb.h declares it inside extern "C".)
 
 #include "mpb_ctx.h"
@@ -16,40 +17,34 @@ int check_args(const char *text, int64_t text_bytes, int64_t max_records, int32_
     if (text_bytes < 0 || (text_bytes > 0 && !text) || max_records < 0 || max_len < 0 || idx_cap_rows < 1 || !idx_out || !n || !consumed ||
         !bad_kind || !why)
         return fail(MPB_E_INVALID, "%s: bad arguments", who);
-    if (text_bytes > k_text_max_bytes)
-        return fail(MPB_E_INVALID, "text of %lld bytes: one call takes at most %lld bytes (1 GiB) of text; split the chunk",
-                    (long long)text_bytes, (long long)k_text_max_bytes);
-    return MPB_OK;
+    return check_text_bytes(text_bytes);
 }
 
 }  // namespace
 
 // k_fq_lines, k_fq_scan and the copy of the head words to the pinned block, queued over the text that lies in out.st.text
-hipError_t fastq_index_queue_head(mpb_ctx *c, Indexed &out, int64_t text_bytes, int32_t final)
+void fastq_index_queue_head(StreamQueue &q, Indexed &out, int64_t text_bytes, int32_t final)
 {
-    hipStream_t s = c->stream;
+    hipStream_t s = q.c->stream;
     const int64_t n_tiles = (text_bytes + MPB_FQ_TILE - 1) / MPB_FQ_TILE;
     FastqStage &st = out.st;
-    { Span t(c, MPB_K_FQ_LINES); mpb_launch_fq_lines(st.text, text_bytes, n_tiles, st.info, s); }
-    { Span t(c, MPB_K_FQ_SCAN); mpb_launch_fq_scan(st.text, text_bytes, final != 0, st.info, n_tiles, st.prefix, st.head, s); }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(c->pin->fq_head, st.head, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    return e;
+    q.run(MPB_K_FQ_LINES, [&] { mpb_launch_fq_lines(st.text, text_bytes, n_tiles, st.info, s); });
+    q.run(MPB_K_FQ_SCAN, [&] { mpb_launch_fq_scan(st.text, text_bytes, final != 0, st.info, n_tiles, st.prefix, st.head, s); });
+    q.down(q.c->pin->fq_head, st.head, 4 * sizeof(uint32_t));
 }
 
-// What follows the synchronisation behind fastq_index_queue_head: the head words' verdict, the blocks sized from the counted
-// lines, k_fq_starts, k_fq_rows and its small read-back.  *why != 0: handed back.  The index stays on the device (out.ix); the
-// stream is synchronised when this returns, whatever it returns.
-int fastq_index_finish(mpb_ctx *c, int64_t text_bytes, int64_t max_records, int32_t max_len, int64_t idx_cap_rows, int64_t *n_needed,
+// What follows the wait behind fastq_index_queue_head: the head words' verdict, the blocks sized from the counted lines,
+// k_fq_starts, k_fq_rows and its small read-back.  *why != 0: handed back.  The index stays on the device (out.ix).
+int fastq_index_finish(StreamQueue &q, int64_t text_bytes, int64_t max_records, int32_t max_len, int64_t idx_cap_rows, int64_t *n_needed,
                        Indexed &out, int32_t *why)
 {
     *why = MPB_FQ_WHY_TAKEN;
+    mpb_ctx *c = q.c;
     hipStream_t s = c->stream;
     const int64_t n_tiles = (text_bytes + MPB_FQ_TILE - 1) / MPB_FQ_TILE;
     FastqStage &st = out.st;
     const uint32_t *head = c->pin->fq_head;
     int64_t *status = c->pin->fq_status;
-    hipError_t e = hipSuccess, e_sync = hipSuccess;
     int rc;
     if (head[1] & 2u) { *why = MPB_FQ_WHY_LONE_CR; return MPB_OK; }
     if (head[1] & 1u) { *why = MPB_FQ_WHY_NON_ASCII; return MPB_OK; }
@@ -69,21 +64,16 @@ int fastq_index_finish(mpb_ctx *c, int64_t text_bytes, int64_t max_records, int3
     if (rc == MPB_E_NOMEM) { *why = MPB_FQ_WHY_LINE_TABLE; return MPB_OK; }
     if (rc) return rc;
     if (cand == 0) return MPB_OK;                            // (n = 0, consumed = 0, no bad record)
-    { Span t(c, MPB_K_FQ_STARTS); mpb_launch_fq_starts(st.text, text_bytes, n_tiles, st.prefix, st.head, ix.start, n_start, s); }
+    q.run(MPB_K_FQ_STARTS, [&] { mpb_launch_fq_starts(st.text, text_bytes, n_tiles, st.prefix, st.head, ix.start, n_start, s); });
     // the rows; when a record fails its checks, once more over the records before it: the longest packed length is theirs alone
     int64_t count = cand;
     for (int pass = 0; pass < 2; pass++) {
         status[0] = INT64_MAX; status[1] = 0; status[2] = 0; status[3] = 0;
-        e = hipMemcpyAsync(st.status, status, 4 * sizeof(int64_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            { Span t(c, MPB_K_FQ_ROWS);
-              mpb_launch_fq_rows(st.text, text_bytes, ix.start, n_start, count, max_len, ix.idx, ix.kinds, ix.desc, st.status, s); }
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(status, st.status, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-        e_sync = hipStreamSynchronize(s);
-        HIPCHK_KEPT("k_fq_starts / k_fq_rows", e);
-        HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+        q.up(st.status, status, 4 * sizeof(int64_t));
+        q.run(MPB_K_FQ_ROWS, [&] {
+            mpb_launch_fq_rows(st.text, text_bytes, ix.start, n_start, count, max_len, ix.idx, ix.kinds, ix.desc, st.status, s); });
+        q.down(status, st.status, 4 * sizeof(int64_t));
+        if ((rc = q.wait("k_fq_starts / k_fq_rows"))) return rc;
         if (status[2] != 0) { *why = MPB_FQ_WHY_ROW_CHECK; return MPB_OK; }
         if (pass == 1 || status[0] == INT64_MAX) break;
         if (status[0] < 0 || status[0] >= count) { *why = MPB_FQ_WHY_ROW_CHECK; return MPB_OK; }
@@ -100,40 +90,60 @@ int fastq_index_finish(mpb_ctx *c, int64_t text_bytes, int64_t max_records, int3
 
 namespace {
 
-// Upload, the four kernels and the two small read-backs.  *why != 0: handed back.  The index stays on the device (out.ix); the
-// stream is synchronised when this returns, whatever it returns.
-int index_on_device(mpb_ctx *c, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
+// Upload, the four kernels and the two small read-backs.  *why != 0: handed back.  The index stays on the device (out.ix).
+int index_on_device(StreamQueue &q, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
                     int64_t idx_cap_rows, int64_t *n_needed, Indexed &out, int32_t *why)
 {
     *why = MPB_FQ_WHY_TAKEN;
-    hipStream_t s = c->stream;
     const int64_t n_tiles = (text_bytes + MPB_FQ_TILE - 1) / MPB_FQ_TILE;
     FastqStage &st = out.st;
     int rc;
-    if ((rc = carve(c, c->fastq_stage, [&](Carver &k) { st.layout(k, text_bytes, n_tiles); }))) return rc;
-    // (everything below is queued on one stream; the host blocks it reads from -- the caller's text, the pinned words -- outlive
-    // the synchronisation that every path out of here passes)
-    hipError_t e = hipSuccess;
-    if (text_bytes > 0) e = hipMemcpyAsync(st.text, text, (size_t)text_bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return hip_fail("hipMemcpyAsync (text upload)", e); }
-    e = fastq_index_queue_head(c, out, text_bytes, final);
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    HIPCHK_KEPT("k_fq_lines / k_fq_scan", e);
-    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
-    return fastq_index_finish(c, text_bytes, max_records, max_len, idx_cap_rows, n_needed, out, why);
+    if ((rc = carve(q.c, q.c->fastq_stage, [&](Carver &k) { st.layout(k, text_bytes, n_tiles); }))) return rc;
+    q.up(st.text, text, text_bytes);
+    fastq_index_queue_head(q, out, text_bytes, final);
+    if ((rc = q.wait("hipMemcpyAsync (text upload) / k_fq_lines / k_fq_scan"))) return rc;
+    return fastq_index_finish(q, text_bytes, max_records, max_len, idx_cap_rows, n_needed, out, why);
 }
 
 }  // namespace
 
 // the rows of the index, the offender's kind and the first byte behind the last record, queued for the caller's arrays
-hipError_t queue_index_out(mpb_ctx *c, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8)
+void queue_index_out(StreamQueue &q, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8)
 {
-    hipStream_t s = c->stream;
-    hipError_t e = hipSuccess;
-    if (in.rows > 0) e = hipMemcpyAsync(idx_out, in.ix.idx, (size_t)in.rows * MPB_IDX_COLS * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && in.n > 0) e = hipMemcpyAsync(consumed32, in.ix.start + 4 * in.n, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && in.rows > in.n) e = hipMemcpyAsync(kind8, in.ix.kinds + in.n, 1, hipMemcpyDeviceToHost, s);
-    return e;
+    q.down(idx_out, in.ix.idx, in.rows * MPB_IDX_COLS * (int64_t)sizeof(int64_t));
+    if (in.n > 0) q.down(consumed32, in.ix.start + 4 * in.n, sizeof(uint32_t));
+    if (in.rows > in.n) q.down(kind8, in.ix.kinds + in.n, 1);
+}
+
+int filter_indexed(StreamQueue &q, const Indexed &in, int64_t text_bytes, uint8_t *text_out, int64_t *idx_out, int64_t *n,
+                   int64_t *consumed, int32_t *bad_kind, const FastqFilterAsk &ask, TextResults &r)
+{
+    mpb_ctx *c = q.c;
+    int rc;
+    if (in.n > 0x7fffffffll - 4096) return fail(MPB_E_INVALID, "batch of %lld reads exceeds 2^31; split it", (long long)in.n);
+    if (in.longest > MPB_MAX_LEN)
+        return fail(MPB_E_INVALID, "reads longer than 65535 bases are not supported; length (%lld)", (long long)in.longest);
+    int64_t n_pass = 0, n_overflow = 0;
+    TextStage st{};
+    if (in.n > 0) {
+        const int64_t stride = align_up(in.longest > 1 ? in.longest : 1, 128);
+        const int64_t piece_rows = text_piece_rows(in.n, stride);
+        if ((rc = carve(c, c->text_stage, [&](Carver &k) { st.layout_results(k, in.n, piece_rows, stride); }))) return rc;
+        if ((rc = filter_text_pieces(q, in.st.text, text_bytes, in.ix.desc, in.n, stride, piece_rows, ask.fastq_offset, ask.lower_n_is_base,
+                                     ask.params, ask.poisson, st, &n_pass, &n_overflow, ask.bad_record))) return rc;
+    }
+    // (the two small words land in the pinned block: nothing of them lies on a frame)
+    uint32_t *consumed32 = &c->pin->fq_head[0];
+    uint8_t *kind8 = (uint8_t *)&c->pin->fq_head[1];
+    *consumed32 = 0; *kind8 = 0;
+    queue_index_out(q, in, idx_out, consumed32, kind8);
+    if (text_out) q.down(text_out, in.st.text, text_bytes);
+    if (in.n > 0) rc = text_results_out(q, st, in.n, ask.params, ask.poisson, r, &n_pass);
+    else rc = q.wait("hipMemcpyAsync (index, text)");
+    if (rc) return rc;
+    *n = in.n; *consumed = (int64_t)*consumed32; *bad_kind = (int32_t)*kind8;
+    if (ask.counts) { ask.counts->n_reads = in.n; ask.counts->n_pass = n_pass; ask.counts->n_fail = in.n - n_pass; ask.counts->n_overflow = n_overflow; }
+    return MPB_OK;
 }
 
 int mpb_fastq_index_host(mpb_ctx *c, const char *text, int64_t text_bytes, int32_t final, int64_t max_records, int32_t max_len,
@@ -145,17 +155,16 @@ int mpb_fastq_index_host(mpb_ctx *c, const char *text, int64_t text_bytes, int32
     CTXCHK(c);
     *n = 0; *consumed = 0; *bad_kind = 0;
     Indexed in;
-    if ((rc = index_on_device(c, text, text_bytes, final, max_records, max_len, idx_cap_rows, n, in, why))) return rc;
+    StreamQueue q(c);
+    if ((rc = index_on_device(q, text, text_bytes, final, max_records, max_len, idx_cap_rows, n, in, why))) return rc;
     *n = 0;
     if (*why) return MPB_OK;
     // (the two small words land in the pinned block: nothing of them lies on a frame)
     uint32_t *consumed32 = &c->pin->fq_head[0];
     uint8_t *kind8 = (uint8_t *)&c->pin->fq_head[1];
     *consumed32 = 0; *kind8 = 0;
-    const hipError_t e = queue_index_out(c, in, idx_out, consumed32, kind8);
-    const hipError_t e_sync = hipStreamSynchronize(c->stream);
-    HIPCHK_KEPT("hipMemcpyAsync (index)", e);
-    HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+    queue_index_out(q, in, idx_out, consumed32, kind8);
+    if ((rc = q.wait("hipMemcpyAsync (index)"))) return rc;
     *n = in.n; *consumed = (int64_t)*consumed32; *bad_kind = (int32_t)*kind8;
     return MPB_OK;
 }
@@ -172,38 +181,16 @@ int mpb_filter_fastq_host(mpb_ctx *c, const char *text, int64_t text_bytes, int3
     if ((rc = check_args(text, text_bytes, max_records, max_len, idx_out, idx_cap_rows, n, consumed, bad_kind, why, "mpb_filter_fastq_host")))
         return rc;
     if (!ee || !ns || !pass) return fail(MPB_E_INVALID, "NULL host buffer");
-    if (fastq_offset < 0 || fastq_offset > 255)
-        return fail(MPB_E_INVALID, "fastq_offset %d: the device pack takes offsets 0..255 (beyond them no character is a quality)", fastq_offset);
+    if ((rc = check_fastq_offset(fastq_offset))) return rc;
     CTXCHK(c);
     *n = 0; *consumed = 0; *bad_kind = 0;
     if (counts) memset(counts, 0, sizeof(*counts));
     Indexed in;
-    if ((rc = index_on_device(c, text, text_bytes, final, max_records, max_len, idx_cap_rows, n, in, why))) return rc;
+    TextResults res{ee, ns, pass, len_out, flags_out, {}};
+    StreamQueue q(c);
+    if ((rc = index_on_device(q, text, text_bytes, final, max_records, max_len, idx_cap_rows, n, in, why))) return rc;
     *n = 0;
     if (*why) return MPB_OK;
-    if (in.n > 0x7fffffffll - 4096) return fail(MPB_E_INVALID, "batch of %lld reads exceeds 2^31; split it", (long long)in.n);
-    if (in.longest > MPB_MAX_LEN)
-        return fail(MPB_E_INVALID, "reads longer than 65535 bases are not supported; length (%lld)", (long long)in.longest);
-    int64_t n_pass = 0, n_overflow = 0;
-    TextStage st{};
-    if (in.n > 0) {
-        const int64_t stride = align_up(in.longest > 1 ? in.longest : 1, 128);
-        const int64_t piece_rows = text_piece_rows(in.n, stride);
-        if ((rc = carve(c, c->text_stage, [&](Carver &k) { st.layout_results(k, in.n, piece_rows, stride); }))) return rc;
-        if ((rc = filter_text_pieces(c, in.st.text, text_bytes, in.ix.desc, in.n, stride, piece_rows, fastq_offset, lower_n_is_base, params,
-                                     poisson, st, &n_pass, &n_overflow, bad_record))) return rc;
-    }
-    uint32_t *consumed32 = &c->pin->fq_head[0];
-    uint8_t *kind8 = (uint8_t *)&c->pin->fq_head[1];
-    *consumed32 = 0; *kind8 = 0;
-    const hipError_t e = queue_index_out(c, in, idx_out, consumed32, kind8);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail("hipMemcpyAsync (index)", e); }
-    if (in.n > 0) {
-        if ((rc = text_results_out(c, st, in.n, params, poisson, ee, ns, pass, len_out, flags_out, &n_pass))) return rc;
-    } else {
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    *n = in.n; *consumed = (int64_t)*consumed32; *bad_kind = (int32_t)*kind8;
-    if (counts) { counts->n_reads = in.n; counts->n_pass = n_pass; counts->n_fail = in.n - n_pass; counts->n_overflow = n_overflow; }
-    return MPB_OK;
+    return filter_indexed(q, in, text_bytes, nullptr, idx_out, n, consumed, bad_kind,
+                          FastqFilterAsk{fastq_offset, lower_n_is_base, params, poisson, counts, bad_record}, res);
 }

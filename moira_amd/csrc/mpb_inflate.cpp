@@ -1,13 +1,13 @@
 // mpb_inflate.cpp -- BGZF .gz input on the device, behind the C ABI of libmoira_pb.so (include/moira_pb.h): the host entry that
 // validates its arguments, builds the members' rows (mpb_bgzf_member_rows, mpb_hostonly.cpp), cuts the members into pieces, uploads
 // a piece's compressed bytes and rows, launches k_bgzf_inflate (mpb_inflate_kernels.hip) on it, copies status and text back, and
-// checks the CRC-32 of every taken member's text against its trailer's on a few threads.
+// checks the CRC-32 of every taken member's text against its trailer's on a few threads.  A piece is queued on a StreamQueue
+// (mpb_queue.h) and waited for once; the members' verdict is mpb_hostonly.cpp's, shared with mpb_bgzf_fastq.cpp.
 // (Every mpb_* function defined here has C linkage: include/moira_pb.h declares it inside extern "C".)
 
 #include "mpb_ctx.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <thread>
@@ -30,15 +30,6 @@ struct InflateStage {
 };
 
 struct Piece { int64_t m0, nm, in_lo, in_hi; };             // members [m0, m0 + nm), their bytes in[in_lo, in_hi)
-
-int64_t piece_members()
-{
-    if (const char *e = getenv("MPB_BGZF_INFLATE_PIECE_MEMBERS")) {
-        const long long v = atoll(e);
-        if (v >= 1 && v <= k_piece_members_max) return (int64_t)v;
-    }
-    return k_piece_members_max;
-}
 
 // fn(lo, hi) over [0, n) on a few threads (the caller's among them)
 template <typename F> void on_threads(int64_t n, int64_t min_per_thread, F fn)
@@ -78,7 +69,7 @@ int mpb_bgzf_inflate_host(mpb_ctx *c, const uint8_t *in, int64_t in_len, const i
     std::vector<uint32_t> crc, mstat;
     std::vector<uint8_t> reason;
     std::vector<Piece> pieces;
-    const int64_t per_piece = std::min(piece_members(), n);
+    const int64_t per_piece = std::min(env_int64("MPB_BGZF_INFLATE_PIECE_MEMBERS", 1, k_piece_members_max, k_piece_members_max), n);
     try {
         rows.resize((size_t)n); crc.resize((size_t)n); reason.resize((size_t)n);
         prow.resize((size_t)per_piece); mstat.resize((size_t)n * MPB_INFLATE_MSTAT);
@@ -102,8 +93,8 @@ int mpb_bgzf_inflate_host(mpb_ctx *c, const uint8_t *in, int64_t in_len, const i
                 const int64_t k = p.m0 + p.nm;
                 if (out_offs[k + 1] - out_lo > span_max && p.nm > 0) break;
                 if (rows[(size_t)k].out_len >= 0) {
-                    const int64_t lo = rows[(size_t)k].stream_off, hi = lo + rows[(size_t)k].stream_len;
-                    const int64_t new_lo = any ? std::min(p.in_lo, lo) : lo, new_hi = any ? std::max(p.in_hi, hi) : hi;
+                    int64_t new_lo = p.in_lo, new_hi = p.in_hi;
+                    bgzf_stream_range(&rows[(size_t)k], 1, any, &new_lo, &new_hi);      // (the piece's range widened by this member's)
                     if (new_hi - new_lo > span_max && p.nm > 0) break;
                     p.in_lo = new_lo; p.in_hi = new_hi; any = true;
                 }
@@ -118,13 +109,13 @@ int mpb_bgzf_inflate_host(mpb_ctx *c, const uint8_t *in, int64_t in_len, const i
         }
     } catch (const std::bad_alloc &) { return fail(MPB_E_NOMEM, "out of host memory for the pieces of %lld members", (long long)n); }
 
-    int64_t taken = 0;
     mpb_bgzf_inflate_stats acc;
     memset(&acc, 0, sizeof(acc));
     if (!pieces.empty()) {
         InflateStage st{};
         if ((rc = carve(c, c->inflate_stage, [&](Carver &k) { st.layout(k, in_need, per_piece, text_need); }))) return rc;
         hipStream_t s = c->stream;
+        StreamQueue q(c);                                    // (it leaves before the vectors above)
         for (const Piece &p : pieces) {
             const int64_t in_bytes = p.in_hi - p.in_lo, out_lo = out_offs[p.m0], text_bytes = out_offs[p.m0 + p.nm] - out_lo;
             for (int64_t j = 0; j < p.nm; j++) {             // the rows, relative to the piece's two ranges
@@ -132,24 +123,17 @@ int mpb_bgzf_inflate_host(mpb_ctx *c, const uint8_t *in, int64_t in_len, const i
                 if (r.out_len >= 0) { r.stream_off -= p.in_lo; r.out_off -= out_lo; }
                 prow[(size_t)j] = r;
             }
-            // (everything below is queued on one stream; the host blocks it reads from outlive the synchronisation)
-            hipError_t e = in_bytes > 0 ? hipMemcpyAsync(st.in, in + p.in_lo, (size_t)in_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-            if (e == hipSuccess) e = hipMemcpyAsync(st.rows, prow.data(), (size_t)p.nm * sizeof(mpb_bgzf_member_row), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) {
-                { Span t(c, MPB_K_BGZF_INFLATE);
-                  mpb_launch_bgzf_inflate(st.in, in_bytes, st.rows, p.nm, st.text, text_bytes, st.mstat, s); }
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(&mstat[(size_t)p.m0 * MPB_INFLATE_MSTAT], st.mstat, (size_t)p.nm * MPB_INFLATE_MSTAT * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && text_bytes > 0) e = hipMemcpyAsync(out + out_lo, st.text, (size_t)text_bytes, hipMemcpyDeviceToHost, s);
-            hipError_t e_sync = hipStreamSynchronize(s);
-            HIPCHK_KEPT("k_bgzf_inflate / hipMemcpyAsync (inflate piece)", e);
-            HIPCHK_KEPT("hipStreamSynchronize", e_sync);
+            q.up(st.in, in + p.in_lo, in_bytes);
+            q.up(st.rows, prow.data(), p.nm * (int64_t)sizeof(mpb_bgzf_member_row));
+            q.run(MPB_K_BGZF_INFLATE, [&] { mpb_launch_bgzf_inflate(st.in, in_bytes, st.rows, p.nm, st.text, text_bytes, st.mstat, s); });
+            q.down(&mstat[(size_t)p.m0 * MPB_INFLATE_MSTAT], st.mstat, p.nm * MPB_INFLATE_MSTAT * (int64_t)sizeof(uint32_t));
+            q.down(out + out_lo, st.text, text_bytes);
+            if ((rc = q.wait("k_bgzf_inflate / hipMemcpyAsync (inflate piece)"))) return rc;
             for (int64_t j = 0; j < p.nm; j++) {
                 const int64_t k = p.m0 + j;
                 if (rows[(size_t)k].out_len < 0) continue;
                 const uint32_t w = mstat[(size_t)k * MPB_INFLATE_MSTAT];
-                reason[(size_t)k] = (uint8_t)(w <= MPB_BGZF_WHY_TRAILING_BYTES ? w : MPB_BGZF_WHY_HEADER);
+                reason[(size_t)k] = bgzf_member_reason(w);
                 if (w == MPB_BGZF_WHY_OK) done[k] = 1;       // (until the CRC says otherwise)
             }
         }
@@ -164,15 +148,9 @@ int mpb_bgzf_inflate_host(mpb_ctx *c, const uint8_t *in, int64_t in_len, const i
             }
         });
     }
-    for (int64_t k = 0; k < n; k++) {
-        if (!done[k]) continue;
-        const uint32_t *ms = &mstat[(size_t)k * MPB_INFLATE_MSTAT];
-        taken++;
-        acc.stored_blocks += ms[1]; acc.fixed_blocks += ms[2]; acc.dynamic_blocks += ms[3];
-        acc.literals += ms[4]; acc.matches += ms[5]; acc.matched_bytes += ms[6];
-        acc.longest_code = std::max(acc.longest_code, (int64_t)ms[7]);
-    }
+    for (int64_t k = 0; k < n; k++)
+        if (done[k]) bgzf_stats_add(&acc, &mstat[(size_t)k * MPB_INFLATE_MSTAT]);
     if (why) memcpy(why, reason.data(), (size_t)n);
-    if (stats) { *stats = acc; stats->members = n; stats->taken = taken; stats->handed_back = n - taken; }
+    if (stats) { *stats = acc; stats->members = n; stats->handed_back = n - acc.taken; }
     return MPB_OK;
 }

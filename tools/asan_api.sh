@@ -7,9 +7,11 @@ cd "$(dirname "$0")/.."
 D=${TMPDIR:-/tmp}/mpb_asan; mkdir -p $D
 cat > $D/main.cpp <<'CPP'
 #include "moira_pb.h"
+#include "mpb_hostonly.h"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 int main()
@@ -127,10 +129,63 @@ int main()
         bad += !(mpb_text_rows(idx, 4, nullptr, 4, 100, 0, 0, nullptr, &longest, &badrec) == MPB_E_INVALID && badrec == 2);
         bad += mpb_text_rows(idx, 4, nullptr, -1, 100, 0, 0, nullptr, &longest, &badrec) != MPB_E_INVALID;
     }
+    // what the inflating entries make of a member (internal: mpb_hostonly.h).  The reason of a status word: itself up to
+    // MPB_BGZF_WHY_TRAILING_BYTES, MPB_BGZF_WHY_HEADER for anything the kernel never writes (MPB_BGZF_WHY_CRC included)
+    {
+        for (uint32_t w = 0; w <= MPB_BGZF_WHY_TRAILING_BYTES; w++) bad += bgzf_member_reason(w) != w;
+        bad += bgzf_member_reason(MPB_BGZF_WHY_CRC) != MPB_BGZF_WHY_HEADER;
+        bad += bgzf_member_reason(0xffffffffu) != MPB_BGZF_WHY_HEADER;
+        // three status rows: the counts add up, the longest code is a maximum (the middle row's), the status word is not counted
+        const uint32_t ms[3][8] = {{0, 1, 2, 3, 100, 50, 700, 9}, {0, 0, 0, 1, 0xffffffffu, 7, 0xffffffffu, 15}, {5, 2, 0, 0, 1, 1, 3, 11}};
+        mpb_bgzf_inflate_stats acc;
+        memset(&acc, 0, sizeof(acc));
+        for (int k = 0; k < 3; k++) bgzf_stats_add(&acc, ms[k]);
+        bad += !(acc.taken == 3 && acc.members == 0 && acc.handed_back == 0 && acc.stored_blocks == 3 && acc.fixed_blocks == 2 &&
+                 acc.dynamic_blocks == 4 && acc.literals == 101 + 0xffffffffll && acc.matches == 58 &&
+                 acc.matched_bytes == 703 + 0xffffffffll && acc.longest_code == 15);
+        // the range of the vouched-for streams: all, none (the range is left alone), mixed with the extremes in the middle, and
+        // one more row widening a range that is there
+        mpb_bgzf_member_row rows[5] = {{500, 0, 40, 10}, {100, 10, 30, 10}, {900, 20, 64, 0}, {300, 30, 10, 10}, {600, 40, 10, 10}};
+        int64_t lo = -7, hi = -7;
+        bad += !(bgzf_stream_range(rows, 5, false, &lo, &hi) && lo == 100 && hi == 964);
+        for (int k = 0; k < 5; k++) rows[k].out_len = -1;
+        lo = hi = -7;
+        bad += !(!bgzf_stream_range(rows, 5, false, &lo, &hi) && lo == -7 && hi == -7);
+        bad += bgzf_stream_range(rows, 0, false, &lo, &hi);
+        rows[1].out_len = 10; rows[3].out_len = 0; rows[2].stream_off = 0; rows[0].stream_off = 5000;      // (0 and 5000: not vouched for)
+        bad += !(bgzf_stream_range(rows, 5, false, &lo, &hi) && lo == 100 && hi == 310);
+        rows[4].out_len = 10;
+        bad += !(bgzf_stream_range(rows + 4, 1, true, &lo, &hi) && lo == 100 && hi == 610);
+        bad += !(bgzf_stream_range(rows, 1, true, &lo, &hi) && lo == 100 && hi == 610);                    // (a row not vouched for widens nothing)
+    }
+    // env_int64: unset, empty, below the range, at its ends, above it, no number
+    {
+        const char *name = "MPB_ASAN_API_ENV_INT64";
+        unsetenv(name);
+        bad += env_int64(name, 1, 1024, 77) != 77;
+        const struct { const char *text; int64_t want; } cases[] = {{"", 77}, {"0", 77}, {"-5", 77}, {"1", 1}, {"1024", 1024}, {"1025", 77},
+                                                                    {"99999999999999", 77}, {"many", 77}, {"12", 12}};
+        for (const auto &cs : cases) { setenv(name, cs.text, 1); bad += env_int64(name, 1, 1024, 77) != cs.want; }
+        setenv(name, "268435455", 1);                        // MPB_TEXT_PIECE_BYTES' range: 0 < v < 256 MiB
+        bad += env_int64(name, 1, (256ll << 20) - 1, 256ll << 20) != 268435455;
+        setenv(name, "268435456", 1);
+        bad += env_int64(name, 1, (256ll << 20) - 1, 256ll << 20) != 256ll << 20;
+        unsetenv(name);
+    }
+    // the refusals the entries share: the same words with and without an entry's name in front
+    {
+        bad += check_fastq_offset(0) != MPB_OK || check_fastq_offset(255, "who") != MPB_OK;
+        bad += check_fastq_offset(256) != MPB_E_INVALID;
+        bad += std::strcmp(mpb_last_error(), "fastq_offset 256: the device pack takes offsets 0..255 (beyond them no character is a quality)") != 0;
+        bad += check_fastq_offset(-1, "mpb_filter_bgzf_fastq_host") != MPB_E_INVALID;
+        bad += std::strcmp(mpb_last_error(), "mpb_filter_bgzf_fastq_host: fastq_offset -1: the device pack takes offsets 0..255 (beyond them no character is a quality)") != 0;
+        bad += check_text_bytes(1ll << 30) != MPB_OK || check_text_bytes((1ll << 30) + 1) != MPB_E_INVALID;
+        bad += std::strcmp(mpb_last_error(), "text of 1073741825 bytes: one call takes at most 1073741824 bytes (1 GiB) of text; split the chunk") != 0;
+    }
     std::printf("asan_api: %d failed checks, version %s\n", bad, mpb_version());
     return bad != 0;
 }
 CPP
-g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -pthread -Iinclude \
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -pthread -Iinclude -Imoira_amd/csrc \
     moira_amd/csrc/mpb_hostonly.cpp $D/main.cpp -o $D/asan_api
 ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $D/asan_api
