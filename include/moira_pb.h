@@ -152,7 +152,8 @@ extern "C" {
 #define MPB_K_POISSON_TAIL 10 /* Poisson approximation: the CDF tail on the device (percentile, +Ns / floor, predicate) */
 #define MPB_K_PACK_TEXT 11   /* FASTQ text + record index -> the packed ragged matrix (k_pack_text) */
 #define MPB_K_CONTIG    12   /* paired-read contigs: the launches of one chunk, one per size class (k_contig) */
-#define MPB_K_CONTIG_ROWS 13 /* the device's contig index -> k_pack_text's row descriptors (k_contig_rows) */
+#define MPB_K_CONTIG_ROWS 13 /* the device's contig index -> k_pack_text's row descriptors (k_contig_rows); also the four pairing
+                              kernels of mpb_contigs_filter_fastq_host (k_pair_rows / _count / _scan / _lists) */
 #define MPB_K_BGZF_DEFLATE 14 /* .gz output on the device: one raw-deflate stream per BGZF member (k_bgzf_deflate) */
 #define MPB_K_BGZF_SCAN  15  /* ... the prefix of the members' sizes (k_bgzf_scan) */
 #define MPB_K_BGZF_FRAME 16  /* ... header, stream and trailer of every member into the dense output (k_bgzf_frame) */
@@ -577,6 +578,51 @@ int mpb_contigs_filter_text_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_
                                  int32_t max_len, int32_t lower_n_is_base, const mpb_filter_params *filter_params, int32_t poisson,
                                  double *ee, int32_t *ns, uint8_t *pass, int32_t *len_out, uint8_t *flags_out, uint8_t *filtered,
                                  mpb_filter_counts *counts, int *filter_rc, int64_t *filter_bad_record);
+
+/*
+ * The chunk call with the filter behind it from the two mates' TEXT ALONE (opt-in): nothing is built on the host.  Both texts are
+ * uploaded once and indexed on the device as mpb_fastq_index_host indexes one; the pairing step (csrc/mpb_pair_kernels.hip:
+ * k_pair_rows, k_pair_count, k_pair_scan, k_pair_lists; what a lane does: csrc/mpb_pair_lane.inc) turns the two device-written
+ * indexes into what the host builds today -- mio_first_header_mismatch's comparison, mpb_pair_rows' validated descriptors, the
+ * LDS size classes and the class lists in pair order -- and mpb_contigs_filter_text_host runs from there, from its k_contig
+ * launches on, in its order and with its errors.  k_contig reads the texts where the index kernels read them.
+ *   ftext / rtext, ffinal / rfinal, max_records     as mpb_fastq_index_host's, per text (each at most 1 GiB)
+ *   fidx_out, ridx_out        int64[idx_cap_rows][MPB_IDX_COLS]; rows [0, n_k + (k_bad_kind ? 1 : 0)) are written
+ *   n_f, f_bad_kind, n_r, r_bad_kind     what mio_fastq_index(text_k, final_k, max_records) returns for each text
+ *   n_pairs                   min(n_f, n_r)
+ *   mismatch                  the first pair < n_pairs whose header tokens differ (mio_first_header_mismatch), or -1
+ *   n_built                   mismatch < 0 ? n_pairs : mismatch: the pairs the chunk call runs over
+ *   f_consumed, r_consumed    the first byte behind record n_pairs - 1 of each text: what mio_fastq_index(text_k, final_k, n_pairs)
+ *                             consumes
+ *   why, which                MPB_FQ_WHY_* as mpb_fastq_index_host's, and the text it speaks of (0 forward, 1 reverse; the forward
+ *                             text is looked at first).  MPB_FQ_WHY_ROW_CHECK also when a device-written index row of a pair
+ *                             < n_built fails one of mpb_pair_rows' checks (never expected).  *why != 0: NOTHING ELSE is defined
+ *   rec_cap_out               the slot size the call chose: max over the n_built pairs of hdr_len + 2 (l1 + l2), plus 8
+ *   out_buf[out_cap_bytes]    n_built slots of rec_cap bytes; every per-pair array (out_idx, overlap, gaps, mismatches, done, ee,
+ *                             ns, pass, len_out, flags_out, filtered) holds idx_cap_rows entries, of which n_built are written
+ * and max_len .. filter_bad_record are mpb_contigs_filter_text_host's.  There are no alignment strings and no contigs-only form.
+ * CONTRACT, when *why == 0: the two indexes, n_f, n_r, the bad kinds and the consumed words equal the host indexer's; mismatch
+ * equals mio_first_header_mismatch's over n_pairs pairs; and every other output is bit-identical to mpb_contigs_filter_text_host
+ * on those two indexes cut to n_built rows with rec_cap = *rec_cap_out.  The device defines no error about content: a pair it does
+ * not take is handed back (done = 0) exactly as there, and the caller builds it from the returned index rows.
+ * Argument errors are MPB_E_INVALID and are said with or without a device; then make_contig's and the filter's parameter checks.
+ * Two capacities are known only once the device has counted: an idx_cap_rows below min(max_records, lines / 4) + 1 of either text
+ * is MPB_E_INVALID with the two needed record counts in *n_f / *n_r, and n_built * rec_cap > out_cap_bytes is MPB_E_INVALID with
+ * *rec_cap_out and *n_pairs set (n_built <= n_pairs), so that a caller who guessed may ask again.
+ * Timing: the four pairing kernels have no kernel id of their own (MPB_K_COUNT stays); they run inside MPB_K_CONTIG_ROWS' spans, as
+ * k_bgzf_crc32 runs inside MPB_K_BGZF_INFLATE's.  Synchronous; the staging blocks belong to the context.
+ */
+int mpb_contigs_filter_fastq_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_bytes, int32_t ffinal,
+                                  const char *rtext, int64_t rtext_bytes, int32_t rfinal, int64_t max_records, int32_t fastq_offset,
+                                  const mpb_contig_params *params, int64_t *fidx_out, int64_t *ridx_out, int64_t idx_cap_rows,
+                                  int64_t *n_f, int32_t *f_bad_kind, int64_t *n_r, int32_t *r_bad_kind, int64_t *n_pairs,
+                                  int64_t *mismatch, int64_t *n_built, int64_t *f_consumed, int64_t *r_consumed, int32_t *why,
+                                  int32_t *which, int64_t *rec_cap_out, char *out_buf, int64_t out_cap_bytes, int64_t *out_idx,
+                                  int32_t *overlap, int32_t *gaps, int32_t *mismatches, uint8_t *done, int64_t *n_done,
+                                  int64_t *n_handed_back, int32_t max_len, int32_t lower_n_is_base,
+                                  const mpb_filter_params *filter_params, int32_t poisson, double *ee, int32_t *ns, uint8_t *pass,
+                                  int32_t *len_out, uint8_t *flags_out, uint8_t *filtered, mpb_filter_counts *counts, int *filter_rc,
+                                  int64_t *filter_bad_record);
 
 /*
  * .gz output on the device (opt-in; the default compressor stays the host's zlib).  The text is cut into BGZF members (SAM/BAM

@@ -147,6 +147,15 @@ PROTOTYPES = {
                                                _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.c_int32, C.c_int32, C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                                C.POINTER(FilterCounts), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "mpb_contigs_filter_fastq_host": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int32, C.c_int64, C.c_int32,
+                                                C.POINTER(ContigParams), _VP, _VP, C.c_int64, C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP,
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                                C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                                C.POINTER(FilterCounts), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mpb_bgzf_bound": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
     "mpb_bgzf_compress_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(BgzfStats)]),
     "mpb_bgzf_member_rows": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),

@@ -28,7 +28,9 @@ BGZF_KERNELS = os.path.join(CSRC, "mpb_bgzf_kernels.hip")          # k_bgzf_defl
 INFLATE_KERNELS = os.path.join(CSRC, "mpb_inflate_kernels.hip")    # k_bgzf_inflate: BGZF .gz input, one more unit of its own
 INDEX_KERNELS = os.path.join(CSRC, "mpb_index_kernels.hip")        # k_fq_lines / _scan / _starts / _rows: the FASTQ record index, likewise
 CRC_KERNELS = os.path.join(CSRC, "mpb_crc_kernels.hip")            # k_bgzf_crc32: the CRC-32 of inflated text where it lies, likewise
-SOURCES = [os.path.join(CSRC, "mpb_kernels.hip"), CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS] + HOST_SOURCES
+PAIR_KERNELS = os.path.join(CSRC, "mpb_pair_kernels.hip")          # k_pair_rows / _count / _scan / _lists: two record indexes -> k_contig's inputs, likewise
+SOURCES = [os.path.join(CSRC, "mpb_kernels.hip"), CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS,
+           PAIR_KERNELS] + HOST_SOURCES
 DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_host_internal.h"),
                   os.path.join(CSRC, "mpb_shared.h"), os.path.join(CSRC, "mpb_hostonly.h"), os.path.join(CSRC, "mpb_ctx.h"),
                   os.path.join(CSRC, "mpb_queue.h"),
@@ -41,6 +43,7 @@ DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_
                   os.path.join(CSRC, "mpb_inflate_lane.inc"),
                   os.path.join(CSRC, "mpb_index_lane.inc"),
                   os.path.join(CSRC, "mpb_crc_lane.inc"),
+                  os.path.join(CSRC, "mpb_pair_lane.inc"),
                   os.path.join(CSRC, "contig_posterior.h"),
                   os.path.join(CSRC, "libmoira_pb.map"),
                   os.path.join(ROOT, "include", "moira_pb.h"),
@@ -164,7 +167,7 @@ if __name__ == "__main__":
         print(" ".join(os.path.relpath(p, ROOT) for p in HOST_SOURCES))
         sys.exit(0)
     if "--units-beside-kernels" in sys.argv:     # every unit besides mpb_kernels.hip, which such a script replaces by its variant
-        print(" ".join(os.path.relpath(p, ROOT) for p in [CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS] + HOST_SOURCES))
+        print(" ".join(os.path.relpath(p, ROOT) for p in [CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS, PAIR_KERNELS] + HOST_SOURCES))
         sys.exit(0)
     build(force="--force" in sys.argv, verbose=True)
     build_contig(force="--force" in sys.argv, verbose=True)

@@ -250,6 +250,12 @@ def build_parser():
                         "127) is indexed on the host as always, with one message, so errors and output files are identical. Paired "
                         "input and fasta+qual input stay on the host indexer; where the switch does not apply one line says so. "
                         + DEVICE_INDEX_MEASURED)
+    f.add_argument("--device_pair_index", action="store_true",
+                   help="(not in moira.py) with --device_contigs and --device_pack, paired FASTQ input on one GPU: build both record "
+                        "indexes, compare the headers and pair and bucket the mates on the device too, in the same call that builds "
+                        "and filters the contigs (each file's text goes up once and the host indexer does not run). A pair of blocks "
+                        "the device does not take is indexed on the host as always, with one message, so errors and output files "
+                        "are identical. Where it does not apply one line says so. Not measured yet: no rate is promised.")
     f.add_argument("--device_compress", action="store_true",
                    help="(not in moira.py) with -oc gz on one GPU: compress the .gz outputs on the device (BGZF members of 65,280 "
                         "text bytes, one workgroup each, batches of 16 MiB of text per call on a context of its own) instead of "
@@ -844,7 +850,7 @@ class _Role:
 
 
 class _DevicePaths:
-    """The opt-in device paths of one run, resolved (`on`: the switches in force): .pack, .contigs, .index, and .compressor / .inflater
+    """The opt-in device paths of one run, resolved (`on`: the switches in force): .pack, .contigs, .index, .pair_index, and .compressor / .inflater
     (a _Role or None).  It owns the run's ONE auxiliary Engine on the filter's device (--device_compress, --device_inflate, or
     both: no third context), behind ONE lock: calls on one context must not overlap (include/moira_pb.h), and the writers' pool
     threads and the read-ahead threads (two for a paired run) run beside the filtering thread.  make: the engine's constructor."""
@@ -856,6 +862,9 @@ class _DevicePaths:
         self.index_refused = _SaidOnce(say, "--device_index: the device did not take a block (%s): the host indexer is used for it.")
         self.members_refused = _SaidOnce(say, "--device_inflate with --device_index: the device did not take a batch of members (%s): "
                                          "it is inflated by the two-call path.")
+        self.pair_index = "device_pair_index" in on
+        self.pair_index_refused = _SaidOnce(say, "--device_pair_index: the device did not take a pair of blocks (%s): the host indexer "
+                                                 "and the fused contig call are used for it.")
         self.members = False                          # the fused BGZF call is taken (set by the run once it knows the filter's engine)
         self.engine = self.compressor = self.inflater = None
         if "device_compress" in on or "device_inflate" in on:
@@ -1075,6 +1084,18 @@ def _device_index_eligible(args, backend):
     """--device_index applies to single-end FASTQ input that --device_pack takes, on a backend whose engine indexes text on its device."""
     return bool(_device_pack_eligible(args, backend) and not args.paired and not args.only_contig
                 and hasattr(getattr(backend, "engine", None), "filter_fastq"))
+
+
+def _device_pair_index_eligible(args, backend, on):
+    """--device_pair_index applies to paired FASTQ input of a run in which --device_contigs and --device_pack are both in force
+    (`on`) and take the fused call, on a backend whose engine has the text-alone paired call."""
+    return bool(args.paired and args.forward_fastq and "device_contigs" in on and "device_pack" in on
+                and _fused_applies(True, True, args.only_contig, backend)
+                and hasattr(getattr(backend, "engine", None), "contigs_filter_fastq"))
+
+
+DEVICE_PAIR_INDEX_SENTENCE = ("--device_pair_index does not apply to this run (it takes paired FASTQ input of the byte-level parser on one "
+                              "GPU, with --device_contigs and --device_pack): the host indexer is used.")
 
 
 def _device_compress_eligible(args, backend):
@@ -1311,6 +1332,96 @@ class _DeviceIndexer:
             self.carry = data
 
 
+PAIR_INDEX_BLOCK = 1 << 24        # --device_pair_index: bytes of text per read of either file (fastio.PairedFastqChunks' block)
+
+
+class _DeferredPairStreams:
+    """The two files of a paired run as two streams of _DeferredBlocks, each read ahead by a thread of its own, for whoever takes
+    the item off the queue (--device_pair_index): nothing is indexed on the producer side.  The consumer thread is the one that
+    filters on the context, so it makes the call that indexes, pairs, builds and filters (_DevicePairIndexer), and it closes the
+    item when it is done with it."""
+
+    def __init__(self, fhs, block_bytes):
+        self.fhs, self.block = fhs, block_bytes
+        self.blocks = [_prefetched(_read_blocks(fh, block_bytes)) for fh in fhs]
+
+    def close(self):
+        for it in self.blocks:
+            it.close()
+        for fh in self.fhs:
+            fh.close()
+
+
+class _DevicePairIndexer:
+    """The consumer's side of --device_pair_index: it owns both files' tails and is fastio.PairedFastqChunks.__iter__'s loop with ONE
+    device call in place of the two index calls -- device(fbuf, rbuf, ffinal, rfinal, max_records) -> (res, cbuf, cidx, aux, ee,
+    has_n, filter_error) (moira_amd.contig.contigs_from_fastq_text_filtered) -- which also builds and filters the contigs.  It
+    yields what a fused chunk yields, (cbuf, cidx, aux, ee, has_n, filter_error), and keeps that loop's rules: want / has_next / eof,
+    the pairs first and then the error of the pair reached, forward file first, forward_header set on a reverse-file error, the
+    record error of pair n only when both files hold record n, zip() stopping with the shorter file.  A header mismatch yields the
+    pairs before it and then raises NameMismatchError, as _fast_chunks does.  A pair of blocks the device hands back (not_taken),
+    or whose call ends in a ValueError, goes through fastio.index x 2 and host(fbuf, fidx, rbuf, ridx), today's fused call; the
+    first such pair is reported.  A fastio.Unsupported of the host indexer is the run's to take."""
+
+    def __init__(self, device, host, max_records, refused, threads=1, not_taken=None):
+        if not_taken is None:
+            from .engine import NotTaken as not_taken
+        self.device, self.host, self.max_records, self.refused, self.threads, self.not_taken = device, host, max_records, refused, threads, not_taken
+
+    def _one(self, tail, eof):
+        """One pass over the two tails -> (fidx, ridx, (f_bad, r_bad), n, (f_consumed, r_consumed), mismatch, built or None)."""
+        from . import fastio as F
+        try:
+            res, *built = self.device(tail[0], tail[1], eof[0], eof[1], self.max_records)
+            return res.fidx, res.ridx, (res.f_bad, res.r_bad), res.n_pairs, (res.f_consumed, res.r_consumed), res.mismatch, \
+                (tuple(built) if res.n_built else None)
+        except (self.not_taken, ValueError) as e:
+            self.refused(e)
+        got = [F.index(tail[k], eof[k], self.max_records, self.threads) for k in (0, 1)]
+        n = min(len(got[0][0]), len(got[1][0]))
+        consumed = [got[k][1] if len(got[k][0]) == n else F.index(tail[k], eof[k], n, self.threads)[1] for k in (0, 1)] if n else [0, 0]
+        bad = F.first_header_mismatch(tail[0], got[0][0][:n], tail[1], got[1][0][:n]) if n else -1
+        nb = n if bad < 0 else bad
+        built = self.host(tail[0], got[0][0][:nb], tail[1], got[1][0][:nb]) if nb else None
+        return got[0][0], got[1][0], (got[0][2], got[1][2]), n, consumed, bad, built
+
+    def run(self, streams):
+        from . import fastio as F
+        tail, eof, want = [b"", b""], [False, False], [True, True]
+        while True:
+            for k in (0, 1):
+                if want[k] and not eof[k]:
+                    blk = next(streams.blocks[k])
+                    if blk.data:
+                        tail[k] = tail[k] + blk.data if tail[k] else blk.data
+                    eof[k] = blk.eof
+            idx = [None, None]
+            idx[0], idx[1], bad, n, consumed, mismatch, built = self._one(tail, eof)
+            # does file k hold a complete record number n (sound or not)?
+            has_next = [len(idx[k]) > n or bad[k] is not None for k in (0, 1)]
+            err = None
+            if has_next[0] and has_next[1]:
+                for k in (0, 1):
+                    if err is None and bad[k] is not None and len(idx[k]) == n:
+                        err = F.PairedRecordError(k, bad[k])
+                if err is not None and err.which == 1:       # then forward record n is sound: the reference names it
+                    err.err.forward_header = F.header_of(tail[0], idx[0][n])
+            if n:
+                if built is not None:
+                    yield built
+                if mismatch >= 0:
+                    raise NameMismatchError(F.header_of(tail[0], idx[0][mismatch]), None, F.header_of(tail[1], idx[1][mismatch]), None)
+                tail = [tail[k][consumed[k]:] for k in (0, 1)]
+            if err is not None:
+                raise err
+            if n == self.max_records:
+                want = [len(tail[k]) < streams.block for k in (0, 1)]
+                continue
+            if any(not has_next[k] and eof[k] for k in (0, 1)):
+                return                                       # one file is exhausted: zip() stops here
+            want = [not has_next[k] for k in (0, 1)]
+
+
 def _members_reader(filename, threads, inflater):
     """The file's GzipReader when it is a gzip file that the package's own reader takes, else None (the fused BGZF call reads
     members, not text: no read-ahead thread stands between)."""
@@ -1353,6 +1464,9 @@ def _fast_chunks(args, paths, contig_engine=None, fused=None):
         return
     half = max(1, _text_threads(args) // 2)
     ffh, rfh = open_input_binary(args.forward_fastq, half, paths.inflater), open_input_binary(args.reverse_fastq, half, paths.inflater)
+    if paths.pair_index:
+        yield _DeferredPairStreams((ffh, rfh), PAIR_INDEX_BLOCK)     # (--device_pair_index: the consumer indexes, and closes the files)
+        return
     try:
         # reading + indexing the two files runs one chunk ahead of contig construction, on a thread of its own
         for fbuf, fidx, rbuf, ridx in _prefetched(iter(F.PairedFastqChunks(ffh, rfh, PAIR_CHUNK_READS, threads=_text_threads(args))), depth=1):
@@ -1584,12 +1698,38 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
                                      CHUNK_READS, paths.index_refused, threads, members_refused=paths.members_refused)
             paths.members = paths.inflater is not None and hasattr(backend.engine, "filter_bgzf_fastq")
 
+        pair_indexer = None
+        if paths.pair_index:
+            from . import contig as CT
+            choice = backend.text_choice(args.alpha, args.ambigs, args.round, method, fd)
+            rest = lambda buf, idx, sel: backend.text(buf, idx, args.alpha, args.ambigs, args.round, in_off, T, n_is_base, method=method,
+                                                      fast_discard=fd, sel=sel)
+
+            def device_pairs(fbuf, rbuf, ffinal, rfinal, max_records):
+                try:
+                    return CT.contigs_from_fastq_text_filtered(
+                        fbuf, rbuf, ffinal, rfinal, max_records, in_off, args.match, args.mismatch, args.gap, args.insert, args.deltaq,
+                        args.consensus_qscore, args.qscore_cap, args.trim_overlap, threads=args.processors, engine=backend.engine,
+                        backend_text=rest, max_len=T, lower_n_is_base=n_is_base, **choice)
+                except CT.QualityRange as e:
+                    raise F.Unsupported(str(e))
+            pair_indexer = _DevicePairIndexer(device_pairs, lambda *a: _chunk_contigs_filtered(args, *a, in_off, *fused), PAIR_CHUNK_READS,
+                                              paths.pair_index_refused, threads)
+
         def chunks():
             # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context; with
             # --device_pack as well they are filtered where they lie, in the same call.  --device_index: the same for a block
             # of text, which may hold several chunks, or none)
             for chunk in _prefetched(_fast_chunks(args, paths, backend.engine if paths.contigs else None, fused)):
-                if isinstance(chunk, (_DeferredBlock, _DeferredMembers)):
+                if isinstance(chunk, _DeferredPairStreams):
+                    try:
+                        for built in pair_indexer.run(chunk):
+                            yield _filtered_where_built(built)
+                    except F.PairedRecordError as e:
+                        raise _record_error(e.which, e.err, args)
+                    finally:
+                        chunk.close()
+                elif isinstance(chunk, (_DeferredBlock, _DeferredMembers)):
                     try:
                         yield from (indexer.take(chunk) if isinstance(chunk, _DeferredBlock) else indexer.take_members(chunk))
                     except F.RecordError as e:
@@ -1770,6 +1910,11 @@ def main(args, backend=None, out=None, _no_fastio=False):
             on.add(switch)
         elif warn is not None:
             warn(sentence)
+    if getattr(args, "device_pair_index", False):            # (after the table: it asks for two of its switches)
+        if fast and _device_pair_index_eligible(args, backend, on):
+            on.add("device_pair_index")
+        elif warn is not None:
+            warn(DEVICE_PAIR_INDEX_SENTENCE)
     paths = _DevicePaths(on, getattr(getattr(backend, "engine", None), "device", None), warn)
     from . import fastio
     try:

@@ -253,6 +253,14 @@ def contigs_from_fastq_filtered(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1
     res = engine.contigs_filter_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
                                      CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, rec_cap=rec_cap, max_len=max_len,
                                      lower_n_is_base=lower_n_is_base, poisson=poisson, **kw)
+    return _merge_filtered(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq, consensus_qscore,
+                           qscore_cap, trim_overlap, threads, rec_cap, backend_text)
+
+
+def _merge_filtered(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq, consensus_qscore, qscore_cap,
+                    trim_overlap, threads, rec_cap, backend_text):
+    """What follows either fused device call: the host builds the pairs that were handed back, and backend_text filters every
+    pair the call did not filter -> (cbuf, cidx, aux, ee, has_n, filter_error)."""
     cbuf, cidx, aux = _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
                                                consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap)
     ee, has_n = np.array(res.ee, np.float64), np.array(res.has_n, bool)
@@ -265,3 +273,32 @@ def contigs_from_fastq_filtered(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1
         except ValueError as e:                          # a host-built contig the text filter refuses: the chunk's error as well
             return cbuf, cidx, aux, ee, has_n, e
     return cbuf, cidx, aux, ee, has_n, None
+
+
+def contigs_from_fastq_text_filtered(fbuf, rbuf, ffinal=True, rfinal=True, max_records=None, fastq_offset=33, match=1, mismatch=-1,
+                                     gap=-2, insert=20, deltaq=6, consensus_qscore="best", qscore_cap=40, trim_overlap=False,
+                                     threads=None, engine=None, backend_text=None, max_len=0, lower_n_is_base=False, poisson=False,
+                                     **kw):
+    """contigs_from_fastq_filtered from the two mates' text ALONE (Engine.contigs_filter_fastq: the record indexes, the header
+    comparison and the pairing are the device's) -> (res, cbuf, cidx, aux, ee, has_n, filter_error): res is the call's
+    PairedFastqResult (.fidx, .ridx, .f_bad, .r_bad, .f_consumed, .r_consumed, .mismatch, .n_built) and the six others are
+    contigs_from_fastq_filtered's over the n_built pairs, merged the same way from the index rows the device returned.
+    engine.NotTaken and ValueError are the call's: the caller indexes on the host and goes through contigs_from_fastq_filtered."""
+    L = load()
+    if consensus_qscore not in CONSENSUS:
+        raise ValueError('consensus_qscore must be "best", "sum" or "posterior".')
+    if engine is None:
+        raise ValueError("contigs_from_fastq_text_filtered needs an engine: the fused call has no host form")
+    threads = threads or usable_cpus()
+    if backend_text is None:
+        def backend_text(buf, idx, sel):
+            r = engine.filter_text(buf, idx, sel=sel, fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base,
+                                   poisson=poisson, **kw)
+            return r.ee, r.has_n
+    res = engine.contigs_filter_fastq(fbuf, rbuf, ffinal, rfinal, max_records, fastq_offset, match, mismatch, gap, insert, deltaq,
+                                      CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, max_len=max_len,
+                                      lower_n_is_base=lower_n_is_base, poisson=poisson, **kw)
+    n = res.n_built
+    return (res,) + _merge_filtered(res, L, fbuf, np.ascontiguousarray(res.fidx[:n]), rbuf, np.ascontiguousarray(res.ridx[:n]),
+                                    fastq_offset, match, mismatch, gap, insert, deltaq, consensus_qscore, qscore_cap, trim_overlap,
+                                    threads, res.rec_cap, backend_text)

@@ -9,6 +9,11 @@
 
 #define MPB_CONTIG_LDS_MAX 65536          // the largest dynamic LDS block a launch asks for
 
+// The LDS size classes of a call, as a kernel takes them by value: cap[0 .. n) ascending (the table itself is k_lds_class[] of
+// mpb_contig.cpp, which buckets on the host with it and hands it to k_pair_rows, which buckets on the device)
+#define MPB_LDS_CLASS_MAX 16
+struct MpbLdsClasses { int32_t cap[MPB_LDS_CLASS_MAX]; int32_t n; };
+
 struct MpbContigArgs {
     const uint8_t *ftext; int64_t fbytes;                // capacity round_up(bytes, 16), zero past the text
     const uint8_t *rtext; int64_t rbytes;

@@ -110,6 +110,10 @@ struct PinWords {
     int64_t text_status[2];                              // mpb_filter_text_host: k_pack_text's status, both ways
     uint32_t fq_head[4];                                 // the device index: k_fq_scan's head words {newlines, refusal flags, lines, 0}
     int64_t fq_status[4];                                // ... k_fq_rows' status, both ways; [3]: the first byte behind the last record
+    uint32_t fq_head2[4];                                // mpb_contigs_filter_fastq_host: the same two blocks of the reverse text
+    int64_t fq_status2[4];
+    int64_t pair_status[4];                              // ... k_pair_rows' / k_pair_count's status, both ways
+    uint32_t pair_head[MPB_PAIR_HEAD_WORDS];             // ... k_pair_scan's head words: the pairs per class, the classes' first places
 };
 
 struct TimedSpan { int kid; hipEvent_t a, b; };
@@ -182,6 +186,7 @@ struct mpb_ctx {
     Buf inflate_stage{BUF_DEVICE};       // mpb_bgzf_inflate_host: one piece of compressed bytes | rows | status rows | the piece's text
     Buf fastq_stage{BUF_DEVICE};         // mpb_fastq_index_host / mpb_filter_fastq_host: text | tile table | prefix | head | status
     Buf fastq_index{BUF_DEVICE};         // ... and, sized from the counted lines: line starts | index rows | kinds | descriptors
+                                         // (mpb_contigs_filter_fastq_host: both texts' shares of either block, one carve each, and the pairing block)
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)
@@ -318,10 +323,11 @@ struct Indexed {                                             // what the device 
     FastqIndex ix{};
     int64_t n = 0, rows = 0, longest = 0;                    // records; rows of the index (n, or n + 1: the offender's); longest packed length
 };
-// k_fq_lines, k_fq_scan and the copy of the head words to the pinned block, queued over the text that lies in out.st.text; after
+// k_fq_lines, k_fq_scan and the copy of the head words to the pinned block (pin_head; null: fq_head), queued over the text that lies in
+// out.st.text; after
 // the caller's wait fastq_index_finish does the rest (*why != 0: handed back; it waits for what it queues); queue_index_out
 // queues the copies of the index's rows, the offender's kind and the first byte behind the last record
-void fastq_index_queue_head(StreamQueue &q, Indexed &out, int64_t text_bytes, int32_t final);
+void fastq_index_queue_head(StreamQueue &q, Indexed &out, int64_t text_bytes, int32_t final, uint32_t *pin_head = nullptr);
 int fastq_index_finish(StreamQueue &q, int64_t text_bytes, int64_t max_records, int32_t max_len, int64_t idx_cap_rows, int64_t *n_needed,
                        Indexed &out, int32_t *why);
 void queue_index_out(StreamQueue &q, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8);

@@ -23,14 +23,14 @@ int check_args(const char *text, int64_t text_bytes, int64_t max_records, int32_
 }  // namespace
 
 // k_fq_lines, k_fq_scan and the copy of the head words to the pinned block, queued over the text that lies in out.st.text
-void fastq_index_queue_head(StreamQueue &q, Indexed &out, int64_t text_bytes, int32_t final)
+void fastq_index_queue_head(StreamQueue &q, Indexed &out, int64_t text_bytes, int32_t final, uint32_t *pin_head)
 {
     hipStream_t s = q.c->stream;
     const int64_t n_tiles = (text_bytes + MPB_FQ_TILE - 1) / MPB_FQ_TILE;
     FastqStage &st = out.st;
     q.run(MPB_K_FQ_LINES, [&] { mpb_launch_fq_lines(st.text, text_bytes, n_tiles, st.info, s); });
     q.run(MPB_K_FQ_SCAN, [&] { mpb_launch_fq_scan(st.text, text_bytes, final != 0, st.info, n_tiles, st.prefix, st.head, s); });
-    q.down(q.c->pin->fq_head, st.head, 4 * sizeof(uint32_t));
+    q.down(pin_head ? pin_head : q.c->pin->fq_head, st.head, 4 * sizeof(uint32_t));
 }
 
 // What follows the wait behind fastq_index_queue_head: the head words' verdict, the blocks sized from the counted lines,

@@ -285,6 +285,21 @@ void mpb_launch_fq_rows(const uint8_t *text, int64_t text_bytes, const uint32_t 
 struct mpb_crc_range { int64_t off; int32_t len, pad; };     // 16 bytes
 void mpb_launch_bgzf_crc32(const uint8_t *text, int64_t text_bytes, const mpb_crc_range *ranges, int64_t n, uint32_t *crc,
                            uint32_t *bad, hipStream_t s);
+// From two device-written record indexes to k_contig's inputs (mpb_pair_kernels.hip; what a lane does: mpb_pair_lane.inc).
+// k_pair_rows: rows 0..m-1 of fidx / ridx (not trusted) -> rows[m] as mpb_pair_rows writes them (a pair that fails a check: a row
+// cd_row_ok refuses) and cls[m], the LDS size class by `classes` (-1: none; take == false: none at all); status[4] (set to
+// {INT64_MAX, INT64_MAX, 0, 0} by the caller): [0] the first pair whose header tokens differ, [1] the first whose rows fail a check.
+// k_pair_count + k_pair_scan over pairs 0..n-1: table / prefix [ceil(n / 256)][16], head[MPB_PAIR_HEAD_WORDS] = the pairs per class,
+// then the classes' first places in the list; status[2] = the largest hdr_len + 2 (l1 + l2), status[3] = the largest l1 + l2 of a
+// pair with a class.  k_pair_lists: list[n], every class' pairs ascending behind each other.
+#define MPB_PAIR_HEAD_WORDS 32
+struct MpbLdsClasses;
+void mpb_launch_pair_rows(const int64_t *fidx, const int64_t *ridx, int64_t m, const uint8_t *ftext, int64_t fbytes, const uint8_t *rtext,
+                          int64_t rbytes, int maxabs, bool take, const MpbLdsClasses &classes, mpb_pair_row *rows, int8_t *cls,
+                          int64_t *status, hipStream_t s);
+void mpb_launch_pair_count(const mpb_pair_row *rows, const int8_t *cls, int64_t n, uint32_t *table, uint32_t *prefix, uint32_t *head,
+                           int64_t *status, hipStream_t s);
+void mpb_launch_pair_lists(const int8_t *cls, int64_t n, const uint32_t *prefix, const uint32_t *head, int32_t *list, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

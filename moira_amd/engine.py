@@ -70,11 +70,12 @@ class TextFilterResult(FilterResult):
 class NotTaken(Exception):
     """The device did not take a text for indexing (Engine.fastq_index, Engine.filter_fastq): .why is MPB_FQ_WHY_* (1 a byte
     >= 0x80, 2 a lone carriage return, 3 the line table would not fit, 4 a row check failed), str() names it.  The caller
-    indexes on the host (fastio.index), which raises whatever there is to raise."""
+    indexes on the host (fastio.index), which raises whatever there is to raise.  .which: the text it speaks of where a call takes
+    two (Engine.contigs_filter_fastq: 0 forward, 1 reverse), else None."""
 
-    def __init__(self, why):
+    def __init__(self, why, which=None):
         Exception.__init__(self, L.FQ_WHY[why] if 0 <= why < len(L.FQ_WHY) else "reason %d" % why)
-        self.why = why
+        self.why, self.which = why, which
 
 
 class FastqFilterResult(TextFilterResult):
@@ -200,6 +201,21 @@ class ContigFilterResult(ContigResult):
         for k in ContigResult.__slots__:
             setattr(self, k, getattr(contigs, k))
         for k, v in zip(ContigFilterResult.__slots__, a):
+            setattr(self, k, v)
+
+
+class PairedFastqResult(ContigFilterResult):
+    """What Engine.contigs_filter_fastq returns: ContigFilterResult's fields over the n_built pairs, and what the device made of
+    the two texts -- fidx / ridx, f_bad / r_bad as fastio.index(text, final, max_records) returns them for each file, n_pairs
+    (min of the two record counts), mismatch (fastio.first_header_mismatch over n_pairs pairs, or -1), n_built (the pairs the
+    contigs were built for: mismatch < 0 ? n_pairs : mismatch), f_consumed / r_consumed (what fastio.index(text, final, n_pairs)
+    consumes) and calls (how often the entry was asked: 1 + the capacities that had to be asked for again)."""
+    __slots__ = ("fidx", "ridx", "f_consumed", "r_consumed", "f_bad", "r_bad", "mismatch", "n_pairs", "n_built", "calls")
+
+    def __init__(self, res, *a):
+        for k in ContigResult.__slots__ + ContigFilterResult.__slots__:
+            setattr(self, k, getattr(res, k))
+        for k, v in zip(PairedFastqResult.__slots__, a):
             setattr(self, k, v)
 
 
@@ -618,6 +634,74 @@ class Engine:
         return self.contigs_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq, consensus, qscore_cap,
                                  trim_overlap, rec_cap=rec_cap, alignments=alignments,
                                  filter=(max_len, lower_n_is_base, poisson, params, out))
+
+    def contigs_filter_fastq(self, fbuf, rbuf, ffinal=True, rfinal=True, max_records=None, fastq_offset=33, match=1, mismatch=-1,
+                             gap=-2, insert=20, deltaq=6, consensus=0, qscore_cap=40, trim_overlap=False, max_len=0,
+                             lower_n_is_base=False, poisson=False, idx_cap_rows=None, out_cap_bytes=None, **kw):
+        """contigs_filter_text from the two mates' FASTQ text ALONE (mpb_contigs_filter_fastq_host): both record indexes, the header
+        comparison, the pair descriptors and the class lists are made on the device -> PairedFastqResult.  .fidx, .ridx, .f_bad,
+        .r_bad, .f_consumed, .r_consumed and .mismatch are the host indexer's, and every other field is contigs_filter_text's on
+        those two indexes cut to .n_built pairs, bit for bit.  NotTaken(why) with .which (0 forward, 1 reverse) when the device
+        hands a text back.  idx_cap_rows / out_cap_bytes: the first guess of the two capacities (None: from the texts' sizes);
+        where a guess is too small the entry says what is needed and is asked again."""
+        params = kw.pop("params", None) or self.params(**kw)
+        fkeep, faddr, fbytes = _text_ptr(fbuf)
+        rkeep, raddr, rbytes = _text_ptr(rbuf)
+        limit = (1 << 62) if max_records is None else int(max_records)
+        if limit < 0:
+            raise ValueError("max_records must not be negative")
+        cap = int(idx_cap_rows) if idx_cap_rows is not None else min(limit, max(fbytes, rbytes) // 64 + 64) + 1
+        out_cap = int(out_cap_bytes) if out_cap_bytes is not None else 2 * (fbytes + rbytes) + 16 * cap
+        prm = L.ContigParams(int(match), int(mismatch), int(gap), int(insert), int(deltaq), int(consensus), int(qscore_cap),
+                             1 if trim_overlap else 0)
+        i64 = lambda v=0: C.c_int64(v)
+        calls = 0
+        while True:
+            calls += 1
+            fidx, ridx = np.empty((cap, 6), np.int64), np.empty((cap, 6), np.int64)
+            cbuf, cidx, aux, done = np.empty(out_cap, np.uint8), np.empty((cap, 6), np.int64), np.empty((3, cap), np.int32), np.zeros(cap, np.uint8)
+            ee, ns, ps, lens, flags = (np.empty(cap, np.float64), np.empty(cap, np.int32), np.empty(cap, np.uint8),
+                                       np.empty(cap, np.int32), np.empty(cap, np.uint8))
+            filtered = np.zeros(cap, np.uint8)
+            n_f, n_r, n_pairs, mis, n_built, f_cons, r_cons, rec_cap = i64(), i64(), i64(), i64(-1), i64(), i64(), i64(), i64()
+            f_kind, r_kind, why, which = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+            n_done, n_back, counts, frc, fbad = i64(), i64(), L.FilterCounts(), C.c_int(0), i64(-1)
+            rc = self.lib.mpb_contigs_filter_fastq_host(
+                self.ctx, faddr, fbytes, 1 if ffinal else 0, raddr, rbytes, 1 if rfinal else 0, limit, int(fastq_offset), C.byref(prm),
+                fidx.ctypes.data, ridx.ctypes.data, cap, C.byref(n_f), C.byref(f_kind), C.byref(n_r), C.byref(r_kind), C.byref(n_pairs),
+                C.byref(mis), C.byref(n_built), C.byref(f_cons), C.byref(r_cons), C.byref(why), C.byref(which), C.byref(rec_cap),
+                cbuf.ctypes.data, out_cap, cidx.ctypes.data, aux[0].ctypes.data, aux[1].ctypes.data, aux[2].ctypes.data, done.ctypes.data,
+                C.byref(n_done), C.byref(n_back), int(max_len), 1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0,
+                ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data, flags.ctypes.data, filtered.ctypes.data,
+                C.byref(counts), C.byref(frc), C.byref(fbad))
+            need = max(n_f.value, n_r.value) + 1
+            if rc == L.E_INVALID and need > cap and cap < limit + 1:
+                if out_cap_bytes is None:
+                    out_cap += 16 * (need - cap)
+                cap = need                                   # a text holds more records than the guess: their number is known now
+                continue
+            if rc == L.E_INVALID and rec_cap.value > 8 and n_pairs.value * rec_cap.value > out_cap:
+                out_cap = n_pairs.value * rec_cap.value      # (n_built <= n_pairs: enough whatever the headers say)
+                continue
+            break
+        del fkeep, rkeep
+        L.check(rc)
+        if why.value:
+            raise NotTaken(why.value, which.value)
+        n = n_built.value
+        res = ContigResult(cbuf[:n * rec_cap.value], cidx[:n], np.ascontiguousarray(aux[:, :n].T), done[:n].view(bool), rec_cap.value,
+                           n_done.value, n_back.value, None, None, None)
+        err = None
+        if frc.value:
+            try:
+                _check_text(frc.value, fbad)
+            except ValueError as e:
+                err = e
+        res = ContigFilterResult(res, ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), filtered[:n].view(bool),
+                                 counts.n_pass, counts.n_overflow, err)
+        return PairedFastqResult(res, fidx[:n_f.value], ridx[:n_r.value], f_cons.value, r_cons.value,
+                                 _record_error(fbuf, fidx, n_f.value, f_kind.value), _record_error(rbuf, ridx, n_r.value, r_kind.value),
+                                 mis.value, n_pairs.value, n, calls)
 
     def decode_ascii_device(self, d_seq, d_qual, n, stride, d_out, d_len=None, fixed_len=0, fastq_offset=33,
                             d_err=None):
