@@ -1150,15 +1150,58 @@ def _device_contigs_eligible(args, backend):
     return bool(args.paired and getattr(backend, "text", None) is not None and hasattr(getattr(backend, "engine", None), "contigs_text"))
 
 
-def _chunk_contigs(args, fbuf, fidx, rbuf, ridx, offset, engine=None):
+class _Contigs:
+    """How a run builds contigs: the alignment options (moira_amd.contig.Alignment, made of `args` once) and --processors."""
+
+    def __init__(self, args):
+        from . import contig as CT
+        self.aln = CT.Alignment(args.match, args.mismatch, args.gap, args.insert, args.deltaq, args.consensus_qscore, args.qscore_cap,
+                                args.trim_overlap)
+        self.threads = args.processors
+
+    def call(self, fn, *a, **kw):
+        """A moira_amd.contig entry with the run's options behind `a`; a quality the byte-level contig path cannot carry is
+        the run's to take (it starts over with the line parser)."""
+        from . import contig as CT
+        from . import fastio as F
+        try:
+            return fn(*a, *self.aln, threads=self.threads, **kw)
+        except CT.QualityRange as e:
+            raise F.Unsupported(str(e))
+
+
+class _TextFilter:
+    """The text filter of a run: the backend and what every text call of the run passes it -- alpha, ambigs, round, the input's
+    FASTQ offset, the truncation length, whether a lower-case n is a base, the method and the fast-discard bounds.  Built once
+    (_run_fast_fastq) for --device_pack's text call, the fused contig calls and both indexers."""
+
+    def __init__(self, backend, args, in_off, T, n_is_base, method, fd):
+        self.backend, self.run, self.how = backend, (args.alpha, args.ambigs, args.round), (method, fd)
+        self.in_off, self.T, self.n_is_base = in_off, T, n_is_base
+
+    def text(self, buf, idx, sel=None):
+        """backend.text of the records sel (None: all) -> (ee, has_n)."""
+        method, fd = self.how
+        return self.backend.text(buf, idx, *self.run, self.in_off, self.T, self.n_is_base, method=method, fast_discard=fd, sel=sel)
+
+    def choice(self):
+        """The filter arguments an engine's text call makes of the run's options."""
+        return self.backend.text_choice(*self.run, *self.how)
+
+    def engine_kw(self):
+        """The keywords of Engine.filter_fastq / filter_bgzf_fastq for this run."""
+        return dict(fastq_offset=self.in_off, max_len=self.T, lower_n_is_base=self.n_is_base, **self.choice())
+
+    def fused_kw(self):
+        """The keywords of the fused contig calls (moira_amd.contig.contigs_from_fastq_filtered and its text-alone form): the
+        pairs the device does not finish are filtered through text()."""
+        return dict(engine=self.backend.engine, backend_text=self.text, max_len=self.T, lower_n_is_base=self.n_is_base, **self.choice())
+
+
+def _chunk_contigs(contigs, fbuf, fidx, rbuf, ridx, offset, engine=None):
     """The contigs of one chunk of pairs -> (cbuf, cidx, aux); engine: on its device, the handed-back pairs on the host."""
     from . import contig as CT
-    from . import fastio as F
-    try:
-        return CT.contigs_from_fastq(fbuf, fidx, rbuf, ridx, offset, args.match, args.mismatch, args.gap, args.insert, args.deltaq,
-                                     args.consensus_qscore, args.qscore_cap, args.trim_overlap, threads=args.processors, engine=engine)
-    except CT.QualityRange as e:
-        raise F.Unsupported(str(e))
+    return contigs.call(CT.contigs_from_fastq, fbuf, fidx, rbuf, ridx, offset, engine=engine)
 
 
 def _fused_applies(device_contigs, device_pack, only, backend):
@@ -1168,23 +1211,12 @@ def _fused_applies(device_contigs, device_pack, only, backend):
                 and hasattr(getattr(backend, "engine", None), "contigs_filter_text"))
 
 
-def _chunk_contigs_filtered(args, fbuf, fidx, rbuf, ridx, offset, backend, filt):
+def _chunk_contigs_filtered(contigs, fbuf, fidx, rbuf, ridx, filt):
     """The contigs of one chunk of pairs and their filter in one device call (moira_amd.contig.contigs_from_fastq_filtered) ->
-    (cbuf, cidx, aux, ee, has_n, filter_error); filt = (method, fast_discard, max_len, lower_n_is_base).  The pairs the device
-    does not finish are built on the host and filtered through backend.text, so results and errors are the two-call path's."""
+    (cbuf, cidx, aux, ee, has_n, filter_error); filt: the run's _TextFilter.  The pairs the device does not finish are built on
+    the host and filtered through filt.text, so results and errors are the two-call path's."""
     from . import contig as CT
-    from . import fastio as F
-    method, fd, T, n_is_base = filt
-    choice = backend.text_choice(args.alpha, args.ambigs, args.round, method, fd)
-    rest = lambda buf, idx, sel: backend.text(buf, idx, args.alpha, args.ambigs, args.round, offset, T, n_is_base, method=method,
-                                              fast_discard=fd, sel=sel)
-    try:
-        return CT.contigs_from_fastq_filtered(fbuf, fidx, rbuf, ridx, offset, args.match, args.mismatch, args.gap, args.insert,
-                                              args.deltaq, args.consensus_qscore, args.qscore_cap, args.trim_overlap,
-                                              threads=args.processors, engine=backend.engine, backend_text=rest, max_len=T,
-                                              lower_n_is_base=n_is_base, **choice)
-    except CT.QualityRange as e:
-        raise F.Unsupported(str(e))
+    return contigs.call(CT.contigs_from_fastq_filtered, fbuf, fidx, rbuf, ridx, filt.in_off, **filt.fused_kw())
 
 
 def _filtered_where_built(built):
@@ -1199,15 +1231,15 @@ def _filtered_where_built(built):
 class _DeferredContigs:
     """A chunk of pairs whose contigs are still to be built, by whoever takes it off the queue.  With --device_contigs the
     producer thread only reads and indexes: calls on one context must not overlap (include/moira_pb.h), and the consumer
-    thread is the one that filters on that context, so it makes the device contig call too.  fused = (backend, filt): the
-    contigs are filtered in the same call (_chunk_contigs_filtered)."""
+    thread is the one that filters on that context, so it makes the device contig call too.  a = _chunk_contigs' arguments;
+    fused (the run's _TextFilter): the contigs are filtered in the same call (_chunk_contigs_filtered)."""
 
     def __init__(self, *a, fused=None):
         self.a, self.fused = a, fused
 
     def build(self):
         if self.fused is not None:
-            return _chunk_contigs_filtered(*self.a[:6], *self.fused)
+            return _chunk_contigs_filtered(*self.a[:5], self.fused)
         return _chunk_contigs(*self.a)
 
 
@@ -1225,12 +1257,9 @@ class _DeferredBlock:
 
 def _read_blocks(fh, block_bytes):
     """The stream as _DeferredBlocks; the last one is empty and says that the text has ended."""
-    while True:
-        data = fh.read(block_bytes)
-        if not data:
-            break
-        yield _DeferredBlock(data, False)
-    yield _DeferredBlock(b"", True)
+    from . import fastio as F
+    for data, eof in F.read_blocks(fh, block_bytes):
+        yield _DeferredBlock(data, eof)
 
 
 class _DeferredMembers:
@@ -1309,27 +1338,21 @@ class _DeviceIndexer:
     def _chunks(self, data, eof, first=None, on_host=False):
         """first: what the fused call made of `data` (its first chunk); on_host: the device refused `data` already."""
         from . import fastio as F
-        while data:
-            filtered, r = None, first
+        ready = [first, on_host]                            # (both speak of the first chunk only)
+
+        def index_fn(data, eof, max_records):
+            (r, on_host), ready[:] = ready, (None, False)
             if r is None and not on_host:
                 try:
-                    r = self.engine.filter_fastq(data, final=eof, max_records=self.max_records, **self.kw)
+                    r = self.engine.filter_fastq(data, final=eof, max_records=max_records, **self.kw)
                 except (self.not_taken, ValueError) as e:
                     self.refused(e)
             if r is not None:
-                idx, consumed, err, filtered = r.idx, r.consumed, r.bad, (r.ee, r.has_n)
-            else:
-                idx, consumed, err = F.index(data, eof, self.max_records, self.threads)
-            first, on_host = None, False
-            if len(idx):
-                yield data, idx, None, filtered
-            if err is not None:
-                raise err
-            data = data[consumed:]
-            if len(idx) < self.max_records:
-                break                                   # the rest is an incomplete record: it waits for the next block
+                return r.idx, r.consumed, r.bad, (None, (r.ee, r.has_n))
+            return F.index(data, eof, max_records, self.threads) + ((None, None),)
+        rest = yield from F.chunks_of(data, eof, self.max_records, index_fn)
         if not eof:
-            self.carry = data
+            self.carry = rest                               # an incomplete record: it waits for the next block
 
 
 PAIR_INDEX_BLOCK = 1 << 24        # --device_pair_index: bytes of text per read of either file (fastio.PairedFastqChunks' block)
@@ -1353,15 +1376,14 @@ class _DeferredPairStreams:
 
 
 class _DevicePairIndexer:
-    """The consumer's side of --device_pair_index: it owns both files' tails and is fastio.PairedFastqChunks.__iter__'s loop with ONE
-    device call in place of the two index calls -- device(fbuf, rbuf, ffinal, rfinal, max_records) -> (res, cbuf, cidx, aux, ee,
-    has_n, filter_error) (moira_amd.contig.contigs_from_fastq_text_filtered) -- which also builds and filters the contigs.  It
-    yields what a fused chunk yields, (cbuf, cidx, aux, ee, has_n, filter_error), and keeps that loop's rules: want / has_next / eof,
-    the pairs first and then the error of the pair reached, forward file first, forward_header set on a reverse-file error, the
-    record error of pair n only when both files hold record n, zip() stopping with the shorter file.  A header mismatch yields the
-    pairs before it and then raises NameMismatchError, as _fast_chunks does.  A pair of blocks the device hands back (not_taken),
-    or whose call ends in a ValueError, goes through fastio.index x 2 and host(fbuf, fidx, rbuf, ridx), today's fused call; the
-    first such pair is reported.  A fastio.Unsupported of the host indexer is the run's to take."""
+    """The consumer's side of --device_pair_index: fastio.paired_lockstep -- the loop of fastio.PairedFastqChunks, which owns both
+    files' tails and the rules that pin the run to the reference's zip() parser -- with ONE device call as its pass in place of
+    the two index calls: device(fbuf, rbuf, ffinal, rfinal, max_records) -> (res, cbuf, cidx, aux, ee, has_n, filter_error)
+    (moira_amd.contig.contigs_from_fastq_text_filtered), which also builds and filters the contigs.  It yields what a fused chunk
+    yields, (cbuf, cidx, aux, ee, has_n, filter_error).  A header mismatch yields the pairs before it and then raises
+    NameMismatchError, as _fast_chunks does, before the loop's own error.  A pair of blocks the device hands back (not_taken), or
+    whose call ends in a ValueError, goes through fastio.paired_host_pass and host(fbuf, fidx, rbuf, ridx), today's fused call;
+    the first such pair is reported.  A fastio.Unsupported of the host indexer is the run's to take."""
 
     def __init__(self, device, host, max_records, refused, threads=1, not_taken=None):
         if not_taken is None:
@@ -1369,57 +1391,26 @@ class _DevicePairIndexer:
         self.device, self.host, self.max_records, self.refused, self.threads, self.not_taken = device, host, max_records, refused, threads, not_taken
 
     def _one(self, tail, eof):
-        """One pass over the two tails -> (fidx, ridx, (f_bad, r_bad), n, (f_consumed, r_consumed), mismatch, built or None)."""
+        """One pass over the two tails, as fastio.paired_lockstep asks for it; its payload is (mismatch, built or None)."""
         from . import fastio as F
         try:
             res, *built = self.device(tail[0], tail[1], eof[0], eof[1], self.max_records)
-            return res.fidx, res.ridx, (res.f_bad, res.r_bad), res.n_pairs, (res.f_consumed, res.r_consumed), res.mismatch, \
-                (tuple(built) if res.n_built else None)
+            return (res.fidx, res.ridx), (res.f_bad, res.r_bad), res.n_pairs, (res.f_consumed, res.r_consumed), \
+                (res.mismatch, tuple(built) if res.n_built else None)
         except (self.not_taken, ValueError) as e:
             self.refused(e)
-        got = [F.index(tail[k], eof[k], self.max_records, self.threads) for k in (0, 1)]
-        n = min(len(got[0][0]), len(got[1][0]))
-        consumed = [got[k][1] if len(got[k][0]) == n else F.index(tail[k], eof[k], n, self.threads)[1] for k in (0, 1)] if n else [0, 0]
-        bad = F.first_header_mismatch(tail[0], got[0][0][:n], tail[1], got[1][0][:n]) if n else -1
-        nb = n if bad < 0 else bad
-        built = self.host(tail[0], got[0][0][:nb], tail[1], got[1][0][:nb]) if nb else None
-        return got[0][0], got[1][0], (got[0][2], got[1][2]), n, consumed, bad, built
+        idx, bad, n, consumed, mismatch = F.paired_host_pass(tail, eof, self.max_records, self.threads)
+        nb = n if mismatch < 0 else mismatch
+        return idx, bad, n, consumed, (mismatch, self.host(tail[0], idx[0][:nb], tail[1], idx[1][:nb]) if nb else None)
 
     def run(self, streams):
         from . import fastio as F
-        tail, eof, want = [b"", b""], [False, False], [True, True]
-        while True:
-            for k in (0, 1):
-                if want[k] and not eof[k]:
-                    blk = next(streams.blocks[k])
-                    if blk.data:
-                        tail[k] = tail[k] + blk.data if tail[k] else blk.data
-                    eof[k] = blk.eof
-            idx = [None, None]
-            idx[0], idx[1], bad, n, consumed, mismatch, built = self._one(tail, eof)
-            # does file k hold a complete record number n (sound or not)?
-            has_next = [len(idx[k]) > n or bad[k] is not None for k in (0, 1)]
-            err = None
-            if has_next[0] and has_next[1]:
-                for k in (0, 1):
-                    if err is None and bad[k] is not None and len(idx[k]) == n:
-                        err = F.PairedRecordError(k, bad[k])
-                if err is not None and err.which == 1:       # then forward record n is sound: the reference names it
-                    err.err.forward_header = F.header_of(tail[0], idx[0][n])
-            if n:
-                if built is not None:
-                    yield built
-                if mismatch >= 0:
-                    raise NameMismatchError(F.header_of(tail[0], idx[0][mismatch]), None, F.header_of(tail[1], idx[1][mismatch]), None)
-                tail = [tail[k][consumed[k]:] for k in (0, 1)]
-            if err is not None:
-                raise err
-            if n == self.max_records:
-                want = [len(tail[k]) < streams.block for k in (0, 1)]
-                continue
-            if any(not has_next[k] and eof[k] for k in (0, 1)):
-                return                                       # one file is exhausted: zip() stops here
-            want = [not has_next[k] for k in (0, 1)]
+        blocks = [((b.data, b.eof) for b in it) for it in streams.blocks]
+        for fbuf, fidx, rbuf, ridx, n, (mismatch, built) in F.paired_lockstep(blocks, streams.block, self.max_records, self._one):
+            if built is not None:
+                yield built
+            if mismatch >= 0:
+                raise NameMismatchError(F.header_of(fbuf, fidx[mismatch]), None, F.header_of(rbuf, ridx[mismatch]), None)
 
 
 def _members_reader(filename, threads, inflater):
@@ -1433,13 +1424,13 @@ def _members_reader(filename, threads, inflater):
     return F.GzipReader(io.open(filename, "rb", buffering=0), threads=threads, inflater=inflater)
 
 
-def _fast_chunks(args, paths, contig_engine=None, fused=None):
+def _fast_chunks(args, paths, contigs, contig_engine=None, fused=None):
     """(buf, idx, aux) per chunk: reads as they are in the file, or contigs built from the two files.  With contig_engine
     (--device_contigs) a paired chunk comes as a _DeferredContigs instead: its consumer builds the contigs, on its own thread
     (fused: and filters them in the same call, FASTQ input only)."""
     from . import fastio as F
     if not args.forward_fastq:
-        yield from _fast_chunks_fasta_qual(args, paths, contig_engine)
+        yield from _fast_chunks_fasta_qual(args, paths, contigs, contig_engine)
         return
     if not args.paired:
         # --device_inflate, --device_index and --device_pack together: BGZF members go to the consumer as they are (one fused call)
@@ -1474,9 +1465,9 @@ def _fast_chunks(args, paths, contig_engine=None, fused=None):
             bad = F.first_header_mismatch(fbuf, fidx, rbuf, ridx)
             n = len(fidx) if bad < 0 else bad
             if n and contig_engine is not None:
-                yield _DeferredContigs(args, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset, contig_engine, fused=fused)
+                yield _DeferredContigs(contigs, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset, contig_engine, fused=fused)
             elif n:
-                yield _chunk_contigs(args, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset)
+                yield _chunk_contigs(contigs, fbuf, fidx[:n], rbuf, ridx[:n], args.fastq_offset)
             if bad >= 0:
                 raise NameMismatchError(F.header_of(fbuf, fidx[bad]), None, F.header_of(rbuf, ridx[bad]), None)
     except F.PairedRecordError as e:
@@ -1571,7 +1562,7 @@ class _InOrder:
             raise self.err
 
 
-def _fast_chunks_fasta_qual(args, paths, contig_engine=None):
+def _fast_chunks_fasta_qual(args, paths, contigs, contig_engine=None):
     """fasta + qual input: records rebuilt as header | sequence | quality bytes (offset 0) by
     mio_fasta_qual_index, so that the rest of the path is the FASTQ one."""
     from . import fastio as F
@@ -1593,9 +1584,9 @@ def _fast_chunks_fasta_qual(args, paths, contig_engine=None):
             if a is None or b is None or len(a[1]) != len(b[1]) or F.first_header_mismatch(a[0], a[1], b[0], b[1]) >= 0:
                 raise F.Unsupported("forward and reverse records do not pair up")
             if contig_engine is not None:
-                yield _DeferredContigs(args, a[0], a[1], b[0], b[1], 0, contig_engine)
+                yield _DeferredContigs(contigs, a[0], a[1], b[0], b[1], 0, contig_engine)
             else:
-                yield _chunk_contigs(args, a[0], a[1], b[0], b[1], 0)
+                yield _chunk_contigs(contigs, a[0], a[1], b[0], b[1], 0)
     finally:
         for f in files:
             f.close()
@@ -1620,6 +1611,7 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
     if getattr(args, "fast_discard", False) and not args.collapse and args.pipeline == "mothur" \
             and method == "poisson_binomial":
         fd = (args.uncert, args.maxerrors)
+    filt, contigs = _TextFilter(backend, args, in_off, T, n_is_base, method, fd), (_Contigs(args) if args.paired else None)
     fq = args.output_format == "fastq"
     usearch = args.pipeline == "USEARCH"
     thr_label = ("errors > %.2f" % args.maxerrors) if args.maxerrors else ("uncert > %.3f" % args.uncert)
@@ -1677,8 +1669,7 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
             # text the entry does not take) sends the chunk through the host path below, which raises what it always raised
             # -- or takes the chunk; the first such chunk of a run is reported, so that the switch never fails silently.
             try:
-                return backend.text(buf, idx, args.alpha, args.ambigs, args.round, in_off, T, n_is_base, method=method,
-                                    fast_discard=fd)
+                return filt.text(buf, idx)
             except ValueError as e:
                 paths.pack_refused(e)
         strides = bucket_of(lens, 64)
@@ -1690,37 +1681,26 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
         return ee, has_n
     ok = False
     try:
-        fused = (backend, (method, fd, T, n_is_base)) if _fused_applies(paths.contigs, paths.pack, only, backend) else None
+        fused = filt if _fused_applies(paths.contigs, paths.pack, only, backend) else None
         indexer = None
         if paths.index:
-            indexer = _DeviceIndexer(backend.engine, dict(fastq_offset=in_off, max_len=T, lower_n_is_base=n_is_base,
-                                                          **backend.text_choice(args.alpha, args.ambigs, args.round, method, fd)),
-                                     CHUNK_READS, paths.index_refused, threads, members_refused=paths.members_refused)
+            indexer = _DeviceIndexer(backend.engine, filt.engine_kw(), CHUNK_READS, paths.index_refused, threads,
+                                     members_refused=paths.members_refused)
             paths.members = paths.inflater is not None and hasattr(backend.engine, "filter_bgzf_fastq")
 
         pair_indexer = None
         if paths.pair_index:
             from . import contig as CT
-            choice = backend.text_choice(args.alpha, args.ambigs, args.round, method, fd)
-            rest = lambda buf, idx, sel: backend.text(buf, idx, args.alpha, args.ambigs, args.round, in_off, T, n_is_base, method=method,
-                                                      fast_discard=fd, sel=sel)
-
-            def device_pairs(fbuf, rbuf, ffinal, rfinal, max_records):
-                try:
-                    return CT.contigs_from_fastq_text_filtered(
-                        fbuf, rbuf, ffinal, rfinal, max_records, in_off, args.match, args.mismatch, args.gap, args.insert, args.deltaq,
-                        args.consensus_qscore, args.qscore_cap, args.trim_overlap, threads=args.processors, engine=backend.engine,
-                        backend_text=rest, max_len=T, lower_n_is_base=n_is_base, **choice)
-                except CT.QualityRange as e:
-                    raise F.Unsupported(str(e))
-            pair_indexer = _DevicePairIndexer(device_pairs, lambda *a: _chunk_contigs_filtered(args, *a, in_off, *fused), PAIR_CHUNK_READS,
+            fused_kw = filt.fused_kw()
+            pair_indexer = _DevicePairIndexer(lambda *a: contigs.call(CT.contigs_from_fastq_text_filtered, *a, in_off, **fused_kw),
+                                              lambda *a: _chunk_contigs_filtered(contigs, *a, fused), PAIR_CHUNK_READS,
                                               paths.pair_index_refused, threads)
 
         def chunks():
             # (--device_contigs: the contigs are built here, on the thread that makes every other call on the context; with
             # --device_pack as well they are filtered where they lie, in the same call.  --device_index: the same for a block
             # of text, which may hold several chunks, or none)
-            for chunk in _prefetched(_fast_chunks(args, paths, backend.engine if paths.contigs else None, fused)):
+            for chunk in _prefetched(_fast_chunks(args, paths, contigs, backend.engine if paths.contigs else None, fused)):
                 if isinstance(chunk, _DeferredPairStreams):
                     try:
                         for built in pair_indexer.run(chunk):

@@ -9,6 +9,7 @@ plus contigs_batch(): the paired half of process_data for a whole chunk on all h
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -152,31 +153,54 @@ def usable_cpus():
     return n
 
 
-def _contigs_device_then_host(engine, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
-                              consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap):
+class Alignment(NamedTuple):
+    """The alignment and consensus options of a paired run, in the order every chunk entry below takes them."""
+    match: int = 1
+    mismatch: int = -1
+    gap: int = -2
+    insert: int = 20
+    deltaq: int = 6
+    consensus_qscore: str = "best"
+    qscore_cap: int = 40
+    trim_overlap: bool = False
+
+    def coded(self):
+        """The options as mct_contigs_from_fastq and the engine's contig entries take them: consensus_qscore by its number."""
+        if self.consensus_qscore not in CONSENSUS:
+            raise ValueError('consensus_qscore must be "best", "sum" or "posterior".')
+        return self._replace(consensus_qscore=CONSENSUS[self.consensus_qscore], trim_overlap=1 if self.trim_overlap else 0)
+
+
+def _rec_cap(fidx, ridx):
+    """The slot of a contig: header + 2 x (l1 + l2), over the chunk."""
+    return int((fidx[:, 1] + 2 * (fidx[:, 3] + ridx[:, 3])).max()) + 8 if len(fidx) else 8
+
+
+def _host_contigs(L, n, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap):
+    """mct_contigs_from_fastq over n pairs (aln: Alignment.coded()) -> (rc, cbuf, cidx, aux int32[3, n])."""
+    cbuf, cidx, aux = np.empty(n * rec_cap, np.uint8), np.empty((n, 6), np.int64), np.empty((3, n), np.int32)
+    ptr = lambda b: b.ctypes.data if isinstance(b, np.ndarray) else b
+    rc = L.mct_contigs_from_fastq(n, ptr(fbuf), fidx.ctypes.data, ptr(rbuf), ridx.ctypes.data, int(fastq_offset), *aln, threads,
+                                  rec_cap, cbuf.ctypes.data, cidx.ctypes.data, aux[0].ctypes.data, aux[1].ctypes.data,
+                                  aux[2].ctypes.data)
+    return rc, cbuf, cidx, aux
+
+
+def _contigs_device_then_host(engine, L, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap):
     """The device builds what it takes; the pairs it hands back (done == 0) go through mct_contigs_from_fastq -- the index
     rows gathered, the same slot size -- and their slots, index rows and aux rows are scattered into place."""
-    res = engine.contigs_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
-                              CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, rec_cap=rec_cap)
-    return _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
-                                    consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap)
+    res = engine.contigs_text(fbuf, fidx, rbuf, ridx, fastq_offset, *aln, rec_cap=rec_cap)
+    return _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap)
 
 
-def _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
-                             consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap):
+def _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap):
     """The second half of _contigs_device_then_host, on the result of either device call."""
     cbuf, cidx, aux = res.cbuf, res.cidx, res.aux
     back = np.nonzero(~res.done)[0]
     if len(back):
         m = len(back)
-        sf, sr = np.ascontiguousarray(fidx[back]), np.ascontiguousarray(ridx[back])
-        hbuf, hidx = np.empty(m * rec_cap, np.uint8), np.empty((m, 6), np.int64)
-        haux = np.empty((3, m), np.int32)
-        ptr = lambda b: b.ctypes.data if isinstance(b, np.ndarray) else b
-        rc = L.mct_contigs_from_fastq(m, ptr(fbuf), sf.ctypes.data, ptr(rbuf), sr.ctypes.data, int(fastq_offset), match, mismatch,
-                                      gap, insert, deltaq, CONSENSUS[consensus_qscore], qscore_cap, 1 if trim_overlap else 0,
-                                      min(threads, m), rec_cap, hbuf.ctypes.data, hidx.ctypes.data, haux[0].ctypes.data,
-                                      haux[1].ctypes.data, haux[2].ctypes.data)
+        rc, hbuf, hidx, haux = _host_contigs(L, m, fbuf, np.ascontiguousarray(fidx[back]), rbuf, np.ascontiguousarray(ridx[back]),
+                                             fastq_offset, aln, min(threads, m), rec_cap)
         if rc:
             # the message names the pair by its position in the host call: put the chunk's position back
             import re
@@ -202,27 +226,27 @@ def contigs_from_fastq(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatc
     engine (a moira_amd.engine.Engine; opt-in): the device builds the pairs it takes (Engine.contigs_text) and this
     function's host path builds the ones it hands back, so results and errors are the host's either way."""
     L = load()
-    if consensus_qscore not in CONSENSUS:
-        raise ValueError('consensus_qscore must be "best", "sum" or "posterior".')
+    aln = Alignment(match, mismatch, gap, insert, deltaq, consensus_qscore, qscore_cap, trim_overlap).coded()
     fidx, ridx = np.ascontiguousarray(fidx), np.ascontiguousarray(ridx)
     n = len(fidx)
     threads = threads or usable_cpus()
-    rec_cap = int((fidx[:, 1] + 2 * (fidx[:, 3] + ridx[:, 3])).max()) + 8 if n else 8     # header + 2 x (l1 + l2)
+    rec_cap = _rec_cap(fidx, ridx)
     if engine is not None and n:
-        return _contigs_device_then_host(engine, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
-                                         consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap)
-    cbuf = np.empty(n * rec_cap, np.uint8)
-    cidx = np.empty((n, 6), np.int64)
-    aux = np.empty((3, n), np.int32)
-    ptr = lambda b: b.ctypes.data if isinstance(b, np.ndarray) else b
-    rc = L.mct_contigs_from_fastq(n, ptr(fbuf), fidx.ctypes.data, ptr(rbuf), ridx.ctypes.data, int(fastq_offset),
-                                  match, mismatch, gap, insert, deltaq, CONSENSUS[consensus_qscore], qscore_cap,
-                                  1 if trim_overlap else 0, threads, rec_cap, cbuf.ctypes.data, cidx.ctypes.data,
-                                  aux[0].ctypes.data, aux[1].ctypes.data, aux[2].ctypes.data)
+        return _contigs_device_then_host(engine, L, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap)
+    rc, cbuf, cidx, aux = _host_contigs(L, n, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap)
     if rc == -7:
         raise QualityRange(L.mct_last_error().decode())
     _check(rc)
     return cbuf, cidx, np.ascontiguousarray(aux.T)
+
+
+def _engine_text_filter(engine, fastq_offset, max_len, lower_n_is_base, poisson, kw):
+    """The default backend_text of the fused calls: Engine.filter_text with the call's own filter arguments."""
+    def backend_text(buf, idx, sel):
+        r = engine.filter_text(buf, idx, sel=sel, fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base,
+                               poisson=poisson, **kw)
+        return r.ee, r.has_n
+    return backend_text
 
 
 def contigs_from_fastq_filtered(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatch=-1, gap=-2, insert=20, deltaq=6,
@@ -237,32 +261,21 @@ def contigs_from_fastq_filtered(fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1
     has_n to the caller instead: filter_error is what filter_text would have raised (else None), and nothing more is asked of
     the device for the chunk; a ValueError of backend_text on the rest is returned the same way."""
     L = load()
-    if consensus_qscore not in CONSENSUS:
-        raise ValueError('consensus_qscore must be "best", "sum" or "posterior".')
+    aln = Alignment(match, mismatch, gap, insert, deltaq, consensus_qscore, qscore_cap, trim_overlap).coded()
     if engine is None:
         raise ValueError("contigs_from_fastq_filtered needs an engine: the fused call has no host form")
     fidx, ridx = np.ascontiguousarray(fidx), np.ascontiguousarray(ridx)
-    n = len(fidx)
-    threads = threads or usable_cpus()
-    rec_cap = int((fidx[:, 1] + 2 * (fidx[:, 3] + ridx[:, 3])).max()) + 8 if n else 8     # header + 2 x (l1 + l2)
-    if backend_text is None:
-        def backend_text(buf, idx, sel):
-            r = engine.filter_text(buf, idx, sel=sel, fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base,
-                                   poisson=poisson, **kw)
-            return r.ee, r.has_n
-    res = engine.contigs_filter_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
-                                     CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, rec_cap=rec_cap, max_len=max_len,
+    rec_cap = _rec_cap(fidx, ridx)
+    res = engine.contigs_filter_text(fbuf, fidx, rbuf, ridx, fastq_offset, *aln, rec_cap=rec_cap, max_len=max_len,
                                      lower_n_is_base=lower_n_is_base, poisson=poisson, **kw)
-    return _merge_filtered(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq, consensus_qscore,
-                           qscore_cap, trim_overlap, threads, rec_cap, backend_text)
+    return _merge_filtered(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads or usable_cpus(), rec_cap,
+                           backend_text or _engine_text_filter(engine, fastq_offset, max_len, lower_n_is_base, poisson, kw))
 
 
-def _merge_filtered(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq, consensus_qscore, qscore_cap,
-                    trim_overlap, threads, rec_cap, backend_text):
+def _merge_filtered(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap, backend_text):
     """What follows either fused device call: the host builds the pairs that were handed back, and backend_text filters every
     pair the call did not filter -> (cbuf, cidx, aux, ee, has_n, filter_error)."""
-    cbuf, cidx, aux = _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq,
-                                               consensus_qscore, qscore_cap, trim_overlap, threads, rec_cap)
+    cbuf, cidx, aux = _host_builds_handed_back(res, L, fbuf, fidx, rbuf, ridx, fastq_offset, aln, threads, rec_cap)
     ee, has_n = np.array(res.ee, np.float64), np.array(res.has_n, bool)
     if res.filter_error is not None:
         return cbuf, cidx, aux, ee, has_n, res.filter_error
@@ -285,20 +298,12 @@ def contigs_from_fastq_text_filtered(fbuf, rbuf, ffinal=True, rfinal=True, max_r
     contigs_from_fastq_filtered's over the n_built pairs, merged the same way from the index rows the device returned.
     engine.NotTaken and ValueError are the call's: the caller indexes on the host and goes through contigs_from_fastq_filtered."""
     L = load()
-    if consensus_qscore not in CONSENSUS:
-        raise ValueError('consensus_qscore must be "best", "sum" or "posterior".')
+    aln = Alignment(match, mismatch, gap, insert, deltaq, consensus_qscore, qscore_cap, trim_overlap).coded()
     if engine is None:
         raise ValueError("contigs_from_fastq_text_filtered needs an engine: the fused call has no host form")
-    threads = threads or usable_cpus()
-    if backend_text is None:
-        def backend_text(buf, idx, sel):
-            r = engine.filter_text(buf, idx, sel=sel, fastq_offset=fastq_offset, max_len=max_len, lower_n_is_base=lower_n_is_base,
-                                   poisson=poisson, **kw)
-            return r.ee, r.has_n
-    res = engine.contigs_filter_fastq(fbuf, rbuf, ffinal, rfinal, max_records, fastq_offset, match, mismatch, gap, insert, deltaq,
-                                      CONSENSUS[consensus_qscore], qscore_cap, trim_overlap, max_len=max_len,
+    res = engine.contigs_filter_fastq(fbuf, rbuf, ffinal, rfinal, max_records, fastq_offset, *aln, max_len=max_len,
                                       lower_n_is_base=lower_n_is_base, poisson=poisson, **kw)
     n = res.n_built
     return (res,) + _merge_filtered(res, L, fbuf, np.ascontiguousarray(res.fidx[:n]), rbuf, np.ascontiguousarray(res.ridx[:n]),
-                                    fastq_offset, match, mismatch, gap, insert, deltaq, consensus_qscore, qscore_cap, trim_overlap,
-                                    threads, res.rec_cap, backend_text)
+                                    fastq_offset, aln, threads or usable_cpus(), res.rec_cap,
+                                    backend_text or _engine_text_filter(engine, fastq_offset, max_len, lower_n_is_base, poisson, kw))

@@ -148,6 +148,71 @@ def _record_error(buf, idx, n, kind):
     return err
 
 
+def _filter_error(frc, fbad):
+    """What a fused call's filter refused, as the ValueError filter_text would have raised (.bad_record), or None."""
+    try:
+        _check_text(frc.value, fbad)
+    except ValueError as e:
+        return e
+
+
+def _record_limit(max_records):
+    """max_records as the text-alone entries take it (None: no limit)."""
+    limit = (1 << 62) if max_records is None else int(max_records)
+    if limit < 0:
+        raise ValueError("max_records must not be negative")
+    return limit
+
+
+def _contig_params(match, mismatch, gap, insert, deltaq, consensus, qscore_cap, trim_overlap):
+    return L.ContigParams(int(match), int(mismatch), int(gap), int(insert), int(deltaq), int(consensus), int(qscore_cap),
+                          1 if trim_overlap else 0)
+
+
+class _TextResults:
+    """The five per-record result arrays of a text entry -- ee, ns, pass, lens, flags -- for `n` records: fresh, or the
+    caller's own (`out`)."""
+    DTYPES = (np.float64, np.int32, np.uint8, np.int32, np.uint8)
+
+    def __init__(self, n, out=None):
+        if out is None:
+            out = tuple(np.empty(n, t) for t in self.DTYPES)
+        ee, ns, ps, lens, flags = out
+        if (ee.dtype, ns.dtype, ps.dtype, lens.dtype, flags.dtype) != self.DTYPES or \
+                not all(a.flags.c_contiguous and len(a) >= n for a in out):
+            raise ValueError("out must be contiguous (float64, int32, uint8, int32, uint8) arrays of at least n entries")
+        self.arrays = ee, ns, ps, lens, flags
+
+    def ptrs(self):
+        return tuple(a.ctypes.data for a in self.arrays)
+
+    def cut(self, n):
+        """-> (ee, ns, passed, lens, has_n) of the first n records (pass and flag bytes are 0 / 1)."""
+        ee, ns, ps, lens, flags = (a[:n] for a in self.arrays)
+        return ee, ns, ps.view(bool), lens, flags.view(bool)
+
+
+def _ask_again(call, cap, limit, out_cap=None, grow_out=False):
+    """The capacity loop of the text-alone entries.  call(cap, out_cap) makes one call of the entry with room for `cap` index
+    rows (and `out_cap` bytes of output, where the entry has such a capacity) and returns (rc, the rows it needs, the bytes it
+    needs or None).  An entry that ended in MPB_E_INVALID because it counted more rows than the guess is asked once more with
+    their number -- never above limit + 1 rows -- and with 16 bytes more of output per row where grow_out says the byte
+    capacity was a guess as well; one that needs more bytes is asked again with them.  -> (the last rc, the calls made)."""
+    calls = 0
+    while True:
+        calls += 1
+        rc, rows, nbytes = call(cap, out_cap)
+        if rc == L.E_INVALID and rows > cap and cap < limit + 1:
+            if grow_out:
+                out_cap += 16 * (rows - cap)
+            cap = rows                                       # the text holds more records than the guess: their number is known now
+            continue
+        if rc == L.E_INVALID and nbytes is not None and nbytes > out_cap:
+            out_cap = nbytes
+            continue
+        return rc, calls
+
+
 def text_rows(idx, sel=None, text_bytes=0, max_len=0, stride=0):
     """The validated row descriptors (mpb_text_rows; host only) of the records sel (None: all) of the record index idx over a
     text of text_bytes bytes -> (rows, longest): rows a TEXT_ROW_DTYPE array (None when stride == 0: validation and the
@@ -397,43 +462,36 @@ class Engine:
         params = kw.pop("params", None) or self.params(**kw)
         idx, sel, n = _index_args(idx, sel)
         keep, addr, nbytes = _text_ptr(buf)
-        if out is None:
-            out = np.empty(n, np.float64), np.empty(n, np.int32), np.empty(n, np.uint8), np.empty(n, np.int32), np.empty(n, np.uint8)
-        ee, ns, ps, lens, flags = out
-        if (ee.dtype, ns.dtype, ps.dtype, lens.dtype, flags.dtype) != (np.float64, np.int32, np.uint8, np.int32, np.uint8) or \
-                not all(a.flags.c_contiguous and len(a) >= n for a in out):
-            raise ValueError("out must be contiguous (float64, int32, uint8, int32, uint8) arrays of at least n entries")
+        r = _TextResults(n, out)
         counts, bad = L.FilterCounts(), C.c_int64(-1)
         rc = self.lib.mpb_filter_text_host(self.ctx, addr, nbytes, idx.ctypes.data, len(idx),
                                            sel.ctypes.data if sel is not None else None, n, int(fastq_offset), int(max_len),
-                                           1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0,
-                                           ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data, flags.ctypes.data,
+                                           1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0, *r.ptrs(),
                                            C.byref(counts), C.byref(bad))
         del keep
         _check_text(rc, bad)
-        return TextFilterResult(ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), counts.n_pass, counts.n_overflow)
+        return TextFilterResult(*r.cut(n), counts.n_pass, counts.n_overflow)
 
     # ---- the FASTQ record index on the device (k_fq_lines / _scan / _starts / _rows) --------------
     def _fastq_call(self, buf, final, max_records, max_len, call):
-        """One call of either text-alone entry: call(addr, nbytes, final, max_records, max_len, idx, cap, n, consumed, bad, why)
-        -> rc.  max_records None: no limit; the index is sized by a guess of the records (64 bytes each) and, where the text
-        holds more, once more by what the entry counted.  -> (idx rows, n, consumed, bad kind)."""
+        """Either text-alone entry: call(addr, nbytes, final, max_records, max_len, idx, cap, n, consumed, bad, why) -> rc.
+        max_records None: no limit; the index is sized by a guess of the records (64 bytes each) and, where the text holds
+        more, once more by what the entry counted (_ask_again).  -> (rc, idx rows, n, consumed, bad kind, why)."""
         keep, addr, nbytes = _text_ptr(buf)
-        limit = (1 << 62) if max_records is None else int(max_records)
-        if limit < 0:
-            raise ValueError("max_records must not be negative")
-        cap = min(limit, nbytes // 64 + 64) + 1
-        while True:
+        limit = _record_limit(max_records)
+        last = None
+
+        def one(cap, _):
+            nonlocal last
             idx = np.empty((cap, 6), np.int64)
             n, consumed, bad, why = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
             rc = call(addr, nbytes, 1 if final else 0, limit, int(max_len), idx.ctypes.data, cap, C.byref(n), C.byref(consumed),
                       C.byref(bad), C.byref(why))
-            if rc == L.E_INVALID and n.value + 1 > cap and cap < limit + 1:
-                cap = n.value + 1                            # the text holds more records than the guess: their number is known now
-                continue
-            break
+            last = idx, n.value, consumed.value, bad.value, why.value
+            return rc, n.value + 1, None
+        rc, _ = _ask_again(one, min(limit, nbytes // 64 + 64) + 1, limit)
         del keep
-        return rc, idx, n.value, consumed.value, bad.value, why.value
+        return (rc,) + last
 
     def fastq_index(self, buf, final=True, max_records=None):
         """The record index of a chunk of FASTQ text in host memory, built on the device from the text alone
@@ -455,23 +513,19 @@ class Engine:
         filter()'s."""
         params = kw.pop("params", None) or self.params(**kw)
         counts, badrec = L.FilterCounts(), C.c_int64(-1)
-        out = {}
+        r = None
 
         def call(addr, nbytes, final_, limit, max_len_, idx_ptr, cap, n, consumed, bad, why):
-            out["a"] = (np.empty(cap, np.float64), np.empty(cap, np.int32), np.empty(cap, np.uint8), np.empty(cap, np.int32),
-                        np.empty(cap, np.uint8))
-            ee, ns, ps, lens, flags = out["a"]
+            nonlocal r
+            r = _TextResults(cap)
             return self.lib.mpb_filter_fastq_host(self.ctx, addr, nbytes, final_, limit, max_len_, idx_ptr, cap, n, consumed, bad, why,
                                                   int(fastq_offset), 1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0,
-                                                  ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data, flags.ctypes.data,
-                                                  C.byref(counts), C.byref(badrec))
+                                                  *r.ptrs(), C.byref(counts), C.byref(badrec))
         rc, idx, n, consumed, bad, why = self._fastq_call(buf, final, max_records, max_len, call)
         _check_text(rc, badrec)
         if why:
             raise NotTaken(why)
-        ee, ns, ps, lens, flags = out["a"]
-        return FastqFilterResult(idx[:n], consumed, _record_error(buf, idx, n, bad), ee[:n], ns[:n], ps[:n].view(bool), lens[:n],
-                                 flags[:n].view(bool), counts.n_pass, counts.n_overflow)
+        return FastqFilterResult(idx[:n], consumed, _record_error(buf, idx, n, bad), *r.cut(n), counts.n_pass, counts.n_overflow)
 
     # ---- BGZF FASTQ filtered where it inflates (k_bgzf_inflate, k_bgzf_crc32, the index, the pack) ----
     def crc32_ranges(self, buf, offs, lens):
@@ -518,26 +572,21 @@ class Engine:
         done, mwhy, st = np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.uint8), L.BgzfInflateStats()
         first = C.c_int64(-1)
         counts, badrec = L.FilterCounts(), C.c_int64(-1)
-        limit = (1 << 62) if max_records is None else int(max_records)
-        if limit < 0:
-            raise ValueError("max_records must not be negative")
-        cap = min(limit, total // 64 + 64) + 1                # (_fastq_call's guess, and its single retry)
-        while True:
-            idx = np.empty((cap, 6), np.int64)
-            ee, ns, ps, lens, flags = (np.empty(cap, np.float64), np.empty(cap, np.int32), np.empty(cap, np.uint8),
-                                       np.empty(cap, np.int32), np.empty(cap, np.uint8))
+        limit = _record_limit(max_records)
+        idx = r = n = consumed = bad = why = None
+
+        def call(cap, _):
+            nonlocal idx, r, n, consumed, bad, why
+            idx, r = np.empty((cap, 6), np.int64), _TextResults(cap)
             n, consumed, bad, why = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
             rc = self.lib.mpb_filter_bgzf_fastq_host(
                 self.ctx, caddr if clen else None, clen, src.ctypes.data, len(src), offs.ctypes.data, sizes.ctypes.data,
                 out_offs.ctypes.data, m, 1 if final else 0, limit, int(max_len), tbuf.ctypes.data if text else None,
                 len(tbuf) if text else 0, done.ctypes.data, mwhy.ctypes.data, C.byref(first), C.byref(st), idx.ctypes.data, cap,
                 C.byref(n), C.byref(consumed), C.byref(bad), C.byref(why), int(fastq_offset), 1 if lower_n_is_base else 0,
-                C.byref(params), 1 if poisson else 0, ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data,
-                flags.ctypes.data, C.byref(counts), C.byref(badrec))
-            if rc == L.E_INVALID and first.value < 0 and n.value + 1 > cap and cap < limit + 1:
-                cap = n.value + 1                            # the text holds more records than the guess: the whole call once more
-                continue
-            break
+                C.byref(params), 1 if poisson else 0, *r.ptrs(), C.byref(counts), C.byref(badrec))
+            return rc, (n.value + 1 if first.value < 0 else 0), None      # (no more rows to ask for once a member was handed back)
+        rc, _ = _ask_again(call, min(limit, total // 64 + 64) + 1, limit)   # (_fastq_call's guess; the whole call once more)
         del ckeep
         _check_text(rc, badrec)
         stats = {k: int(getattr(st, k)) for k, _ in L.BgzfInflateStats._fields_}
@@ -547,8 +596,8 @@ class Engine:
             raise NotTaken(why.value)
         n = n.value
         tout = tbuf[:total] if text else None
-        return BgzfFastqFilterResult(tout, stats, idx[:n], consumed.value, _record_error(tout, idx, n, bad.value), ee[:n], ns[:n],
-                                     ps[:n].view(bool), lens[:n], flags[:n].view(bool), counts.n_pass, counts.n_overflow)
+        return BgzfFastqFilterResult(tout, stats, idx[:n], consumed.value, _record_error(tout, idx, n, bad.value), *r.cut(n),
+                                     counts.n_pass, counts.n_overflow)
 
     # ---- paired-read contigs on the device (mpb_pair_rows, k_contig) ------------------------------
     @staticmethod
@@ -580,8 +629,7 @@ class Engine:
         if alignments:
             aln_cap = max(int((fidx[:, 3] + ridx[:, 3]).max()) if n else 1, 1)
             aln, aln_len, score = np.zeros((n, 2, aln_cap), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32)
-        prm = L.ContigParams(int(match), int(mismatch), int(gap), int(insert), int(deltaq), int(consensus), int(qscore_cap),
-                             1 if trim_overlap else 0)
+        prm = _contig_params(match, mismatch, gap, insert, deltaq, consensus, qscore_cap, trim_overlap)
         n_done, n_back, bad = C.c_int64(0), C.c_int64(0), C.c_int64(-1)
         chunk = (self.ctx, faddr, fbytes, fidx.ctypes.data, raddr, rbytes, ridx.ctypes.data, n,
                  int(fastq_offset), C.byref(prm), int(rec_cap), cbuf.ctypes.data, cidx.ctypes.data,
@@ -592,26 +640,18 @@ class Engine:
         if filter is None:
             rc = self.lib.mpb_contigs_text_host(*chunk)
         else:
-            max_len, lower_n_is_base, poisson, params, (ee, ns, ps, lens, flags) = filter
+            max_len, lower_n_is_base, poisson, params, r = filter
             filtered = np.zeros(n, np.uint8)
             counts, frc, fbad = L.FilterCounts(), C.c_int(0), C.c_int64(-1)
             rc = self.lib.mpb_contigs_filter_text_host(*chunk, int(max_len), 1 if lower_n_is_base else 0, C.byref(params),
-                                                       1 if poisson else 0, ee.ctypes.data, ns.ctypes.data, ps.ctypes.data,
-                                                       lens.ctypes.data, flags.ctypes.data, filtered.ctypes.data, C.byref(counts),
+                                                       1 if poisson else 0, *r.ptrs(), filtered.ctypes.data, C.byref(counts),
                                                        C.byref(frc), C.byref(fbad))
         del fkeep, rkeep
         _check_text(rc, bad)
         res = ContigResult(cbuf, cidx, np.ascontiguousarray(aux.T), done.view(bool), rec_cap, n_done.value, n_back.value, aln, aln_len, score)
         if filter is None:
             return res
-        err = None
-        if frc.value:
-            try:
-                _check_text(frc.value, fbad)
-            except ValueError as e:
-                err = e
-        return ContigFilterResult(res, ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), filtered.view(bool),
-                                  counts.n_pass, counts.n_overflow, err)
+        return ContigFilterResult(res, *r.cut(n), filtered.view(bool), counts.n_pass, counts.n_overflow, _filter_error(frc, fbad))
 
     def contigs_filter_text(self, fbuf, fidx, rbuf, ridx, fastq_offset=33, match=1, mismatch=-1, gap=-2, insert=20, deltaq=6,
                             consensus=0, qscore_cap=40, trim_overlap=False, rec_cap=None, alignments=False, max_len=0,
@@ -624,16 +664,9 @@ class Engine:
         contigs_from_fastq_filtered does).  max_len, lower_n_is_base, poisson, out and `kw` as filter_text's.  What filter_text
         would have raised for the chunk is returned as filter_error (with .bad_record), not raised: the contigs are valid."""
         params = kw.pop("params", None) or self.params(**kw)
-        n = len(fidx)
-        if out is None:
-            out = np.empty(n, np.float64), np.empty(n, np.int32), np.empty(n, np.uint8), np.empty(n, np.int32), np.empty(n, np.uint8)
-        ee, ns, ps, lens, flags = out
-        if (ee.dtype, ns.dtype, ps.dtype, lens.dtype, flags.dtype) != (np.float64, np.int32, np.uint8, np.int32, np.uint8) or \
-                not all(a.flags.c_contiguous and len(a) >= n for a in out):
-            raise ValueError("out must be contiguous (float64, int32, uint8, int32, uint8) arrays of at least n entries")
         return self.contigs_text(fbuf, fidx, rbuf, ridx, fastq_offset, match, mismatch, gap, insert, deltaq, consensus, qscore_cap,
                                  trim_overlap, rec_cap=rec_cap, alignments=alignments,
-                                 filter=(max_len, lower_n_is_base, poisson, params, out))
+                                 filter=(max_len, lower_n_is_base, poisson, params, _TextResults(len(fidx), out)))
 
     def contigs_filter_fastq(self, fbuf, rbuf, ffinal=True, rfinal=True, max_records=None, fastq_offset=33, match=1, mismatch=-1,
                              gap=-2, insert=20, deltaq=6, consensus=0, qscore_cap=40, trim_overlap=False, max_len=0,
@@ -647,22 +680,20 @@ class Engine:
         params = kw.pop("params", None) or self.params(**kw)
         fkeep, faddr, fbytes = _text_ptr(fbuf)
         rkeep, raddr, rbytes = _text_ptr(rbuf)
-        limit = (1 << 62) if max_records is None else int(max_records)
-        if limit < 0:
-            raise ValueError("max_records must not be negative")
+        limit = _record_limit(max_records)
         cap = int(idx_cap_rows) if idx_cap_rows is not None else min(limit, max(fbytes, rbytes) // 64 + 64) + 1
         out_cap = int(out_cap_bytes) if out_cap_bytes is not None else 2 * (fbytes + rbytes) + 16 * cap
-        prm = L.ContigParams(int(match), int(mismatch), int(gap), int(insert), int(deltaq), int(consensus), int(qscore_cap),
-                             1 if trim_overlap else 0)
+        prm = _contig_params(match, mismatch, gap, insert, deltaq, consensus, qscore_cap, trim_overlap)
         i64 = lambda v=0: C.c_int64(v)
-        calls = 0
-        while True:
-            calls += 1
+        fidx = ridx = cbuf = cidx = aux = done = r = filtered = n_f = n_r = n_pairs = mis = n_built = f_cons = r_cons = rec_cap = None
+        f_kind = r_kind = why = which = n_done = n_back = counts = frc = fbad = None
+
+        def call(cap, out_cap):
+            nonlocal fidx, ridx, cbuf, cidx, aux, done, r, filtered, n_f, n_r, n_pairs, mis, n_built, f_cons, r_cons, rec_cap
+            nonlocal f_kind, r_kind, why, which, n_done, n_back, counts, frc, fbad
             fidx, ridx = np.empty((cap, 6), np.int64), np.empty((cap, 6), np.int64)
             cbuf, cidx, aux, done = np.empty(out_cap, np.uint8), np.empty((cap, 6), np.int64), np.empty((3, cap), np.int32), np.zeros(cap, np.uint8)
-            ee, ns, ps, lens, flags = (np.empty(cap, np.float64), np.empty(cap, np.int32), np.empty(cap, np.uint8),
-                                       np.empty(cap, np.int32), np.empty(cap, np.uint8))
-            filtered = np.zeros(cap, np.uint8)
+            r, filtered = _TextResults(cap), np.zeros(cap, np.uint8)
             n_f, n_r, n_pairs, mis, n_built, f_cons, r_cons, rec_cap = i64(), i64(), i64(), i64(-1), i64(), i64(), i64(), i64()
             f_kind, r_kind, why, which = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
             n_done, n_back, counts, frc, fbad = i64(), i64(), L.FilterCounts(), C.c_int(0), i64(-1)
@@ -672,18 +703,10 @@ class Engine:
                 C.byref(mis), C.byref(n_built), C.byref(f_cons), C.byref(r_cons), C.byref(why), C.byref(which), C.byref(rec_cap),
                 cbuf.ctypes.data, out_cap, cidx.ctypes.data, aux[0].ctypes.data, aux[1].ctypes.data, aux[2].ctypes.data, done.ctypes.data,
                 C.byref(n_done), C.byref(n_back), int(max_len), 1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0,
-                ee.ctypes.data, ns.ctypes.data, ps.ctypes.data, lens.ctypes.data, flags.ctypes.data, filtered.ctypes.data,
-                C.byref(counts), C.byref(frc), C.byref(fbad))
-            need = max(n_f.value, n_r.value) + 1
-            if rc == L.E_INVALID and need > cap and cap < limit + 1:
-                if out_cap_bytes is None:
-                    out_cap += 16 * (need - cap)
-                cap = need                                   # a text holds more records than the guess: their number is known now
-                continue
-            if rc == L.E_INVALID and rec_cap.value > 8 and n_pairs.value * rec_cap.value > out_cap:
-                out_cap = n_pairs.value * rec_cap.value      # (n_built <= n_pairs: enough whatever the headers say)
-                continue
-            break
+                *r.ptrs(), filtered.ctypes.data, C.byref(counts), C.byref(frc), C.byref(fbad))
+            # (bytes: n_built <= n_pairs, so n_pairs slots are enough whatever the headers say; a slot of 8 bytes holds no pair)
+            return rc, max(n_f.value, n_r.value) + 1, (n_pairs.value * rec_cap.value if rec_cap.value > 8 else 0)
+        rc, calls = _ask_again(call, cap, limit, out_cap, grow_out=out_cap_bytes is None)
         del fkeep, rkeep
         L.check(rc)
         if why.value:
@@ -691,14 +714,7 @@ class Engine:
         n = n_built.value
         res = ContigResult(cbuf[:n * rec_cap.value], cidx[:n], np.ascontiguousarray(aux[:, :n].T), done[:n].view(bool), rec_cap.value,
                            n_done.value, n_back.value, None, None, None)
-        err = None
-        if frc.value:
-            try:
-                _check_text(frc.value, fbad)
-            except ValueError as e:
-                err = e
-        res = ContigFilterResult(res, ee[:n], ns[:n], ps[:n].view(bool), lens[:n], flags[:n].view(bool), filtered[:n].view(bool),
-                                 counts.n_pass, counts.n_overflow, err)
+        res = ContigFilterResult(res, *r.cut(n), filtered[:n].view(bool), counts.n_pass, counts.n_overflow, _filter_error(frc, fbad))
         return PairedFastqResult(res, fidx[:n_f.value], ridx[:n_r.value], f_cons.value, r_cons.value,
                                  _record_error(fbuf, fidx, n_f.value, f_kind.value), _record_error(rbuf, ridx, n_r.value, r_kind.value),
                                  mis.value, n_pairs.value, n, calls)

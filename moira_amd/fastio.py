@@ -601,6 +601,33 @@ def _plain_file_fd(fh):
         return None
 
 
+def chunks_of(data, eof, max_records, index_fn):
+    """The single-file chunk loop: index_fn(data, eof, max_records) -> (idx, consumed, err, extra) indexes what lies at the
+    front of `data` (bytes, or a uint8 array that is only ever sliced as a view); every chunk is yielded as
+    (data, idx) + extra, a record that fails the reference's checks raises its error after the records before it, and the
+    generator returns the unconsumed rest -- an incomplete record, for whoever reads on."""
+    while len(data):
+        idx, consumed, err, extra = index_fn(data, eof, max_records)
+        if len(idx):
+            yield (data, idx) + extra
+        if err is not None:
+            raise err
+        data = data[consumed:]
+        if len(idx) < max_records:
+            break                                           # the rest is an incomplete record: read on
+    return data
+
+
+def read_blocks(fh, block_bytes):
+    """The stream as (bytes, whether the text has ended); the last block is empty and says that it has."""
+    while True:
+        data = fh.read(block_bytes)
+        if not data:
+            break
+        yield data, False
+    yield b"", True
+
+
 class FastqChunks:
     """Iterate a binary FASTQ stream as (buf, idx) chunks of at most `max_records` records.
     Raises Unsupported before anything has been yielded from a chunk the C parser cannot take.
@@ -614,6 +641,9 @@ class FastqChunks:
         self.block = block_bytes or (1 << 25)
         # an uncompressed file read by several threads: 128 MiB, so that a chunk of 262144 x 250-bp records is one block
         self.plain_block = block_bytes or (1 << 27)
+
+    def _index(self, data, eof, max_records):
+        return index(data, eof, max_records, self.threads) + ((),)
 
     def _iter_plain(self, fd):
         L = load()
@@ -630,21 +660,10 @@ class FastqChunks:
                 raise OSError(_err())
             off += got
             eof = got < want or off >= size
-            data = buf[:len(carry) + got]
-            pos = 0
-            while pos < len(data):
-                view = data[pos:]
-                idx, consumed, err = index(view, eof, self.max_records, self.threads)
-                if len(idx):
-                    yield view, idx
-                if err is not None:
-                    raise err
-                pos += consumed
-                if len(idx) < self.max_records:
-                    break                                   # the rest is an incomplete record: read on
+            rest = yield from chunks_of(buf[:len(carry) + got], eof, self.max_records, self._index)     # (views: no copy)
             if eof:
                 return                                      # trailing lines that do not make a record are dropped
-            carry = data[pos:].copy()
+            carry = rest.copy()
 
     def __iter__(self):
         fd = _plain_file_fd(self.fh) if self.threads > 1 else None
@@ -652,25 +671,11 @@ class FastqChunks:
             yield from self._iter_plain(fd)
             return
         tail = b""
-        eof = False
-        while not eof or tail:
-            if not eof:
-                more = self.fh.read(self.block)
-                if more:
-                    tail = tail + more if tail else more
-                else:
-                    eof = True
-            while tail:
-                idx, consumed, err = index(tail, eof, self.max_records, self.threads)
-                if len(idx):
-                    yield tail, idx
-                if err is not None:
-                    raise err
-                tail = tail[consumed:]
-                if len(idx) < self.max_records:
-                    break                       # the rest is an incomplete record: read on
-            if eof:
-                return                          # trailing lines that do not make a record are dropped
+        for more, eof in read_blocks(self.fh, self.block):
+            if more:
+                tail = tail + more if tail else more
+            tail = yield from chunks_of(tail, eof, self.max_records, self._index)
+        # trailing lines that do not make a record are dropped
 
 
 class PairedRecordError(Exception):
@@ -679,6 +684,56 @@ class PairedRecordError(Exception):
     def __init__(self, which, err):
         Exception.__init__(self, which, err)
         self.which, self.err = which, err
+
+
+def paired_host_pass(tail, eof, max_records, threads=1, headers=True):
+    """The host's indexes of two tails -> ((fidx, ridx), (f_bad, r_bad), n, (f_consumed, r_consumed), mismatch): n pairs are
+    complete in both, the consumed counts are those of exactly n records (a file that holds more is indexed again at n, to
+    keep what the other file has not reached yet), and mismatch is first_header_mismatch over the n pairs, or -1
+    (headers=False: not looked at, for a caller that compares the headers itself)."""
+    got = [index(tail[k], eof[k], max_records, threads) for k in (0, 1)]
+    n = min(len(got[0][0]), len(got[1][0]))
+    consumed = [got[k][1] if len(got[k][0]) == n else index(tail[k], eof[k], n, threads)[1] for k in (0, 1)] if n else [0, 0]
+    mismatch = first_header_mismatch(tail[0], got[0][0][:n], tail[1], got[1][0][:n]) if n and headers else -1
+    return (got[0][0], got[1][0]), (got[0][2], got[1][2]), n, consumed, mismatch
+
+
+def paired_lockstep(blocks, block_bytes, max_records, one_pass):
+    """Two FASTQ texts in lockstep.  blocks: two iterators of (bytes, whether the text has ended), as read_blocks makes them;
+    one_pass(tail, eof) -> (idx, bad, n, consumed, payload) over the two tails: both indexes, both bad records (None, or the
+    RecordError of the record after the last), the number of pairs, the bytes those pairs take of either tail, and
+    whatever the caller wants back.  Yields (fbuf, fidx, rbuf, ridx, n, payload) for every pass with n > 0; the first n rows
+    of either index are the pairs.  Stops with the shorter file, as zip() does in the reference's parser
+    (moira/moira.py:1158-1160); a record that fails the reference's checks raises PairedRecordError only when its pair is
+    reached -- both files hold record n -- after the pairs before it, forward file first."""
+    tail, eof, want = [b"", b""], [False, False], [True, True]
+    while True:
+        for k in (0, 1):
+            if want[k] and not eof[k]:
+                more, eof[k] = next(blocks[k])
+                if more:
+                    tail[k] = tail[k] + more if tail[k] else more
+        idx, bad, n, consumed, payload = one_pass(tail, eof)
+        # does file k hold a complete record number n (sound or not)?
+        has_next = [len(idx[k]) > n or bad[k] is not None for k in (0, 1)]
+        err = None
+        if has_next[0] and has_next[1]:
+            for k in (0, 1):
+                if err is None and bad[k] is not None and len(idx[k]) == n:
+                    err = PairedRecordError(k, bad[k])
+            if err is not None and err.which == 1:       # then forward record n is sound: the reference names it
+                err.err.forward_header = header_of(tail[0], idx[0][n])
+        if n:
+            yield tail[0], idx[0], tail[1], idx[1], n, payload
+            tail = [tail[k][consumed[k]:] for k in (0, 1)]
+        if err is not None:
+            raise err
+        if n == max_records:
+            want = [len(tail[k]) < block_bytes for k in (0, 1)]
+            continue
+        if any(not has_next[k] and eof[k] for k in (0, 1)):
+            return                                       # one file is exhausted: zip() stops here
+        want = [not has_next[k] for k in (0, 1)]
 
 
 class PairedFastqChunks:
@@ -690,40 +745,10 @@ class PairedFastqChunks:
         self.fh, self.max_records, self.block, self.threads = (ffh, rfh), max_records, block_bytes, max(1, int(threads))
 
     def __iter__(self):
-        tail, eof, want = [b"", b""], [False, False], [True, True]
-        while True:
-            for k in (0, 1):
-                if want[k] and not eof[k]:
-                    more = self.fh[k].read(self.block)
-                    if more:
-                        tail[k] = tail[k] + more if tail[k] else more
-                    else:
-                        eof[k] = True
-            got = [index(tail[k], eof[k], self.max_records, self.threads) for k in (0, 1)]
-            n = min(len(got[0][0]), len(got[1][0]))
-            # does file k hold a complete record number n (sound or not)?
-            has_next = [len(got[k][0]) > n or got[k][2] is not None for k in (0, 1)]
-            err = None
-            if has_next[0] and has_next[1]:
-                for k in (0, 1):
-                    if err is None and got[k][2] is not None and len(got[k][0]) == n:
-                        err = PairedRecordError(k, got[k][2])
-                if err is not None and err.which == 1:       # then forward record n is sound: the reference names it
-                    err.err.forward_header = header_of(tail[0], got[0][0][n])
-            if n:
-                for k in (0, 1):
-                    if len(got[k][0]) > n:                   # keep what the other file has not reached yet
-                        got[k] = index(tail[k], eof[k], n, self.threads)
-                yield tail[0], got[0][0], tail[1], got[1][0]
-                tail = [tail[k][got[k][1]:] for k in (0, 1)]
-            if err is not None:
-                raise err
-            if n == self.max_records:
-                want = [len(tail[k]) < self.block for k in (0, 1)]
-                continue
-            if any(not has_next[k] and eof[k] for k in (0, 1)):
-                return                                       # one file is exhausted: zip() stops here
-            want = [not has_next[k] for k in (0, 1)]
+        one_pass = lambda tail, eof: paired_host_pass(tail, eof, self.max_records, self.threads, headers=False)
+        for fbuf, fidx, rbuf, ridx, n, _ in paired_lockstep([read_blocks(fh, self.block) for fh in self.fh], self.block,
+                                                            self.max_records, one_pass):
+            yield fbuf, fidx[:n], rbuf, ridx[:n]
 
 
 class FastaQualChunks:

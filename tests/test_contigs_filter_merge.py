@@ -142,7 +142,7 @@ def test_cli_helper_hands_the_results_on_with_the_chunk():
     texts = P.texts(make_pairs())
     eng = FakeEngine(texts, (2,), (9,))
     be = fake_backend(eng)
-    chunk = cli._DeferredContigs(run_args(), *texts, 33, eng, fused=(be, ("poisson_binomial", None, 0, False)))
+    chunk = cli._DeferredContigs(cli._Contigs(run_args()), *texts, 33, eng, fused=cli._TextFilter(be, run_args(), 33, 0, False, "poisson_binomial", None))
     buf, idx, aux, filtered = cli._filtered_where_built(chunk.build())
     assert eng.fused_calls == 1 and eng.plain_calls == 0 and be.text_calls == [[2, 9]]
     want_ee, want_n = fake_results(eng.host[1], np.arange(60), 0)
@@ -155,7 +155,7 @@ def test_cli_helper_sends_a_refused_chunk_down_the_device_pack_branch():
     texts = P.texts(make_pairs())
     eng = FakeEngine(texts, (2,), (), error=ValueError("Qualities must have positive values."))
     be = fake_backend(eng)
-    chunk = cli._DeferredContigs(run_args(), *texts, 33, eng, fused=(be, ("poisson_binomial", None, 0, False)))
+    chunk = cli._DeferredContigs(cli._Contigs(run_args()), *texts, 33, eng, fused=cli._TextFilter(be, run_args(), 33, 0, False, "poisson_binomial", None))
     buf, idx, aux, filtered = cli._filtered_where_built(chunk.build())
     assert filtered is None and be.text_calls == [] and np.array_equal(idx, eng.host[1])
     assert cli._filtered_where_built((buf, idx, aux)) == (buf, idx, aux, None)
@@ -170,7 +170,7 @@ def test_either_switch_alone_does_not_reach_the_fused_call():
     assert not cli._fused_applies(True, True, True, be)                               # --only_contig never reaches the device pack
     assert not cli._fused_applies(True, True, False, types.SimpleNamespace(engine=object(), text_choice=be.text_choice))
     # --device_contigs alone: the chunk is built through contigs_text, as before
-    built = cli._DeferredContigs(run_args(), *texts, 33, eng).build()
+    built = cli._DeferredContigs(cli._Contigs(run_args()), *texts, 33, eng).build()
     assert len(built) == 3 and eng.plain_calls == 1 and eng.fused_calls == 0 and be.text_calls == []
 
 

@@ -257,3 +257,78 @@ def test_what_the_host_calls_unsupported_is_the_runs_to_take():
     ix = cli._DeviceIndexer(FakeEngine(refuse={0}), {}, 100, lambda e: None)
     with pytest.raises(F.Unsupported):
         list(ix.take(cli._DeferredBlock(text, True)))
+
+
+# ---- the capacity loop of the text-alone entries (engine._ask_again) against a scripted call -----------------------------------------
+
+def scripted(answers):
+    """-> (call, the (cap, out_cap) pairs it was asked with): the k-th call answers answers[k] = (rc, rows needed, bytes needed)."""
+    asked = []
+
+    def call(cap, out_cap):
+        asked.append((cap, out_cap))
+        return answers[len(asked) - 1]
+    return call, asked
+
+
+def test_a_guess_that_is_enough_is_one_call():
+    call, asked = scripted([(L.OK, 8, None)])
+    assert E._ask_again(call, 11, 1 << 62) == (L.OK, 1) and asked == [(11, None)]
+    call, asked = scripted([(L.E_INVALID, 8, None)])                     # refused for another reason: not asked again
+    assert E._ask_again(call, 11, 1 << 62) == (L.E_INVALID, 1) and asked == [(11, None)]
+
+
+def test_a_guess_too_small_is_asked_once_more_with_the_rows_needed():
+    call, asked = scripted([(L.E_INVALID, 41, None), (L.OK, 41, None)])
+    assert E._ask_again(call, 11, 1 << 62) == (L.OK, 2) and asked == [(11, None), (41, None)]
+    # through Engine._fastq_call (it needs no context): the guess is 64 bytes a record, the second call has n + 1 rows
+    text, seen = b"@r\nAC\n+\nII\n" * 500, []
+
+    def entry(addr, nbytes, final, limit, max_len, idx_ptr, cap, n, consumed, bad, why):
+        seen.append((cap, limit))
+        n._obj.value = 500
+        return L.E_INVALID if cap < 501 else L.OK
+    rc, idx, n, consumed, bad, why = E.Engine._fastq_call(None, text, True, None, 0, entry)
+    assert seen == [(len(text) // 64 + 65, 1 << 62), (501, 1 << 62)] and (rc, len(idx), n) == (L.OK, 501, 500)
+
+
+def test_at_the_record_limit_the_error_surfaces_without_a_second_call():
+    call, asked = scripted([(L.E_INVALID, 30, None)])
+    rc, calls = E._ask_again(call, 11, 10)                              # cap == limit + 1: more rows cannot be the reason
+    assert (rc, calls) == (L.E_INVALID, 1) and asked == [(11, None)]
+    with pytest.raises(ValueError):
+        L.check(rc)
+    with pytest.raises(ValueError, match="max_records must not be negative"):
+        E._record_limit(-1)
+    assert E._record_limit(None) == 1 << 62 and E._record_limit(7) == 7
+
+
+def test_the_paired_entrys_two_capacities_grow_as_they_did():
+    # rows too small, then bytes too small: + 16 bytes per missing row, then n_pairs * rec_cap
+    call, asked = scripted([(L.E_INVALID, 25, 0), (L.E_INVALID, 25, 5000), (L.OK, 25, 5000)])
+    assert E._ask_again(call, 10, 1 << 62, 1000, grow_out=True) == (L.OK, 3)
+    assert asked == [(10, 1000), (25, 1000 + 16 * 15), (25, 5000)]
+    # a byte capacity the caller gave is not grown by the rows step
+    call, asked = scripted([(L.E_INVALID, 25, 0), (L.OK, 25, 900)])
+    assert E._ask_again(call, 10, 1 << 62, 1000, grow_out=False) == (L.OK, 2) and asked == [(10, 1000), (25, 1000)]
+    # enough bytes, another reason: the error surfaces
+    call, asked = scripted([(L.E_INVALID, 10, 1000)])
+    assert E._ask_again(call, 10, 1 << 62, 1000, grow_out=True) == (L.E_INVALID, 1)
+
+
+def test_a_handed_back_bgzf_member_is_not_asked_again():
+    """Engine.filter_bgzf_fastq reports no rows to ask for once a member was handed back (first >= 0), whatever n says."""
+    call, asked = scripted([(L.E_INVALID, 0, None)])
+    assert E._ask_again(call, 11, 1 << 62) == (L.E_INVALID, 1) and asked == [(11, None)]
+    # the method itself over a scripted entry: n says 999 rows, far above the guess, but member 0 was handed back
+    caps = []
+
+    def entry(*a):
+        first, cap, n = a[16], a[19], a[20]
+        caps.append(cap)
+        first._obj.value, n._obj.value = 0, 999
+        return L.E_INVALID
+    fake = types.SimpleNamespace(ctx=None, lib=types.SimpleNamespace(mpb_filter_bgzf_fastq_host=entry), params=E.Engine.params)
+    with pytest.raises(ValueError):
+        E.Engine.filter_bgzf_fastq(fake, b"\0" * 64, [0], [64], [0, 100])
+    assert caps == [100 // 64 + 65]

@@ -241,10 +241,38 @@ def expect(ftext, rtext, block, max_records=1000):
     return out, err
 
 
+LINE_ARGS = types.SimpleNamespace(forward_fastq="forward.fastq", reverse_fastq="reverse.fastq")
+
+
+def line_parser(ftext, rtext):
+    """The line parser over the same two texts -- it shares no code with the pairing loop -> (the headers of the pairs it yields
+    before the end, the exception it ends with or None)."""
+    files = [io.StringIO(t.decode("ascii"), newline=None) for t in (ftext, rtext)]
+    files[0].moira_name, files[1].moira_name = LINE_ARGS.forward_fastq, LINE_ARGS.reverse_fastq
+    headers, err = [], None
+    try:
+        for rec in cli.parse_fastq(files[0], files[1], 33, raw=True):
+            headers.append(rec[0])
+    except (cli.NameMismatchError, cli.EmptySeqError, cli.EmptyQualError, cli.LengthMismatchError) as e:
+        err = e
+    return headers, err
+
+
+def as_the_run_raises(err):
+    """(class, arguments) of what the run raises for the way the loop ended: a PairedRecordError goes through cli._record_error."""
+    if isinstance(err, F.PairedRecordError):
+        err = cli._record_error(err.which, err.err, LINE_ARGS)
+    return None if err is None else (type(err), err.args)
+
+
 def same(ftext, rtext, size, max_records=1000, **kw):
     got, err, eng = drive(ftext, rtext, (size, size), max_records, **kw)
     want, want_err = expect(ftext, rtext, size, max_records)
     assert got == want and signature(err) == signature(want_err)
+    # both of those run fastio.paired_lockstep: the line parser is the witness that does not
+    line_headers, line_err = line_parser(ftext, rtext)
+    assert [h.decode("ascii").replace(":", "_") for c in got for h, _, _ in c] == line_headers      # (fastio.header_of's rule)
+    assert as_the_run_raises(err) == as_the_run_raises(line_err)
     return got, err, eng
 
 
