@@ -747,6 +747,48 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *ctx, const char *carry, int64_t carry_le
                                mpb_filter_counts *counts, int64_t *bad_record);
 
 /*
+ * Output records formatted on the device (k_fmt_count, k_fmt_scan, k_fmt_write; csrc/mpb_format_kernels.hip): records sel[k]
+ * (sel NULL: k; any order, repeats allowed), k < nsel, of a text and its record index idx[n_records][MPB_IDX_COLS] become fasta
+ * (kind 0), qual (1) or fastq (2) text, byte for byte what mio_format (include/moira_io.h) writes for the same arguments with
+ * ee == NULL -- that function stays the definition of the output; its ";ee=...;" suffix is not offered here.  relabel (at most
+ * 255 bytes) with relabel_index[nsel] (each >= 0) replaces the header token; labels[n_labels] (at most 16, each at most 255
+ * bytes) with label_id[nsel] (-1: none) appends "\t" + label.
+ * UPLOADED FORM (resident == 0): text[text_bytes] (at most 1 GiB) and idx go up once; any buffer and index of that layout do
+ * (fastio.index's, or the contigs' out_buf + out_idx).  The selected rows are validated on the host first -- sel[k] in
+ * 0..n_records-1, header, sequence and (kinds 1, 2) quality ranges inside the text, SEQ_LEN == QUAL_LEN for kinds 1 and 2,
+ * relabel_index[k] >= 0, label_id[k] < n_labels -- and a bad one is MPB_E_INVALID with *bad_record = k before anything is
+ * uploaded; the kernels make the same checks again.
+ * RESIDENT FORM (resident != 0; text and idx NULL): the text and the device-written index that the last successful
+ * mpb_filter_fastq_host or mpb_filter_bgzf_fastq_host call of this context left on the device are read where they lie (for the
+ * BGZF call: carry + members' text, as its index counts); n_records is that call's *n.  The context numbers these texts:
+ * mpb_resident_text returns the generation in force (1, 2, ...), 0 for none.  Every successful call of the two makes a new one.
+ * The generation is set to none by every call that may move, grow, overwrite or free the blocks the text and index lie in,
+ * whether it succeeds, fails or hands its text back: mpb_fastq_index_host, mpb_filter_fastq_host, mpb_filter_bgzf_fastq_host,
+ * mpb_contigs_filter_fastq_host and mpb_destroy.  No other call touches them.  A `resident` that is not the generation in force
+ * is MPB_E_INVALID with a message that holds "is not resident", and nothing is touched.  Only sel, relabel_index, label_id and
+ * the strings go up (the compressed form adds 16 bytes per member).  A device-written row that fails the kernel's check is never
+ * expected: MPB_E_INVALID with *bad_record.
+ * SIZES.  *text_needed receives the length of the formatted text once the scan has run.  Text form (bgzf == 0): an out_cap
+ * below it is MPB_E_INVALID with *text_needed set, so a caller may ask again; else out[0, *out_bytes) is the text.  Compressed
+ * form (bgzf != 0): out_cap must be at least mpb_bgzf_bound(*text_needed) (MPB_E_INVALID with *text_needed set otherwise); out
+ * receives the BGZF members of the formatted text in order, without the end marker, byte for byte what mpb_bgzf_compress_host
+ * returns for that text; stats (may be NULL) as there.  The formatted text is written in windows of at most 256 MiB
+ * (environment MPB_FORMAT_PIECE_BYTES: less; the compressed form: whole members, at most MPB_BGZF_PIECE_MEMBERS' piece), each
+ * copied back or compressed before the next; neither the text nor the members depend on the window.
+ * Argument errors (said before the context is looked at) are MPB_E_INVALID: a NULL where a pointer is needed, a negative size,
+ * kind outside 0..2, fastq_offset or out_offset outside 0..255, relabel without relabel_index, label_id without labels, more
+ * than 16 labels or an over-long string, both or neither of text / idx and resident.  When a row fails, nothing is written.
+ * The three kernels have no MPB_K_* id: they are timed under MPB_K_PACK_TEXT, so after this call alone that slot holds them
+ * alone.  Synchronous; the staging blocks belong to the context.
+ */
+int mpb_format_text_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, const int64_t *idx, int64_t n_records, int64_t resident,
+                         const int64_t *sel, int64_t nsel, int32_t kind, int32_t fastq_offset, int32_t out_offset, int32_t clamp_q0,
+                         int32_t max_len, const char *relabel, const int64_t *relabel_index, const char *const *labels,
+                         int32_t n_labels, const int32_t *label_id, int32_t bgzf, uint8_t *out, int64_t out_cap, int64_t *out_bytes,
+                         int64_t *text_needed, int64_t *bad_record, mpb_bgzf_stats *stats);
+int64_t mpb_resident_text(mpb_ctx *ctx);
+
+/*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is
  * cut into n_ctx contiguous, balanced shards in read order, one host thread per context runs mpb_filter_host
  * (poisson == 0) or mpb_filter_poisson_host (poisson != 0) on its shard, and every shard's results land in the

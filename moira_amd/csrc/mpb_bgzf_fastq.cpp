@@ -114,6 +114,7 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *c, const char *carry, int64_t carry_len,
     } catch (const std::bad_alloc &) { return fail(MPB_E_NOMEM, "out of host memory for %lld members", (long long)n_members); }
     if ((rc = mpb_bgzf_member_rows(in, in_len, offs, sizes, out_offs, n_members, rows.data(), crc.data(), reason.data()))) return rc;
     CTXCHK(c);
+    resident_drop(c);
     *first_back = -1; *n = 0; *consumed = 0; *bad_kind = 0; *why = MPB_FQ_WHY_TAKEN;
     if (counts) memset(counts, 0, sizeof(*counts));
     if (stats) { memset(stats, 0, sizeof(*stats)); stats->members = n_members; stats->handed_back = n_members; }

@@ -374,6 +374,7 @@ int mpb_contigs_filter_fastq_host(mpb_ctx *c, const char *ftext, int64_t ftext_b
     if ((rc = check_text_bytes(ftext_bytes)) || (rc = check_text_bytes(rtext_bytes))) return rc;
     if ((rc = check_contig_params(params, &fa))) return rc;
     CTXCHK(c);
+    resident_drop(c);                                        // (both texts' shares are carved out of the index's two blocks)
     *n_f = 0; *n_r = 0; *f_bad_kind = 0; *r_bad_kind = 0; *n_pairs = 0; *mismatch = -1; *n_built = 0; *f_consumed = 0; *r_consumed = 0;
     *why = MPB_FQ_WHY_TAKEN; *which = 0; *rec_cap_out = 8;
     const int64_t maxabs = contig_maxabs(params);

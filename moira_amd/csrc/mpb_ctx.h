@@ -114,6 +114,7 @@ struct PinWords {
     int64_t fq_status2[4];
     int64_t pair_status[4];                              // ... k_pair_rows' / k_pair_count's status, both ways
     uint32_t pair_head[MPB_PAIR_HEAD_WORDS];             // ... k_pair_scan's head words: the pairs per class, the classes' first places
+    int64_t fmt_words[2];                                // mpb_format_text_host: k_fmt_count's status, both ways; k_fmt_scan's head word
 };
 
 struct TimedSpan { int kid; hipEvent_t a, b; };
@@ -187,6 +188,14 @@ struct mpb_ctx {
     Buf fastq_stage{BUF_DEVICE};         // mpb_fastq_index_host / mpb_filter_fastq_host: text | tile table | prefix | head | status
     Buf fastq_index{BUF_DEVICE};         // ... and, sized from the counted lines: line starts | index rows | kinds | descriptors
                                          // (mpb_contigs_filter_fastq_host: both texts' shares of either block, one carve each, and the pairing block)
+    Buf format_stage{BUF_DEVICE};        // mpb_format_text_host: text | index | sel | relabel_index | label_id | blob | sizes | prefix | words | one piece
+    Buf format_out{BUF_DEVICE};          // ... one window of the formatted text, or the CRC ranges of one piece of its members
+    // the text and index the last successful mpb_filter_fastq_host / mpb_filter_bgzf_fastq_host call left in the two blocks above
+    // (mpb_format_text_host's resident form); gen == 0: none
+    struct ResidentText {
+        int64_t gen = 0, last = 0;       // the generation in force; the last one handed out
+        const uint8_t *text = nullptr; int64_t text_bytes = 0; const int64_t *idx = nullptr; int64_t n = 0;
+    } resident;
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
     struct NarrowChoice {                // the last decision, reused while the batches keep their shape (it steers speed only)
@@ -340,6 +349,34 @@ struct FastqFilterAsk {
 };
 int filter_indexed(StreamQueue &q, const Indexed &in, int64_t text_bytes, uint8_t *text_out, int64_t *idx_out, int64_t *n,
                    int64_t *consumed, int32_t *bad_kind, const FastqFilterAsk &ask, TextResults &r);
+// ... the text and the device-written index a successful filter_indexed left in fastq_stage / fastq_index become the context's
+// resident text (a new generation); resident_drop: none.  Every entry that carves either block drops it first.
+void resident_keep(mpb_ctx *c, const Indexed &in, int64_t text_bytes);
+void resident_drop(mpb_ctx *c);
+// mpb_bgzf.cpp: one piece of text | tokens | slots | sizes | status rows | CRCs | offsets | the framed output, and what the host
+// keeps of a piece; shared with mpb_format.cpp, whose pieces of text are written where the kernels read them
+struct BgzfStage {
+    uint8_t *text; uint32_t *tok; uint8_t *slots; uint32_t *size, *mstat, *crc; int64_t *off; uint8_t *out;
+    void layout(Carver &k, int64_t members)
+    {
+        k.take(text, align_up(members * (int64_t)MPB_BGZF_DATA, 16));
+        k.take(tok, members * (int64_t)MPB_BGZF_DATA);
+        k.take(slots, members * (int64_t)MPB_BGZF_SLOT);
+        k.take(size, members); k.take(mstat, members * 4); k.take(crc, members);
+        k.take(off, members + 1);
+        k.take(out, members * ((int64_t)MPB_BGZF_DATA + 31));
+    }
+};
+struct BgzfHost {
+    std::vector<uint32_t> crc, mstat;                        // crc: the members' CRCs, then the device's refusal marks
+    std::vector<int64_t> off;
+    int reserve(int64_t per_piece);
+};
+// the members of one piece (MPB_BGZF_PIECE_MEMBERS; at most 1024)
+int64_t bgzf_piece_members(int64_t members);
+int bgzf_compress_piece(StreamQueue &q, const BgzfStage &st, int64_t tb, int64_t nm, const uint8_t *host_text,
+                        const mpb_crc_range *d_ranges, uint32_t *d_bad, BgzfHost &h, uint8_t *out, int64_t out_room, int64_t *got_out,
+                        mpb_bgzf_stats *stats);
 // mpb_perread.cpp: the per-read entry's resident kernel leaves (before anything is freed: the runtime waits for the whole
 // device there); ... and its stream and blocks go
 void serve_quiesce(mpb_ctx *c);

@@ -107,6 +107,16 @@ int index_on_device(StreamQueue &q, const char *text, int64_t text_bytes, int32_
 
 }  // namespace
 
+void resident_keep(mpb_ctx *c, const Indexed &in, int64_t text_bytes)
+{
+    c->resident.gen = ++c->resident.last;
+    c->resident.text = in.st.text; c->resident.text_bytes = text_bytes; c->resident.idx = in.ix.idx; c->resident.n = in.n;
+}
+
+void resident_drop(mpb_ctx *c) { c->resident.gen = 0; }
+
+int64_t mpb_resident_text(mpb_ctx *c) { return c ? c->resident.gen : 0; }
+
 // the rows of the index, the offender's kind and the first byte behind the last record, queued for the caller's arrays
 void queue_index_out(StreamQueue &q, const Indexed &in, int64_t *idx_out, uint32_t *consumed32, uint8_t *kind8)
 {
@@ -142,6 +152,7 @@ int filter_indexed(StreamQueue &q, const Indexed &in, int64_t text_bytes, uint8_
     else rc = q.wait("hipMemcpyAsync (index, text)");
     if (rc) return rc;
     *n = in.n; *consumed = (int64_t)*consumed32; *bad_kind = (int32_t)*kind8;
+    resident_keep(c, in, text_bytes);
     if (ask.counts) { ask.counts->n_reads = in.n; ask.counts->n_pass = n_pass; ask.counts->n_fail = in.n - n_pass; ask.counts->n_overflow = n_overflow; }
     return MPB_OK;
 }
@@ -153,6 +164,7 @@ int mpb_fastq_index_host(mpb_ctx *c, const char *text, int64_t text_bytes, int32
     int rc = check_args(text, text_bytes, max_records, max_len, idx_out, idx_cap_rows, n, consumed, bad_kind, why, "mpb_fastq_index_host");
     if (rc) return rc;
     CTXCHK(c);
+    resident_drop(c);
     *n = 0; *consumed = 0; *bad_kind = 0;
     Indexed in;
     StreamQueue q(c);
@@ -183,6 +195,7 @@ int mpb_filter_fastq_host(mpb_ctx *c, const char *text, int64_t text_bytes, int3
     if (!ee || !ns || !pass) return fail(MPB_E_INVALID, "NULL host buffer");
     if ((rc = check_fastq_offset(fastq_offset))) return rc;
     CTXCHK(c);
+    resident_drop(c);
     *n = 0; *consumed = 0; *bad_kind = 0;
     if (counts) memset(counts, 0, sizeof(*counts));
     Indexed in;

@@ -300,6 +300,18 @@ void mpb_launch_pair_rows(const int64_t *fidx, const int64_t *ridx, int64_t m, c
 void mpb_launch_pair_count(const mpb_pair_row *rows, const int8_t *cls, int64_t n, uint32_t *table, uint32_t *prefix, uint32_t *head,
                            int64_t *status, hipStream_t s);
 void mpb_launch_pair_lists(const int8_t *cls, int64_t n, const uint32_t *prefix, const uint32_t *head, int32_t *list, hipStream_t s);
+// The writer's formatter on the device (mpb_format_kernels.hip; what a lane does, FmParams and the blob: mpb_format_lane.inc).
+// Records sel[k] (null: k), k < nsel, of idx[p.n_records][6] over text[p.text_bytes] (an allocation rounded up to 16 bytes); the
+// rows, sel, relabel_index and label_id are not trusted.  k_fmt_count + k_fmt_scan: size[nsel], prefix[nsel + 1], head[0] = the
+// bytes of the formatted text; status[0] (set to INT64_MAX by the caller) = the first k whose row fails a check.  k_fmt_write:
+// records k0..k1-1, clipped to bytes [win_lo, win_hi) of the formatted text, into out[win_hi - win_lo]; nothing when status[0] is set.
+struct FmParams;
+void mpb_launch_fmt_count(const uint8_t *text, const int64_t *idx, const int64_t *sel, const int64_t *relabel_index,
+                          const int32_t *label_id, int64_t nsel, const FmParams &p, int64_t *size, int64_t *prefix, int64_t *head,
+                          int64_t *status, hipStream_t s);
+void mpb_launch_fmt_write(const uint8_t *text, const uint8_t *blob, const int64_t *idx, const int64_t *sel,
+                          const int64_t *relabel_index, const int32_t *label_id, int64_t k0, int64_t k1, const FmParams &p,
+                          const int64_t *prefix, const int64_t *status, int64_t win_lo, int64_t win_hi, uint8_t *out, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

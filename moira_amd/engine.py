@@ -80,11 +80,19 @@ class NotTaken(Exception):
 
 class FastqFilterResult(TextFilterResult):
     """TextFilterResult of Engine.filter_fastq, with the record index the device built next to it: idx, consumed, bad as
-    fastio.index returns them."""
+    fastio.index returns them.  .resident: the generation of the text and index the call left on the device
+    (Engine.format_text(resident=...)); 0 when there is none."""
 
     def __init__(self, idx, consumed, bad, *a):
         TextFilterResult.__init__(self, *a)
         self.idx, self.consumed, self.bad = idx, consumed, bad
+        self.resident = 0
+
+
+class NotResident(Exception):
+    """Engine.format_text(resident=g): g is not the generation of the text the context holds -- a later call of filter_fastq,
+    filter_bgzf_fastq, fastq_index or contigs_filter_fastq has replaced or dropped it.  Nothing was touched: the caller formats
+    on the host (fastio.format_records) or from an upload."""
 
 
 class MembersNotTaken(Exception):
@@ -525,7 +533,9 @@ class Engine:
         _check_text(rc, badrec)
         if why:
             raise NotTaken(why)
-        return FastqFilterResult(idx[:n], consumed, _record_error(buf, idx, n, bad), *r.cut(n), counts.n_pass, counts.n_overflow)
+        res = FastqFilterResult(idx[:n], consumed, _record_error(buf, idx, n, bad), *r.cut(n), counts.n_pass, counts.n_overflow)
+        res.resident = self.resident_text()
+        return res
 
     # ---- BGZF FASTQ filtered where it inflates (k_bgzf_inflate, k_bgzf_crc32, the index, the pack) ----
     def crc32_ranges(self, buf, offs, lens):
@@ -596,8 +606,82 @@ class Engine:
             raise NotTaken(why.value)
         n = n.value
         tout = tbuf[:total] if text else None
-        return BgzfFastqFilterResult(tout, stats, idx[:n], consumed.value, _record_error(tout, idx, n, bad.value), *r.cut(n),
-                                     counts.n_pass, counts.n_overflow)
+        res = BgzfFastqFilterResult(tout, stats, idx[:n], consumed.value, _record_error(tout, idx, n, bad.value), *r.cut(n),
+                                    counts.n_pass, counts.n_overflow)
+        res.resident = self.resident_text()
+        return res
+
+    # ---- output records formatted on the device (k_fmt_count, k_fmt_scan, k_fmt_write) -------------
+    def resident_text(self):
+        """The generation of the text and index the last filter_fastq / filter_bgzf_fastq call left on the device; 0: none."""
+        return int(self.lib.mpb_resident_text(self.ctx))
+
+    def format_text(self, buf=None, idx=None, sel=None, kind=2, resident=None, bgzf=False, fastq_offset=33, max_len=0, relabel=None,
+                    relabel_index=None, labels=None, label_id=None, out_offset=None, clamp_q0=True):
+        """Records sel (None: all) of a text and its record index as fasta (kind 0), qual (1) or fastq (2) text, formatted on
+        the device (mpb_format_text_host): byte for byte fastio.format_records' on the same arguments (its `ee` is not offered).
+        buf + idx: the text and index go up once.  resident=g (a filter result's .resident; buf None): the text and index that
+        call left on the device are read where they lie; idx is then the result's .idx, used for the record count and to size
+        the output only.  -> bytes; with bgzf=True a uint8 array of the BGZF members of that text, compressed where it lies,
+        without the end marker -- the bytes bgzf_compress returns for it (the counts: bgzf_stats()).
+        NotResident for a generation that is no longer in force; ValueError with .bad_record = k for a selected record whose
+        row, sel, relabel_index or label_id entry fails a check (nothing is written then)."""
+        if idx is None:
+            raise ValueError("format_text: idx is needed (resident form: the filter result's .idx)")
+        idx, sel, nsel = _index_args(idx, sel)
+        if resident is None or not resident:
+            if buf is None:
+                raise ValueError("format_text: either buf and idx or resident")
+            keep, addr, nbytes = _text_ptr(buf)
+            gen = 0
+        else:
+            if buf is not None:
+                raise ValueError("format_text: either buf and idx or resident, not both")
+            keep, addr, nbytes, gen = None, None, 0, int(resident)
+        if relabel is not None:
+            relabel = relabel.encode() if isinstance(relabel, str) else bytes(relabel)
+            if relabel_index is None:
+                raise ValueError("format_text: relabel without relabel_index")
+            relabel_index = np.ascontiguousarray(relabel_index, np.int64).reshape(-1)
+            if len(relabel_index) != nsel:
+                raise ValueError("format_text: relabel_index must hold one entry per selected record")
+        enc, lab_arr = [], None
+        if label_id is not None:
+            label_id = np.ascontiguousarray(label_id, np.int32).reshape(-1)
+            if len(label_id) != nsel:
+                raise ValueError("format_text: label_id must hold one entry per selected record")
+            enc = [t.encode() if isinstance(t, str) else bytes(t) for t in (labels or [])]
+            lab_arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        # an upper bound of the formatted text from the index: the call never has to be made twice
+        n = len(idx)
+        rows = idx if sel is None else idx[sel[(sel >= 0) & (sel < n)]]
+        lens = np.clip(rows[:, 3], 0, 1 << 31)
+        if max_len > 0:
+            lens = np.minimum(lens, int(max_len))
+        body = {0: lens + 1, 1: 4 * lens + 1, 2: 2 * lens + 4}.get(int(kind), lens)
+        head = (len(relabel) + 20) if relabel is not None else np.clip(rows[:, 1], 0, 1 << 31)
+        bound = int(np.sum(body + head)) + nsel * (3 + max([len(t) for t in enc] + [0]))
+        cap = C.c_int64(bound)
+        if bgzf:
+            L.check(self.lib.mpb_bgzf_bound(bound, C.byref(cap)))
+        out = np.empty(max(cap.value, 1), np.uint8)
+        got, needed, bad, st = C.c_int64(0), C.c_int64(0), C.c_int64(-1), L.BgzfStats()
+        off = int(fastq_offset)
+        rc = self.lib.mpb_format_text_host(
+            self.ctx, addr, nbytes, idx.ctypes.data if not gen else None, n, gen, sel.ctypes.data if sel is not None else None, nsel,
+            int(kind), off, off if out_offset is None else int(out_offset), 1 if clamp_q0 else 0, int(max_len),
+            relabel,
+            relabel_index.ctypes.data if relabel is not None else None, C.cast(lab_arr, C.c_void_p) if lab_arr is not None else None,
+            len(enc), label_id.ctypes.data if label_id is not None else None, 1 if bgzf else 0, out.ctypes.data, cap.value,
+            C.byref(got), C.byref(needed), C.byref(bad), C.byref(st))
+        del keep
+        if rc == L.E_INVALID and b"is not resident" in self.lib.mpb_last_error():
+            raise NotResident(self.lib.mpb_last_error().decode(errors="replace"))
+        _check_text(rc, bad)
+        if bgzf:
+            self._bgzf_stats = {k: int(getattr(st, k)) for k, _ in L.BgzfStats._fields_}
+            return out[:got.value]
+        return out[:got.value].tobytes()
 
     # ---- paired-read contigs on the device (mpb_pair_rows, k_contig) ------------------------------
     @staticmethod
