@@ -208,6 +208,20 @@ int32_t mio_collapse_set_threads(mio_collapse *c, int32_t threads);
 int32_t mio_collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, int64_t n, int32_t max_len,
                          const double *ee, const uint8_t *flags, const int32_t *aux);
 
+/* mio_collapse_add with part of its work done elsewhere (mpb_collapse_text_host computes both on the device): hash
+ * uint64[n] = mio_py2_hash's value of every record, rep int32[n] = for every record an earlier record of THIS chunk
+ * with the same (truncated) sequence, or k itself.  The effect on the object is identical to mio_collapse_add's on the
+ * same chunk; nothing is hashed, and a record with rep[k] != k is neither looked up nor compared: it takes the group
+ * its representative found.  A record with rep[k] == k is looked up as ever (its group may come from an earlier
+ * chunk), so a duplicate that rep[] misses costs only time.
+ * The result is correct iff hash[] is right and rep[k] != k implies equal bytes.
+ * Checked before anything is changed (MIO_E_INVALID, the object untouched): 0 <= rep[k] <= k, rep[rep[k]] == rep[k],
+ * hash[k] == hash[rep[k]], equal truncated lengths.  verify != 0: also every hash is computed again and every
+ * duplicate compared with its representative (MIO_E_INVALID on a difference, the object untouched). */
+int32_t mio_collapse_add_grouped(mio_collapse *c, const char *buf, const int64_t *idx, int64_t n, int32_t max_len,
+                                 const double *ee, const uint8_t *flags, const int32_t *aux, const uint64_t *hash,
+                                 const int32_t *rep, int32_t verify);
+
 /* Fix the output order (moira/moira.py:492) and copy out, in that order, per group: the
  * representative's ee, the sequence length, the abundance, the flags and aux[.][3] (any pointer may be
  * NULL). */

@@ -789,6 +789,31 @@ int mpb_format_text_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, con
 int64_t mpb_resident_text(mpb_ctx *ctx);
 
 /*
+ * The data-parallel part of the collapse of identical sequences, on the device (k_col_hash, k_col_group, k_col_rep;
+ * csrc/mpb_collapse_kernels.hip).  For records k < n_records of a text and its record index idx[n_records][MPB_IDX_COLS] the
+ * sequence is text[SEQ_OFF, SEQ_OFF + L), L = SEQ_LEN, or min(SEQ_LEN, max_len) when max_len > 0 -- mio_collapse_add's.
+ *   hash[k]   uint64: what mio_py2_hash (include/moira_io.h) returns for that sequence, the CPython-2.7 string hash
+ *   rep[k]    int32: the smallest k' <= k whose sequence has the same bytes (k itself for the first of its kind)
+ * Both are what mio_collapse_add_grouped takes; neither depends on how the device schedules its lanes.
+ * UPLOADED FORM (resident == 0): text[text_bytes] (at most 1 GiB) and idx go up once; any buffer and index of that layout do.
+ * The rows are validated on the host first -- the sequence's offset and length non-negative, the range inside the text -- and a
+ * bad one is MPB_E_INVALID with *bad_record = k before anything is uploaded; the kernel makes the same check again.
+ * RESIDENT FORM (resident != 0; text and idx NULL): the text and the device-written index that the last successful
+ * mpb_filter_fastq_host or mpb_filter_bgzf_fastq_host call of this context left on the device are read where they lie;
+ * n_records is that call's *n; the generations are mpb_format_text_host's (above), and so is what ends one.  A `resident` that
+ * is not the generation in force is MPB_E_INVALID with a message that holds "is not resident", and nothing is touched.  This
+ * call does not end the generation: a format call and a collapse call may follow each other on it in either order.  A
+ * device-written row that fails the kernel's check is never expected: MPB_E_INVALID with *bad_record.
+ * Argument errors (said before the context is looked at) are MPB_E_INVALID: a NULL where a pointer is needed (bad_record;
+ * hash and rep when n_records > 0), a negative size or max_len, n_records above 2^31 - 1, both or neither of text / idx and
+ * resident.  n_records == 0 succeeds and writes nothing.
+ * The three kernels have no MPB_K_* id: they are timed under MPB_K_PACK_TEXT, as the formatter's.  Synchronous; the staging
+ * block (hashes, 2^ceil(log2(2 n)) owner slots and their first records, the slot of every record) belongs to the context.
+ */
+int mpb_collapse_text_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, const int64_t *idx, int64_t n_records,
+                           int64_t resident, int32_t max_len, uint64_t *hash, int32_t *rep, int64_t *bad_record);
+
+/*
  * The same batch call over SEVERAL contexts (normally one per GPU of the node) from one host process: the batch is
  * cut into n_ctx contiguous, balanced shards in read order, one host thread per context runs mpb_filter_host
  * (poisson == 0) or mpb_filter_poisson_host (poisson != 0) on its shard, and every shard's results land in the

@@ -726,13 +726,22 @@ int32_t mio_collapse_set_threads(mio_collapse *c, int32_t threads)
     return MIO_OK;
 }
 
-int32_t mio_collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, int64_t n, int32_t max_len,
-                         const double *ee, const uint8_t *flags, const int32_t *aux)
+namespace {
+
+// mio_collapse_add (given == NULL: the hashes are computed here, every record is looked up) and mio_collapse_add_grouped (given,
+// rep: checked by the caller; a record with rep[k] != k takes the group record rep[k] found -- same hash, so same shard, same
+// filling thread, and met earlier in file order: uid_of[] is written before it is read)
+int32_t collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, int64_t n, int32_t max_len, const double *ee,
+                     const uint8_t *flags, const int32_t *aux, const uint64_t *given, const int32_t *rep)
 {
-    if (!c || !buf || !idx || n < 0 || (n > 0 && !ee)) return fail(MIO_E_INVALID, "mio_collapse_add: bad arguments");
     c->exported = false;
-    std::vector<uint64_t> hashes;
-    try { hashes.resize((size_t)n); } catch (const std::bad_alloc &) { return fail(MIO_E_INVALID, "out of memory while collapsing"); }
+    std::vector<uint64_t> own;
+    std::vector<int64_t> uid_of;                              // the group of record k, for the records that are representatives
+    try {
+        if (!given) own.resize((size_t)n);
+        if (rep) uid_of.resize((size_t)n);
+    } catch (const std::bad_alloc &) { return fail(MIO_E_INVALID, "out of memory while collapsing"); }
+    uint64_t *hashes = own.data();
     auto seq_of = [&](int64_t k, int64_t *L) {
         const int64_t *r = idx + k * MIO_IDX_COLS;
         *L = r[MIO_SEQ_LEN];
@@ -768,7 +777,7 @@ int32_t mio_collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, i
     auto fill = [&](int t) {
         try {
             for (int64_t k = 0; k < n; k++) {
-                const uint64_t h = hashes[(size_t)k];
+                const uint64_t h = given ? given[k] : hashes[(size_t)k];
                 const int sid = mio_collapse::shard_of(h);
                 if (sid % T != t) continue;
                 mio_collapse::Shard &S = c->shard[sid];
@@ -784,7 +793,9 @@ int32_t mio_collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, i
                 const int64_t name_id = (int64_t)S.names.size();
                 S.names.push_back({hoff, (int32_t)hl, -1});
                 uint64_t slot = 0;
-                const int64_t hit = S.find(h, seq, L, &slot);
+                const bool dup = rep && rep[k] != k;
+                const int64_t hit = dup ? uid_of[(size_t)rep[k]] : S.find(h, seq, L, &slot);
+                if (rep && !dup) uid_of[(size_t)k] = hit < 0 ? (int64_t)S.uniq.size() : hit;
                 if (hit < 0) {                                                          // moira.py:461-464
                     mio_collapse::Uniq u;
                     u.seq_off = S.put(seq, L);
@@ -827,7 +838,7 @@ int32_t mio_collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, i
     };
     int64_t before[mio_collapse::NSHARD];
     for (int sid = 0; sid < mio_collapse::NSHARD; sid++) before[sid] = (int64_t)c->shard[sid].uniq.size();
-    run([&](int t) { hash_range(n / T * t, t == T - 1 ? n : n / T * (t + 1)); });
+    if (!given) run([&](int t) { hash_range(n / T * t, t == T - 1 ? n : n / T * (t + 1)); });
     run(fill);
     c->reads_seen += n;
     for (int t = 0; t < T; t++)
@@ -851,6 +862,44 @@ int32_t mio_collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, i
         return fail(MIO_E_INVALID, "out of memory while collapsing");
     }
     return MIO_OK;
+}
+
+}  // namespace
+
+int32_t mio_collapse_add(mio_collapse *c, const char *buf, const int64_t *idx, int64_t n, int32_t max_len,
+                         const double *ee, const uint8_t *flags, const int32_t *aux)
+{
+    if (!c || !buf || !idx || n < 0 || (n > 0 && !ee)) return fail(MIO_E_INVALID, "mio_collapse_add: bad arguments");
+    return collapse_add(c, buf, idx, n, max_len, ee, flags, aux, nullptr, nullptr);
+}
+
+int32_t mio_collapse_add_grouped(mio_collapse *c, const char *buf, const int64_t *idx, int64_t n, int32_t max_len,
+                                 const double *ee, const uint8_t *flags, const int32_t *aux, const uint64_t *hash,
+                                 const int32_t *rep, int32_t verify)
+{
+    if (!c || !buf || !idx || n < 0 || n > INT32_MAX || (n > 0 && (!ee || !hash || !rep)))
+        return fail(MIO_E_INVALID, "mio_collapse_add_grouped: bad arguments");
+    auto len_of = [&](int64_t k) {
+        const int64_t L = idx[k * MIO_IDX_COLS + MIO_SEQ_LEN];
+        return max_len > 0 && L > max_len ? (int64_t)max_len : L;
+    };
+    // everything is checked before anything is changed
+    for (int64_t k = 0; k < n; k++) {
+        const int64_t r = rep[k];
+        if (r < 0 || r > k) return fail(MIO_E_INVALID, "mio_collapse_add_grouped: rep[%lld] = %lld is not in 0..%lld", (long long)k, (long long)r, (long long)k);
+        if (rep[r] != r) return fail(MIO_E_INVALID, "mio_collapse_add_grouped: rep[%lld] = %lld is no representative", (long long)k, (long long)r);
+        if (hash[k] != hash[r]) return fail(MIO_E_INVALID, "mio_collapse_add_grouped: records %lld and %lld of one group differ in hash", (long long)k, (long long)r);
+        if (len_of(k) != len_of(r)) return fail(MIO_E_INVALID, "mio_collapse_add_grouped: records %lld and %lld of one group differ in length", (long long)k, (long long)r);
+    }
+    if (verify)
+        for (int64_t k = 0; k < n; k++) {
+            const int64_t L = len_of(k);
+            const unsigned char *s = (const unsigned char *)buf + idx[k * MIO_IDX_COLS + MIO_SEQ_OFF];
+            if (rep[k] != k && L > 0 && memcmp(s, buf + idx[(int64_t)rep[k] * MIO_IDX_COLS + MIO_SEQ_OFF], (size_t)L) != 0)
+                return fail(MIO_E_INVALID, "mio_collapse_add_grouped: records %lld and %lld of one group differ in sequence", (long long)k, (long long)rep[k]);
+            if (py2_hash(s, L) != hash[k]) return fail(MIO_E_INVALID, "mio_collapse_add_grouped: hash[%lld] is not the sequence's", (long long)k);
+        }
+    return collapse_add(c, buf, idx, n, max_len, ee, flags, aux, hash, rep);
 }
 
 int32_t mio_collapse_export(mio_collapse *c, double *ee, int64_t *len, int64_t *size, uint8_t *flags, int32_t *aux)

@@ -115,6 +115,7 @@ struct PinWords {
     int64_t pair_status[4];                              // ... k_pair_rows' / k_pair_count's status, both ways
     uint32_t pair_head[MPB_PAIR_HEAD_WORDS];             // ... k_pair_scan's head words: the pairs per class, the classes' first places
     int64_t fmt_words[2];                                // mpb_format_text_host: k_fmt_count's status, both ways; k_fmt_scan's head word
+    int64_t col_status[2];                               // mpb_collapse_text_host: k_col_hash's status, both ways
 };
 
 struct TimedSpan { int kid; hipEvent_t a, b; };
@@ -190,6 +191,7 @@ struct mpb_ctx {
                                          // (mpb_contigs_filter_fastq_host: both texts' shares of either block, one carve each, and the pairing block)
     Buf format_stage{BUF_DEVICE};        // mpb_format_text_host: text | index | sel | relabel_index | label_id | blob | sizes | prefix | words | one piece
     Buf format_out{BUF_DEVICE};          // ... one window of the formatted text, or the CRC ranges of one piece of its members
+    Buf collapse_stage{BUF_DEVICE};      // mpb_collapse_text_host: text | index (the uploaded form's) | hash | slot | rep | status | table | first
     // the text and index the last successful mpb_filter_fastq_host / mpb_filter_bgzf_fastq_host call left in the two blocks above
     // (mpb_format_text_host's resident form); gen == 0: none
     struct ResidentText {

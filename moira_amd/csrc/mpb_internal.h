@@ -312,6 +312,13 @@ void mpb_launch_fmt_count(const uint8_t *text, const int64_t *idx, const int64_t
 void mpb_launch_fmt_write(const uint8_t *text, const uint8_t *blob, const int64_t *idx, const int64_t *sel,
                           const int64_t *relabel_index, const int32_t *label_id, int64_t k0, int64_t k1, const FmParams &p,
                           const int64_t *prefix, const int64_t *status, int64_t win_lo, int64_t win_hi, uint8_t *out, hipStream_t s);
+// The data-parallel part of collapse (mpb_collapse_kernels.hip; what a lane does and ClParams: mpb_collapse_lane.inc).  Records
+// k < p.n_records of idx[.][6] over text[p.text_bytes] (an allocation rounded up to 16 bytes; the rows are not trusted): k_col_hash
+// -> hash[n] and status[0] (set to INT64_MAX by the caller) = the first k whose row fails its check; k_col_group over table[p.cap]
+// (every byte 0xFF: empty) and first[p.cap] (every byte 0xFF) -> slot[n]; k_col_rep -> rep[n].  With status[0] set, rep[k] = k.
+struct ClParams;
+void mpb_launch_collapse(const uint8_t *text, const int64_t *idx, const ClParams &p, uint64_t *hash, int32_t *table, uint32_t *first,
+                         int64_t *slot, int32_t *rep, int64_t *status, hipStream_t s);
 void mpb_launch_synth(uint8_t *q, int64_t n, int64_t stride, int32_t fixed_len, int32_t min_len,
                       int32_t max_len, int32_t *len, uint64_t seed, int64_t first_read,
                       hipStream_t s, int32_t profile = 0);

@@ -31,6 +31,10 @@ struct StreamQueue {
     {
         if (bytes > 0 && ok()) { pending = true; kept = hipMemsetAsync(dst, 0, (size_t)bytes, c->stream); }
     }
+    void ones(void *dst, int64_t bytes)                  // every byte 0xFF
+    {
+        if (bytes > 0 && ok()) { pending = true; kept = hipMemsetAsync(dst, 0xFF, (size_t)bytes, c->stream); }
+    }
     // the launches of fn() (one launch wrapper or several) inside one timing span of kernel id `kid`
     template <typename Fn> void run(int kid, Fn &&fn)
     {

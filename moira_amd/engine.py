@@ -683,6 +683,36 @@ class Engine:
             return out[:got.value]
         return out[:got.value].tobytes()
 
+    # ---- the data-parallel part of collapse on the device (k_col_hash, k_col_group, k_col_rep) -----
+    def collapse_text(self, buf=None, idx=None, resident=None, n=None, max_len=0):
+        """For every record of a text and its record index: the CPython-2.7 hash of its (truncated) sequence and the first record
+        of the chunk with the same sequence (mpb_collapse_text_host) -> (hash uint64[n], rep int32[n]), what
+        fastio.Collapse.add(hash=, rep=) takes.  buf + idx: both go up once.  resident=g (a filter result's .resident; buf
+        None): the text and index that call left on the device are read where they lie; the record count is n, or len(idx)
+        of the result's .idx.  The generation stays in force.  NotResident for a generation that no longer is; ValueError
+        with .bad_record = k for a record whose sequence range does not lie inside the text."""
+        if resident is None or not resident:
+            if buf is None or idx is None:
+                raise ValueError("collapse_text: either buf and idx or resident")
+            idx = np.ascontiguousarray(idx, np.int64)
+            if idx.ndim != 2 or idx.shape[1] != 6:
+                raise ValueError("collapse_text: idx must be an (n x 6) int64 record index")
+            keep, addr, nbytes, gen, count = *_text_ptr(buf), 0, len(idx)
+        else:
+            if buf is not None:
+                raise ValueError("collapse_text: either buf and idx or resident, not both")
+            if n is None and idx is None:
+                raise ValueError("collapse_text: the resident form needs n (or the filter result's .idx)")
+            keep, addr, nbytes, gen, count = None, None, 0, int(resident), int(len(idx) if n is None else n)
+        hash_, rep, bad = np.empty(count, np.uint64), np.empty(count, np.int32), C.c_int64(-1)
+        rc = self.lib.mpb_collapse_text_host(self.ctx, addr, nbytes, idx.ctypes.data if not gen else None, count, gen, int(max_len),
+                                             hash_.ctypes.data, rep.ctypes.data, C.byref(bad))
+        del keep
+        if rc == L.E_INVALID and b"is not resident" in self.lib.mpb_last_error():
+            raise NotResident(self.lib.mpb_last_error().decode(errors="replace"))
+        _check_text(rc, bad)
+        return hash_, rep
+
     # ---- paired-read contigs on the device (mpb_pair_rows, k_contig) ------------------------------
     @staticmethod
     def pair_rows(fidx, ridx, ftext_bytes, rtext_bytes, rec_cap):

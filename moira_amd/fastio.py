@@ -54,6 +54,8 @@ PROTOTYPES = {
     "mio_collapse_set_threads": (C.c_int32, [C.c_void_p, C.c_int32]),
     "mio_collapse_add": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "mio_collapse_add_grouped": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "mio_collapse_export": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mio_format_report": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -298,12 +300,26 @@ class Collapse:
     def __len__(self):
         return self.lib.mio_collapse_count(self.h)
 
-    def add(self, buf, idx, ee, flags, max_len=0, aux=None):
+    def add(self, buf, idx, ee, flags, max_len=0, aux=None, hash=None, rep=None, verify=False):
+        """A chunk's records in file order.  hash uint64[n] and rep int32[n] (both or neither; Engine.collapse_text makes them
+        on the device): the same effect with no hashing and no look-up of a record whose rep is an earlier one
+        (mio_collapse_add_grouped); verify: every hash and every duplicate is checked again on the host first."""
         idx = np.ascontiguousarray(idx)
         ee = np.ascontiguousarray(ee, np.float64)
         flags = np.ascontiguousarray(flags, np.uint8)
         if aux is not None:
             aux = np.ascontiguousarray(aux, np.int32)
+        if (hash is None) != (rep is None):
+            raise ValueError("Collapse.add: hash and rep come together")
+        if hash is not None:
+            hash, rep = np.ascontiguousarray(hash, np.uint64), np.ascontiguousarray(rep, np.int32)
+            if len(hash) != len(idx) or len(rep) != len(idx):
+                raise ValueError("Collapse.add: hash and rep have one entry per record")
+            if self.lib.mio_collapse_add_grouped(self.h, _ptr(buf), idx.ctypes.data, len(idx), int(max_len), ee.ctypes.data,
+                                                 flags.ctypes.data, aux.ctypes.data if aux is not None else None,
+                                                 hash.ctypes.data, rep.ctypes.data, 1 if verify else 0):
+                raise ValueError(_err())
+            return
         if self.lib.mio_collapse_add(self.h, _ptr(buf), idx.ctypes.data, len(idx), int(max_len), ee.ctypes.data,
                                      flags.ctypes.data, aux.ctypes.data if aux is not None else None):
             raise ValueError(_err())
