@@ -492,6 +492,64 @@ int mpb_filter_fastq_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, in
                           mpb_filter_counts *counts, int64_t *bad_record);
 
 /*
+ * fasta+qual input on the device (opt-in; the default stays mio_fasta_qual_index of libmoira_io.so, which is the yardstick and the
+ * only code that defines an error): a chunk of FASTA TEXT and a chunk of QUAL TEXT, in host memory, are uploaded once.  Both go
+ * through the record index's line kernels (newlines per tile, their prefix, the line starts); record r is lines 2 r and 2 r + 1
+ * of each, and the record stage (k_fa_count, k_fa_scan, k_fa_write; csrc/mpb_fasta_qual_kernels.hip) builds the buffer of slots
+ * `header token | sequence | one byte per quality` and the six-column index over it.
+ *   ftext / qtext      each at most 1 GiB           final, max_records, max_len     as mpb_fastq_index_host's, for both texts
+ *   out, out_cap       the slots (at most 1 GiB); records are taken while their slots end at or before out_cap
+ *   idx_out            int64[idx_cap_rows][MPB_IDX_COLS], offsets relative to out
+ * WHEN THE DEVICE TAKES THE TEXTS (*why == 0): *n, *f_consumed, *q_consumed, *out_used, out[0, *out_used) and rows [0, *n) of
+ * idx_out equal mio_fasta_qual_index(ftext, ..., qtext, ..., final, max_records, out, out_cap, ...)'s, bit for bit.  The
+ * candidate records are min(max_records, lines of ftext / 2, lines of qtext / 2) (an unterminated last line counts only when
+ * final); *n is the candidates that fit out_cap.
+ * WHEN IT DOES NOT, *why says why, *which the text (0 fasta, 1 qual), *bad_record the first offending record where there is one
+ * (else -1), and NOTHING ELSE is defined; the caller runs the host function.  MPB_FQ_WHY_NON_ASCII / LONE_CR / LINE_TABLE /
+ * ROW_CHECK as above, and
+ *   MPB_FA_WHY_NAMES      the header tokens of a record differ         MPB_FA_WHY_EMPTY   an empty sequence or quality line
+ *   MPB_FA_WHY_TOKEN      a quality line that is not 1-3 digit tokens of at most 254 with single blanks or tabs between them
+ *   MPB_FA_WHY_LENGTH     the tokens of a quality line are not as many as the bases
+ *   MPB_FA_WHY_TRUNCATED  final, fewer than max_records candidates, and a text has lines left over
+ * All or nothing: one such record among the candidates hands the whole call back, as the host returns MIO_E_UNSUPPORTED for the
+ * whole call.  The device looks at every candidate, also behind the last that fits, and does not take a token of more than three
+ * digits ("0007", which the host reads): it refuses a superset of what the host refuses, never takes texts the host would not,
+ * and never returns anything the host would not return.  A problem in the texts' content never fails the call.
+ * Argument errors are MPB_E_INVALID, said with or without a device: a NULL pointer, a negative size, a text or out_cap above
+ * 1 GiB, and an idx_cap_rows below the candidates -- known once the lines are counted; *n then holds their number, so that a
+ * caller who guessed may ask again.  Device memory is sized from the counted lines (one small read-back after the scan).  The
+ * three kernels have no MPB_K_* id: they are timed under MPB_K_FQ_ROWS.  Synchronous; the staging blocks belong to the context
+ * (the record index's two), so this call ends a resident generation as mpb_fastq_index_host does.
+ */
+#define MPB_FA_WHY_NAMES     5
+#define MPB_FA_WHY_EMPTY     6
+#define MPB_FA_WHY_TOKEN     7
+#define MPB_FA_WHY_LENGTH    8
+#define MPB_FA_WHY_TRUNCATED 9
+int mpb_fasta_qual_index_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_bytes, const char *qtext, int64_t qtext_bytes, int32_t final,
+                              int64_t max_records, int32_t max_len, uint8_t *out, int64_t out_cap, int64_t *idx_out, int64_t idx_cap_rows,
+                              int64_t *n, int64_t *f_consumed, int64_t *q_consumed, int64_t *out_used, int32_t *why, int32_t *which,
+                              int64_t *bad_record);
+
+/*
+ * Two texts in, slots, index and results out: mpb_fasta_qual_index_host's buffer and mpb_filter_text_host's filter from ONE
+ * upload.  {n, first record not taken, longest packed length} are read back; the matrix is laid out at
+ * round_up(max(longest, 1), 128); records 0..n-1 are packed and filtered piece by piece from the device-written descriptors over
+ * the slots with FASTQ offset 0 (mpb_filter_text_host's piece loop, MPB_TEXT_PIECE_BYTES included); results, index and slots are
+ * copied back (out may be NULL here: no slots come back).  ee, ns, pass, len_out, flags_out hold idx_cap_rows entries (len_out,
+ * flags_out, counts and bad_pack_record may be NULL).  *why != 0: handed back as above, and nothing was filtered.  Otherwise the
+ * results are bit-identical to mio_fasta_qual_index + mpb_filter_text_host(fastq_offset = 0) on the same texts.  The slots and
+ * their index stay on the device as the resident text of a new generation: mpb_format_text_host and mpb_collapse_text_host take
+ * them by `resident`, exactly as after mpb_filter_fastq_host.
+ */
+int mpb_filter_fasta_qual_host(mpb_ctx *ctx, const char *ftext, int64_t ftext_bytes, const char *qtext, int64_t qtext_bytes, int32_t final,
+                               int64_t max_records, int32_t max_len, uint8_t *out, int64_t out_cap, int64_t *idx_out,
+                               int64_t idx_cap_rows, int64_t *n, int64_t *f_consumed, int64_t *q_consumed, int64_t *out_used,
+                               int32_t *why, int32_t *which, int64_t *bad_record, int32_t lower_n_is_base,
+                               const mpb_filter_params *params, int32_t poisson, double *ee, int32_t *ns, uint8_t *pass,
+                               int32_t *len_out, uint8_t *flags_out, mpb_filter_counts *counts, int64_t *bad_pack_record);
+
+/*
  * Paired-read contigs on the device (opt-in; the default builder stays mct_contigs_from_fastq of libmoira_contig.so): the
  * Needleman-Wunsch fill, the traceback and the consensus of a chunk of read pairs that are still FASTQ text, one wave per pair
  * (k_contig, csrc/mpb_contig_kernels.hip).  The contract is BYTE IDENTITY with mct_contigs_from_fastq on every pair the device
@@ -759,12 +817,13 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *ctx, const char *carry, int64_t carry_le
  * relabel_index[k] >= 0, label_id[k] < n_labels -- and a bad one is MPB_E_INVALID with *bad_record = k before anything is
  * uploaded; the kernels make the same checks again.
  * RESIDENT FORM (resident != 0; text and idx NULL): the text and the device-written index that the last successful
- * mpb_filter_fastq_host or mpb_filter_bgzf_fastq_host call of this context left on the device are read where they lie (for the
+ * mpb_filter_fastq_host, mpb_filter_bgzf_fastq_host or mpb_filter_fasta_qual_host call of this context left on the device are
+ * read where they lie (for the
  * BGZF call: carry + members' text, as its index counts); n_records is that call's *n.  The context numbers these texts:
  * mpb_resident_text returns the generation in force (1, 2, ...), 0 for none.  Every successful call of the two makes a new one.
  * The generation is set to none by every call that may move, grow, overwrite or free the blocks the text and index lie in,
  * whether it succeeds, fails or hands its text back: mpb_fastq_index_host, mpb_filter_fastq_host, mpb_filter_bgzf_fastq_host,
- * mpb_contigs_filter_fastq_host and mpb_destroy.  No other call touches them.  A `resident` that is not the generation in force
+ * mpb_contigs_filter_fastq_host, mpb_fasta_qual_index_host, mpb_filter_fasta_qual_host and mpb_destroy.  No other call touches them.  A `resident` that is not the generation in force
  * is MPB_E_INVALID with a message that holds "is not resident", and nothing is touched.  Only sel, relabel_index, label_id and
  * the strings go up (the compressed form adds 16 bytes per member).  A device-written row that fails the kernel's check is never
  * expected: MPB_E_INVALID with *bad_record.

@@ -40,6 +40,9 @@ INFLATE_KERNEL_NAMES = {K_BGZF_INFLATE: "bgzf_inflate"}
 K_FQ_LINES, K_FQ_SCAN, K_FQ_STARTS, K_FQ_ROWS = 18, 19, 20, 21     # MPB_K_FQ_*: the FASTQ record index on the device
 INDEX_KERNEL_NAMES = {K_FQ_LINES: "fq_lines", K_FQ_SCAN: "fq_scan", K_FQ_STARTS: "fq_starts", K_FQ_ROWS: "fq_rows"}
 FQ_WHY = ("taken", "non-ASCII byte", "lone carriage return", "line table", "row check")     # MPB_FQ_WHY_*
+FA_WHY_NAMES, FA_WHY_EMPTY, FA_WHY_TOKEN, FA_WHY_LENGTH, FA_WHY_TRUNCATED = 5, 6, 7, 8, 9     # MPB_FA_WHY_*: fasta+qual input on the device
+FA_WHY = FQ_WHY + ("header tokens differ", "empty sequence or quality line", "quality token", "qualities and bases differ in number",
+                   "truncated record at the end of the files")
 BGZF_WHY = ("ok", "header", "block type", "stored length", "code-length code", "repeat", "tree", "symbol", "distance", "overrun",
             "short", "truncated", "trailing bytes", "crc")     # MPB_BGZF_WHY_*
 BGZF_DATA = 0xff00             # MPB_BGZF_DATA: text bytes per BGZF member
@@ -137,6 +140,13 @@ PROTOTYPES = {
                                         C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.c_int32, C.c_int32, C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP,
                                         C.POINTER(FilterCounts), C.POINTER(C.c_int64)]),
+    "mpb_fasta_qual_index_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _VP, C.c_int64, _VP,
+                                            C.c_int64] + [C.POINTER(C.c_int64)] * 4 + [C.POINTER(C.c_int32)] * 2 +
+                                  [C.POINTER(C.c_int64)]),
+    "mpb_filter_fasta_qual_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _VP, C.c_int64, _VP,
+                                             C.c_int64] + [C.POINTER(C.c_int64)] * 4 + [C.POINTER(C.c_int32)] * 2 +
+                                   [C.POINTER(C.c_int64), C.c_int32, C.POINTER(FilterParams), C.c_int32, _VP, _VP, _VP, _VP, _VP,
+                                    C.POINTER(FilterCounts), C.POINTER(C.c_int64)]),
     "mpb_pair_rows": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _VP, C.POINTER(C.c_int64)]),
     "mpb_contig_posterior_tables": (C.c_int, [_VP, _VP]),
     "mpb_contigs_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.POINTER(ContigParams),

@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libmoira_pb.so")
 HOST_SOURCES = [os.path.join(CSRC, name) for name in ("mpb_hostonly.cpp", "mpb_context.cpp", "mpb_resident.cpp", "mpb_hostfed.cpp",
                                                       "mpb_perread.cpp", "mpb_poisson.cpp", "mpb_text.cpp", "mpb_contig.cpp",
                                                       "mpb_bgzf.cpp", "mpb_inflate.cpp", "mpb_index.cpp", "mpb_bgzf_fastq.cpp",
-                                                      "mpb_format.cpp", "mpb_collapse.cpp", "mpb_broker.cpp")]
+                                                      "mpb_format.cpp", "mpb_collapse.cpp", "mpb_fasta_qual.cpp", "mpb_broker.cpp")]
 CONTIG_KERNELS = os.path.join(CSRC, "mpb_contig_kernels.hip")      # k_contig: a kernel unit of its own (mpb_kernels.hip stays as it is)
 BGZF_KERNELS = os.path.join(CSRC, "mpb_bgzf_kernels.hip")          # k_bgzf_deflate / _scan / _frame: .gz output, a unit of its own as well
 INFLATE_KERNELS = os.path.join(CSRC, "mpb_inflate_kernels.hip")    # k_bgzf_inflate: BGZF .gz input, one more unit of its own
@@ -31,8 +31,9 @@ CRC_KERNELS = os.path.join(CSRC, "mpb_crc_kernels.hip")            # k_bgzf_crc3
 PAIR_KERNELS = os.path.join(CSRC, "mpb_pair_kernels.hip")          # k_pair_rows / _count / _scan / _lists: two record indexes -> k_contig's inputs, likewise
 FORMAT_KERNELS = os.path.join(CSRC, "mpb_format_kernels.hip")      # k_fmt_count / _scan / _write: output records from text + index, likewise
 COLLAPSE_KERNELS = os.path.join(CSRC, "mpb_collapse_kernels.hip")  # k_col_hash / _group / _rep: hashes and first equal records of a chunk, likewise
+FASTA_QUAL_KERNELS = os.path.join(CSRC, "mpb_fasta_qual_kernels.hip")  # k_fa_count / _scan / _write: fasta + qual text -> slots and index, likewise
 SOURCES = [os.path.join(CSRC, "mpb_kernels.hip"), CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS,
-           PAIR_KERNELS, FORMAT_KERNELS, COLLAPSE_KERNELS] + HOST_SOURCES
+           PAIR_KERNELS, FORMAT_KERNELS, COLLAPSE_KERNELS, FASTA_QUAL_KERNELS] + HOST_SOURCES
 DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_host_internal.h"),
                   os.path.join(CSRC, "mpb_shared.h"), os.path.join(CSRC, "mpb_hostonly.h"), os.path.join(CSRC, "mpb_ctx.h"),
                   os.path.join(CSRC, "mpb_queue.h"),
@@ -48,6 +49,7 @@ DEPS = SOURCES + [os.path.join(CSRC, "mpb_internal.h"), os.path.join(CSRC, "mpb_
                   os.path.join(CSRC, "mpb_pair_lane.inc"),
                   os.path.join(CSRC, "mpb_format_lane.inc"),
                   os.path.join(CSRC, "mpb_collapse_lane.inc"),
+                  os.path.join(CSRC, "mpb_fasta_qual_lane.inc"),
                   os.path.join(CSRC, "contig_posterior.h"),
                   os.path.join(CSRC, "libmoira_pb.map"),
                   os.path.join(ROOT, "include", "moira_pb.h"),
@@ -171,7 +173,7 @@ if __name__ == "__main__":
         print(" ".join(os.path.relpath(p, ROOT) for p in HOST_SOURCES))
         sys.exit(0)
     if "--units-beside-kernels" in sys.argv:     # every unit besides mpb_kernels.hip, which such a script replaces by its variant
-        print(" ".join(os.path.relpath(p, ROOT) for p in [CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS, PAIR_KERNELS, FORMAT_KERNELS, COLLAPSE_KERNELS] + HOST_SOURCES))
+        print(" ".join(os.path.relpath(p, ROOT) for p in [CONTIG_KERNELS, BGZF_KERNELS, INFLATE_KERNELS, INDEX_KERNELS, CRC_KERNELS, PAIR_KERNELS, FORMAT_KERNELS, COLLAPSE_KERNELS, FASTA_QUAL_KERNELS] + HOST_SOURCES))
         sys.exit(0)
     build(force="--force" in sys.argv, verbose=True)
     build_contig(force="--force" in sys.argv, verbose=True)

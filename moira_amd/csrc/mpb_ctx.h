@@ -188,11 +188,14 @@ struct mpb_ctx {
     Buf inflate_stage{BUF_DEVICE};       // mpb_bgzf_inflate_host: one piece of compressed bytes | rows | status rows | the piece's text
     Buf fastq_stage{BUF_DEVICE};         // mpb_fastq_index_host / mpb_filter_fastq_host: text | tile table | prefix | head | status
     Buf fastq_index{BUF_DEVICE};         // ... and, sized from the counted lines: line starts | index rows | kinds | descriptors
+                                         // (mpb_fasta_qual_index_host / mpb_filter_fasta_qual_host: both texts and the slots in the first, both line
+                                         // tables, sizes, prefix, index rows and descriptors in the second)
                                          // (mpb_contigs_filter_fastq_host: both texts' shares of either block, one carve each, and the pairing block)
     Buf format_stage{BUF_DEVICE};        // mpb_format_text_host: text | index | sel | relabel_index | label_id | blob | sizes | prefix | words | one piece
     Buf format_out{BUF_DEVICE};          // ... one window of the formatted text, or the CRC ranges of one piece of its members
     Buf collapse_stage{BUF_DEVICE};      // mpb_collapse_text_host: text | index (the uploaded form's) | hash | slot | rep | status | table | first
-    // the text and index the last successful mpb_filter_fastq_host / mpb_filter_bgzf_fastq_host call left in the two blocks above
+    // the text and index the last successful mpb_filter_fastq_host / mpb_filter_bgzf_fastq_host / mpb_filter_fasta_qual_host call left in
+    // the two blocks above
     // (mpb_format_text_host's resident form); gen == 0: none
     struct ResidentText {
         int64_t gen = 0, last = 0;       // the generation in force; the last one handed out

@@ -278,6 +278,19 @@ void mpb_launch_fq_starts(const uint8_t *text, int64_t text_bytes, int64_t n_til
                           uint32_t *start, int64_t n_start, hipStream_t s);
 void mpb_launch_fq_rows(const uint8_t *text, int64_t text_bytes, const uint32_t *start, int64_t n_start, int64_t n, int32_t max_len,
                         int64_t *idx, uint8_t *kinds, mpb_text_row *desc, int64_t *status, hipStream_t s);
+// fasta+qual input on the device (mpb_fasta_qual_kernels.hip; what a lane does: mpb_fasta_qual_lane.inc).  Record r < n is lines
+// 2 r and 2 r + 1 of ftext[fbytes] and of qtext[qbytes] (allocations rounded up to 16 bytes) by fstart / qstart[n_start], k_fq_starts'
+// tables, which are not trusted.  k_fa_count + k_fa_scan: size[n], prefix[n + 1], head[4] = {n_fit: the leading records whose slots
+// end at or before out_cap, prefix[n_fit], prefix[n], 0}; status[4] (set to {INT64_MAX, 0, 0, 0} by the caller): [0] = the first
+// record that is not taken as record << 8 | why << 1 | which.  k_fa_write: records 0..n_fit-1 into out[out_bytes], idx[.][6] and
+// desc[.] (k_pack_text's descriptors over out); status[1] = the longest packed length, status[2] = 1 when a slot's place failed its
+// check; nothing when status[0] is set.
+void mpb_launch_fa_count(const uint8_t *ftext, int64_t fbytes, const uint32_t *fstart, const uint8_t *qtext, int64_t qbytes,
+                         const uint32_t *qstart, int64_t n_start, int64_t n, int64_t out_cap, int64_t *size, int64_t *prefix,
+                         int64_t *head, int64_t *status, hipStream_t s);
+void mpb_launch_fa_write(const uint8_t *ftext, int64_t fbytes, const uint32_t *fstart, const uint8_t *qtext, int64_t qbytes,
+                         const uint32_t *qstart, int64_t n_start, int64_t n, int32_t max_len, const int64_t *prefix, const int64_t *head,
+                         uint8_t *out, int64_t out_bytes, int64_t *idx, mpb_text_row *desc, int64_t *status, hipStream_t s);
 // RFC 1952's CRC-32 on the device (mpb_crc_kernels.hip; what a lane does: mpb_crc_lane.inc).  k_bgzf_crc32: one wave per range of
 // ranges[n] over text[text_bytes] (a 16-byte aligned block; 0 <= len <= MPB_CRC_RANGE_MAX, any off) -> crc[k], bad[k] = 0; a range
 // that does not lie inside the text is checked again in the kernel: crc[k] = 0, bad[k] = 1, nothing read

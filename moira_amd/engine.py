@@ -71,11 +71,24 @@ class NotTaken(Exception):
     """The device did not take a text for indexing (Engine.fastq_index, Engine.filter_fastq): .why is MPB_FQ_WHY_* (1 a byte
     >= 0x80, 2 a lone carriage return, 3 the line table would not fit, 4 a row check failed), str() names it.  The caller
     indexes on the host (fastio.index), which raises whatever there is to raise.  .which: the text it speaks of where a call takes
-    two (Engine.contigs_filter_fastq: 0 forward, 1 reverse), else None."""
+    two (Engine.contigs_filter_fastq: 0 forward, 1 reverse; Engine.fasta_qual_index, Engine.filter_fasta_qual: 0 fasta, 1 qual,
+    with MPB_FA_WHY_* beside the four reasons above -- names: _lib.FA_WHY), else None.  .bad_record: the first offending record
+    where the device named one, else None."""
 
-    def __init__(self, why, which=None):
-        Exception.__init__(self, L.FQ_WHY[why] if 0 <= why < len(L.FQ_WHY) else "reason %d" % why)
-        self.why, self.which = why, which
+    def __init__(self, why, which=None, bad_record=None):
+        Exception.__init__(self, L.FA_WHY[why] if 0 <= why < len(L.FA_WHY) else "reason %d" % why)
+        self.why, self.which, self.bad_record = why, which, bad_record
+
+
+class FastaQualFilterResult(TextFilterResult):
+    """TextFilterResult of Engine.filter_fasta_qual, with what the device built of the two texts next to it: .text (a uint8
+    array: the slots header | sequence | one byte per quality), .idx (the record index over it), .f_consumed and .q_consumed
+    as fastio.fasta_qual_index returns them.  .resident: the generation of the slots and index the call left on the device."""
+
+    def __init__(self, text, idx, f_consumed, q_consumed, *a):
+        TextFilterResult.__init__(self, *a)
+        self.text, self.idx, self.f_consumed, self.q_consumed = text, idx, f_consumed, q_consumed
+        self.resident = 0
 
 
 class FastqFilterResult(TextFilterResult):
@@ -91,7 +104,7 @@ class FastqFilterResult(TextFilterResult):
 
 class NotResident(Exception):
     """Engine.format_text(resident=g): g is not the generation of the text the context holds -- a later call of filter_fastq,
-    filter_bgzf_fastq, fastq_index or contigs_filter_fastq has replaced or dropped it.  Nothing was touched: the caller formats
+    filter_bgzf_fastq, fastq_index, contigs_filter_fastq, fasta_qual_index or filter_fasta_qual has replaced or dropped it.  Nothing was touched: the caller formats
     on the host (fastio.format_records) or from an upload."""
 
 
@@ -537,6 +550,68 @@ class Engine:
         res.resident = self.resident_text()
         return res
 
+    # ---- fasta+qual input on the device (the index's line kernels, k_fa_count / _scan / _write) ----
+    def _fasta_qual_call(self, fbuf, qbuf, final, max_records, max_len, call):
+        """Either fasta+qual entry: call(the entry's arguments up to bad_record) -> rc.  out is sized 2 * len(fbuf) + 16, an upper
+        bound on the slots, so it never fills; the index by a guess of the records and, where the texts hold more, once more by
+        what the entry counted (_ask_again).  -> (rc, out, idx rows, n, f_consumed, q_consumed, out_used, why, which, bad_record)."""
+        fkeep, faddr, fbytes = _text_ptr(fbuf)
+        qkeep, qaddr, qbytes = _text_ptr(qbuf)
+        limit = _record_limit(max_records)
+        out = np.empty(2 * fbytes + 16, np.uint8)
+        last = None
+
+        def one(cap, _):
+            nonlocal last
+            idx = np.empty((cap, 6), np.int64)
+            n, fc, qc, used, bad = (C.c_int64(0) for _ in range(5))
+            why, which = C.c_int32(0), C.c_int32(0)
+            rc = call(faddr, fbytes, qaddr, qbytes, 1 if final else 0, limit, int(max_len), out.ctypes.data, len(out), idx.ctypes.data, cap,
+                      C.byref(n), C.byref(fc), C.byref(qc), C.byref(used), C.byref(why), C.byref(which), C.byref(bad))
+            last = out, idx, n.value, fc.value, qc.value, used.value, why.value, which.value, bad.value
+            return rc, n.value, None
+        rc, _ = _ask_again(one, min(limit, fbytes // 64 + 64), limit)
+        del fkeep, qkeep
+        return (rc,) + last
+
+    @staticmethod
+    def _fasta_qual_not_taken(why, which, bad):
+        return NotTaken(why, which, bad if bad >= 0 else None)
+
+    def fasta_qual_index(self, fbuf, qbuf, final=True, max_records=None):
+        """A chunk of fasta text and a chunk of qual text in host memory -> (out, idx, f_consumed, q_consumed): the slots
+        header | sequence | one byte per quality (a uint8 array) and their record index, built on the device from the texts
+        alone (mpb_fasta_qual_index_host), as fastio.fasta_qual_index builds them.  NotTaken(why, which) when the device hands
+        the texts back (.bad_record: the first offending record where there is one): the caller goes through the host function."""
+        call = lambda *a: self.lib.mpb_fasta_qual_index_host(self.ctx, *a)
+        rc, out, idx, n, fc, qc, used, why, which, bad = self._fasta_qual_call(fbuf, qbuf, final, max_records, 0, call)
+        L.check(rc)
+        if why:
+            raise self._fasta_qual_not_taken(why, which, bad)
+        return out[:used], idx[:n], fc, qc
+
+    def filter_fasta_qual(self, fbuf, qbuf, final=True, max_records=None, max_len=0, lower_n_is_base=False, poisson=False, **kw):
+        """A chunk of fasta text and a chunk of qual text ALONE -> FastaQualFilterResult: one upload, slots and index built on
+        the device, the records packed and filtered there (mpb_filter_fasta_qual_host).  .text, .idx, .f_consumed, .q_consumed
+        are fastio.fasta_qual_index's and the results are filter_text's (fastq_offset=0) on them, bit for bit.  NotTaken(why,
+        which) when the device hands the texts back.  `kw` as filter()'s."""
+        params = kw.pop("params", None) or self.params(**kw)
+        counts, badrec = L.FilterCounts(), C.c_int64(-1)
+        r = None
+
+        def call(*a):
+            nonlocal r
+            r = _TextResults(max(a[10], 1))                  # (a[10]: the rows of this try)
+            return self.lib.mpb_filter_fasta_qual_host(self.ctx, *a, 1 if lower_n_is_base else 0, C.byref(params), 1 if poisson else 0,
+                                                       *r.ptrs(), C.byref(counts), C.byref(badrec))
+        rc, out, idx, n, fc, qc, used, why, which, bad = self._fasta_qual_call(fbuf, qbuf, final, max_records, max_len, call)
+        _check_text(rc, badrec)
+        if why:
+            raise self._fasta_qual_not_taken(why, which, bad)
+        res = FastaQualFilterResult(out[:used], idx[:n], fc, qc, *r.cut(n), counts.n_pass, counts.n_overflow)
+        res.resident = self.resident_text()
+        return res
+
     # ---- BGZF FASTQ filtered where it inflates (k_bgzf_inflate, k_bgzf_crc32, the index, the pack) ----
     def crc32_ranges(self, buf, offs, lens):
         """The CRC-32 (zlib.crc32's) of buf[offs[k] : offs[k] + lens[k]] for every k, computed on the device (mpb_crc32_ranges_host:
@@ -613,7 +688,8 @@ class Engine:
 
     # ---- output records formatted on the device (k_fmt_count, k_fmt_scan, k_fmt_write) -------------
     def resident_text(self):
-        """The generation of the text and index the last filter_fastq / filter_bgzf_fastq call left on the device; 0: none."""
+        """The generation of the text and index the last filter_fastq / filter_bgzf_fastq / filter_fasta_qual call left on the device;
+        0: none."""
         return int(self.lib.mpb_resident_text(self.ctx))
 
     def format_text(self, buf=None, idx=None, sel=None, kind=2, resident=None, bgzf=False, fastq_offset=33, max_len=0, relabel=None,

@@ -767,6 +767,22 @@ class PairedFastqChunks:
             yield fbuf, fidx[:n], rbuf, ridx[:n]
 
 
+def fasta_qual_index(fbuf, qbuf, final, max_records, out, idx):
+    """One call of mio_fasta_qual_index over a block of fasta text and a block of qual text (bytes): up to `max_records`
+    records become slots header | sequence | one byte per quality in `out` (a uint8 array, or a view of one) and rows of `idx`
+    (int64[.][IDX_COLS], offsets relative to `out`) -> (n, f_consumed, q_consumed, out_used).  Raises Unsupported for anything
+    the line parser treats specially."""
+    L = load()
+    fc, qc, ou = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    n = L.mio_fasta_qual_index(fbuf, len(fbuf), qbuf, len(qbuf), 1 if final else 0, min(int(max_records), len(idx)), out.ctypes.data,
+                               len(out), idx.ctypes.data, C.addressof(fc), C.addressof(qc), C.addressof(ou))
+    if n == E_UNSUPPORTED:
+        raise Unsupported(_err())
+    if n < 0:
+        raise ValueError(_err())
+    return n, fc.value, qc.value, ou.value
+
+
 class FastaQualChunks:
     """A fasta file and its qual file as (buf, idx) chunks of exactly `max_records` records (fewer only at
     the end): buf is a uint8 array built by mio_fasta_qual_index (header | sequence | one byte per quality,
@@ -794,19 +810,11 @@ class FastaQualChunks:
                 out = np.empty(self.max_records * 64 + 4 * self.block, np.uint8)
                 idx = np.empty((self.max_records, IDX_COLS), np.int64)
                 have = used = 0
-            fc, qc, ou = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-            n = L.mio_fasta_qual_index(tail[0], len(tail[0]), tail[1], len(tail[1]), 1 if final else 0,
-                                       self.max_records - have, out.ctypes.data + used, len(out) - used,
-                                       idx.ctypes.data + have * IDX_COLS * 8, C.addressof(fc), C.addressof(qc),
-                                       C.addressof(ou))
-            if n == E_UNSUPPORTED:
-                raise Unsupported(_err())
-            if n < 0:
-                raise ValueError(_err())
+            n, fc, qc, ou = fasta_qual_index(tail[0], tail[1], final, self.max_records - have, out[used:], idx[have:])
             idx[have:have + n, [HDR_OFF, SEQ_OFF, QUAL_OFF]] += used      # offsets were relative to this call's slice
             have += n
-            used += ou.value
-            tail = [tail[0][fc.value:], tail[1][qc.value:]]
+            used += ou
+            tail = [tail[0][fc:], tail[1][qc:]]
             starved = n == 0                                             # nothing complete in what is buffered
             full = have == self.max_records
             if full or (final and n == 0):
