@@ -151,8 +151,76 @@ def golden_cases():
     return [case("golden", text, idx), case("golden_100", text, idx, max_len=100)]
 
 
+def py2_hash_np(seqs):
+    """CPython 2.7's hash(str) of every row of a uint8 matrix of equally long, non-empty sequences, in numpy (uint64, wrapping)."""
+    m, L = seqs.shape
+    with np.errstate(over="ignore"):
+        x = seqs[:, 0].astype(np.uint64) << np.uint64(7)
+        for j in range(L):
+            x = (x * np.uint64(1000003)) ^ seqs[:, j].astype(np.uint64)
+        x ^= np.uint64(L)
+    x[x == np.uint64(0xFFFFFFFFFFFFFFFF)] = np.uint64(0xFFFFFFFFFFFFFFFE)
+    return x
+
+
+def table_of(n):
+    """(cap, cap_shift) of n records, ClParams' rule: cap the power of two that is at least max(16, 2 n)."""
+    cap = 16
+    while cap < 2 * n:
+        cap *= 2
+    return cap, 64 - (cap.bit_length() - 1)
+
+
+def start_slots(h, n):
+    """cl_start of the hashes h (uint64) in the table of n records."""
+    with np.errstate(over="ignore"):
+        return ((h * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(table_of(n)[1])).astype(np.int64)
+
+
+_CANDIDATES = []
+
+
+def one_slot_sequences(n, slot, distinct, length=24):
+    """`distinct` different sequences of `length` bases whose real hash starts its probe walk at `slot` of the table of n records,
+    found by seeded search; the hashes are pairwise different and are fastio.py2_hashes'."""
+    if not _CANDIDATES:
+        pool = np.frombuffer(b"ACGT", np.uint8)[np.random.default_rng(18).integers(0, 4, (1000000, length))]
+        _CANDIDATES.append((pool, py2_hash_np(pool)))
+    pool, h = _CANDIDATES[0]
+    assert pool.shape[1] == length
+    hit = np.flatnonzero(start_slots(h, n) == slot)[:distinct]
+    assert len(hit) == distinct, (len(hit), distinct)
+    seqs = [pool[i].tobytes() for i in hit]
+    text, idx = raw(seqs)
+    real = np.array(F.py2_hashes(text, idx, 0), np.uint64)
+    assert np.array_equal(real, h[hit]) and len(set(real.tolist())) == distinct == len(set(seqs))
+    assert (start_slots(real, n) == slot).all()
+    return seqs
+
+
+def crowded_cases():
+    """Long probe walks under real hashes, which the GPU can run (forged_cases: the lane model alone): 4,096 records of 64
+    sequences that all start at slot cap - 2, so that every walk but the first two wraps around the table's end, and 600 records
+    of 200 sequences that all start at slot 0."""
+    out = []
+    for name, n, distinct, slot, seed in (("crowded_wrap_4096", 4096, 64, table_of(4096)[0] - 2, 19), ("crowded_slot0_600", 600, 200, 0, 20)):
+        seqs = one_slot_sequences(n, slot, distinct)
+        draw = np.random.default_rng(seed).integers(0, distinct, n)
+        draw[:distinct] = np.random.default_rng(seed).permutation(distinct)      # (every sequence is there)
+        c = case(name, *raw([seqs[i] for i in draw]))
+        assert len(c["idx"]) == n and len(set(start_slots(np.array(F.py2_hashes(c["text"], c["idx"], 0), np.uint64), n).tolist())) == 1
+        out.append(c)
+    return out
+
+
+def long_cases():
+    """Sequences of 65535 bases (tests/helpers/long_read_inputs.py: collapse_seqs), with max_len 0 and 40000."""
+    from helpers import long_read_inputs
+    return long_read_inputs.collapse_cases()
+
+
 def all_cases():
-    return small_cases() + truncation_cases() + count_cases() + big_cases() + golden_cases()
+    return small_cases() + truncation_cases() + count_cases() + big_cases() + golden_cases() + crowded_cases()
 
 
 def forged_cases():

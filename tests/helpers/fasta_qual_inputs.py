@@ -159,6 +159,15 @@ def directed_cases():
     return cs
 
 
+def long_cases():
+    """Records of up to 65535 values (tests/helpers/long_read_inputs.py): both separators, both line ends, an open last line,
+    and the refusals beyond byte 200,000 of a quality line."""
+    from helpers import long_read_inputs as LR
+    return [LR.fasta_qual_case("long_blank_lf"), LR.fasta_qual_case("long_tab_crlf", b"\t", b"\r\n"),
+            LR.fasta_qual_case("long_tab_lf_open", b"\t", last_eol=False), LR.fasta_qual_case("long_blank_crlf_max_len", b" ", b"\r\n", max_len=40000),
+            LR.fasta_qual_case("long_not_final", final=False)] + LR.fasta_qual_refusals()
+
+
 _NAME = b"abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789_:/.-#"
 
 

@@ -138,6 +138,19 @@ def not_looked_at():
     return [("non_ascii_in_open_tail/more", good + b"@x\xfe", 0, BIG), ("lone_cr_in_open_tail/more", good + b"@x\rzz", 0, BIG)]
 
 
+def long_reads():
+    """Records of up to 65535 bases (tests/helpers/long_read_inputs.py: fastq_text), LF and CRLF: whole, cut inside the
+    65535-base quality line, and with max_records just before and just behind a long record."""
+    from helpers import long_read_inputs as LR
+    cases = []
+    for tag, nl in (("lf", b"\n"), ("crlf", b"\r\n")):
+        text, idx = LR.fastq_text(nl)
+        cases += both("long_%s" % tag, text) + both("long_%s_cut_in_quality" % tag, text[:int(idx[1, 4]) + 40000])
+        for m in (1, 2, 3, 4):
+            cases += both("long_%s_max_records%d" % (tag, m), text, m)
+    return cases
+
+
 def directed():
     return placement() + endings() + limits() + bad_records() + headers() + not_looked_at()
 

@@ -176,6 +176,25 @@ def golden_cases():
     return out
 
 
+def long_cases():
+    """Records of up to 65535 bases (tests/helpers/long_read_inputs.py: fastq_text): all kinds, truncated inside a lane step,
+    reversed with repeats, CRLF, and every quality byte 33..126 at every lane with every offset pair and clamp_q0 on and off."""
+    from helpers import long_read_inputs as LR
+    text, idx = LR.fastq_text()
+    n = len(idx)
+    out = [case("long_%s" % KIND_NAME[k], text, idx, kind=k) for k in KINDS]
+    out += [case("long_max_len_40000_%s" % KIND_NAME[k], text, idx, kind=k, max_len=40000) for k in KINDS]
+    out.append(case("long_reversed_repeats_qual", text, idx, sel=np.concatenate([np.arange(n)[::-1], [1, 1, 3, 0, 1]]), kind=F.FMT_QUAL))
+    out.append(case("long_crlf_fastq", *LR.fastq_text(b"\r\n"), kind=F.FMT_FASTQ))
+    text, idx = LR.fastq_text(b"\n", "every")
+    for off, out_off in ((33, 33), (33, 64), (64, 33)):
+        for clamp in (True, False):
+            for k in (F.FMT_QUAL, F.FMT_FASTQ):
+                out.append(case("long_q_%d_%d_%d_%s" % (off, out_off, clamp, KIND_NAME[k]), text, idx, kind=k, fastq_offset=off,
+                                out_offset=out_off, clamp_q0=clamp))
+    return out
+
+
 def all_cases():
     return (length_cases() + alignment_cases() + crlf_cases() + count_cases() + sel_cases() + quality_cases() + max_len_cases() +
             relabel_cases() + golden_cases())

@@ -74,6 +74,15 @@ def test_every_case_is_the_oracles_hash_and_first_equal_record(checker, tmp_path
         assert lines[c["name"]] == ("ok", "n=%d groups=%d" % (len(c["idx"]), groups(c))), c["name"]
 
 
+def test_sequences_of_65535_bases_are_the_oracles(checker, tmp_path):
+    """cl_hash and cl_equal over 4,096 words a sequence, every load checked (the kernels: tests/test_gpu_long_text.py)."""
+    cases = X.long_cases()
+    lines = check(checker, tmp_path, cases)
+    for c in cases:
+        assert lines[c["name"]] == ("ok", "n=%d groups=%d" % (len(c["idx"]), groups(c))), c["name"]
+    assert [groups(c) for c in cases] == [8, 3]
+
+
 def test_forged_hashes_leave_rep_to_the_byte_compare(checker, tmp_path):
     cases = X.forged_cases()
     lines = check(checker, tmp_path, cases)

@@ -100,6 +100,23 @@ def test_directed_cases_are_the_hosts_or_handed_back_with_their_reason(checker, 
             assert (fields(lines[c["name"]][1])["host"] == 0) == (c["name"] == "zeros_0007"), c["name"]
 
 
+def test_records_of_65535_values_are_the_hosts_or_handed_back_with_their_reason(checker, tmp_path):
+    """Quality lines of up to 256 KiB: up to 2,048 steps of a group over a line, every load and store checked (the kernels:
+    tests/test_gpu_long_text.py)."""
+    cases = X.long_cases()
+    lines = check(checker, tmp_path, cases)
+    for c in cases:
+        verdict, rest = lines[c["name"]]
+        if c["expect"] is None:
+            assert verdict == "taken", (c["name"], rest)
+            as_host(c, rest)
+            assert fields(rest)["longest"] == (c["max_len"] or 65535)
+        else:
+            got = fields(rest)
+            assert verdict == "back" and (got["why"], got["which"], got["bad"]) == c["expect"], (c["name"], rest)
+            assert (got["host"] == 0) == (c["name"] == "long_zeros_0007"), c["name"]
+
+
 def test_two_thousand_valid_small_texts_are_all_taken(checker, tmp_path):
     cases = X.fuzz_cases()
     assert len(cases) == 2000

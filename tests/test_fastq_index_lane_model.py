@@ -82,6 +82,17 @@ def test_directed_texts_equal_the_host_index(checker, tmp_path):
     check_taken(cases, run(checker, str(tmp_path), cases))
 
 
+def test_records_of_65535_bases_equal_the_host_index(checker, tmp_path):
+    """Tiles without a newline, lines over four tiles (the kernels: tests/test_gpu_long_text.py)."""
+    cases = X.long_reads()
+    got = run(checker, str(tmp_path), cases)
+    check_taken(cases, got)
+    assert max(g["longest"] for g in got) == 65535
+    got = run(checker, str(tmp_path), cases[:2], max_len=40000)
+    check_taken(cases[:2], got)
+    assert max(g["longest"] for g in got) == 40000
+
+
 def test_descriptors_with_max_len(checker, tmp_path):
     cases = X.endings() + X.headers()
     got = run(checker, str(tmp_path), cases, max_len=3)

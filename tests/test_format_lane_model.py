@@ -87,6 +87,15 @@ def test_every_case_is_mio_formats_bytes(checker, tmp_path):
         assert lines[c["name"]] == ("ok", "bytes=%d" % len(X.want(c))), c["name"]
 
 
+def test_records_of_65535_bases_are_mio_formats_bytes(checker, tmp_path):
+    """Up to 512 steps of a lane group's running-base loop, every load and store checked (the kernels: tests/test_gpu_long_text.py)."""
+    cases = X.long_cases()
+    assert len({c["name"] for c in cases}) == len(cases)
+    lines = check(checker, tmp_path, cases)
+    for c in cases:
+        assert lines[c["name"]] == ("ok", "bytes=%d" % len(X.want(c))), c["name"]
+
+
 def test_the_equal_offset_form_keeps_a_byte_below_the_offset(checker, tmp_path):
     """put_qual_string copies the line when the offsets are equal and raises only the byte fastq_offset itself: q = -1 stays the
     byte it was there, while with different offsets it becomes the floor.  Both are mio_format's bytes."""

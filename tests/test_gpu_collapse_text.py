@@ -1,7 +1,8 @@
 """The data-parallel part of collapse on the GPU (include/moira_pb.h: mpb_collapse_text_host; Engine.collapse_text; k_col_hash,
 k_col_group, k_col_rep).  The oracle of hash is fastio.py2_hashes (mio_py2_hash), the oracle of rep a Python dict of truncated
 sequences to first index; the cases are tests/helpers/collapse_inputs.py's, the ones the host lane model runs
-(tests/test_collapse_lane_model.py, which also pins the byte compare with forged hashes: no GPU test can)."""
+(tests/test_collapse_lane_model.py, which also pins the byte compare with forged equal hashes: no GPU test can; long probe
+walks from one start slot run here too, with real hashes found by search: crowded_cases)."""
 import numpy as np
 import pytest
 
@@ -47,7 +48,7 @@ def test_the_uploaded_form_is_the_oracles_hash_and_first_equal_record(eng, c):
 
 
 def test_two_calls_on_the_same_input_return_equal_arrays(eng):
-    for c in X.big_cases():
+    for c in X.big_cases() + X.crowded_cases():
         a, b = eng.collapse_text(c["text"], c["idx"]), eng.collapse_text(c["text"], c["idx"])
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 

@@ -82,6 +82,44 @@ def test_the_index_entry_is_the_hosts_or_hands_back_with_its_reason(eng, c):
     assert np.array_equal(idx[:n], widx) and (idx[n:] == -7).all()
 
 
+SEEDED = {}
+SLICES = 4
+
+
+def seeded_cases():
+    """The lane model's 2,000 seeded valid texts and 600 damaged ones, made once."""
+    if not SEEDED:
+        SEEDED["all"] = X.fuzz_cases() + X.damage_cases()
+    return SEEDED["all"]
+
+
+@pytest.mark.parametrize("part", range(SLICES))
+def test_seeded_fuzz_and_damage_are_taken_as_the_host_takes_them_or_handed_back(eng, part):
+    """tests/test_fasta_qual_lane_model.py's rule on the kernels: a text that is taken equals the host's; one the host calls
+    unsupported is never taken; one the host takes is handed back only under the lanes' documented superset (a quality token of
+    more than three digits: TOKEN, in the qual text).  Every valid text is taken.  All 2,600 texts, in four slices."""
+    import re
+    cases = seeded_cases()
+    assert len(cases) == 2600
+    taken = back = 0
+    for c in cases[part::SLICES]:
+        w = X.want(c)
+        rc, out, idx, n, fc, qc, used, why, which, bad = raw_index(eng, c)
+        assert rc == L.OK, c["name"]
+        if why == 0:
+            assert w is not None, c["name"]                  # (never taken where the host says unsupported)
+            wout, widx, wfc, wqc = w
+            assert (n, fc, qc, used) == (len(widx), wfc, wqc, len(wout)), c["name"]
+            assert np.array_equal(out[:used], wout) and (out[used:] == 0xA5).all(), c["name"]
+            assert np.array_equal(idx[:n], widx) and (idx[n:] == -7).all(), c["name"]
+            taken += 1
+        else:
+            assert not c["name"].startswith("fuzz"), c["name"]
+            assert w is None or ((why, which) == (X.TOKEN, 1) and re.search(rb"\d{4,}", c["qtext"])), (c["name"], why, which, bad)
+            back += 1
+    assert taken >= 500 and back >= 100                      # (2,000 valid texts and the damaged ones the host takes; the rest)
+
+
 @pytest.mark.parametrize("c", ENGINE_CASES, ids=[c["name"] for c in ENGINE_CASES])
 def test_the_wrappers_return_the_hosts_results_and_the_filters(eng, c):
     kw = dict(final=c["final"], max_records=None if c["max_records"] == X.NO_LIMIT else c["max_records"])
