@@ -808,7 +808,8 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *ctx, const char *carry, int64_t carry_le
  * Output records formatted on the device (k_fmt_count, k_fmt_scan, k_fmt_write; csrc/mpb_format_kernels.hip): records sel[k]
  * (sel NULL: k; any order, repeats allowed), k < nsel, of a text and its record index idx[n_records][MPB_IDX_COLS] become fasta
  * (kind 0), qual (1) or fastq (2) text, byte for byte what mio_format (include/moira_io.h) writes for the same arguments with
- * ee == NULL -- that function stays the definition of the output; its ";ee=...;" suffix is not offered here.  relabel (at most
+ * ee == NULL -- that function stays the definition of the output; its ";ee=...;" suffix is not offered here (it is
+ * mpb_format_records_host's, below).  relabel (at most
  * 255 bytes) with relabel_index[nsel] (each >= 0) replaces the header token; labels[n_labels] (at most 16, each at most 255
  * bytes) with label_id[nsel] (-1: none) appends "\t" + label.
  * UPLOADED FORM (resident == 0): text[text_bytes] (at most 1 GiB) and idx go up once; any buffer and index of that layout do
@@ -820,7 +821,14 @@ int mpb_filter_bgzf_fastq_host(mpb_ctx *ctx, const char *carry, int64_t carry_le
  * mpb_filter_fastq_host, mpb_filter_bgzf_fastq_host or mpb_filter_fasta_qual_host call of this context left on the device are
  * read where they lie (for the
  * BGZF call: carry + members' text, as its index counts); n_records is that call's *n.  The context numbers these texts:
- * mpb_resident_text returns the generation in force (1, 2, ...), 0 for none.  Every successful call of the two makes a new one.
+ * mpb_resident_text returns the generation in force (1, 2, ...), 0 for none.  Every successful call of these makes a new one.
+ * THE CONTIG GENERATION.  mpb_contigs_filter_fastq_host drops the generation first, as listed below, and at its end keeps a new
+ * one when *why == 0, *n_built > 0, *n_handed_back == 0 and the filter went through (*filter_rc == MPB_OK): the text is the slot
+ * buffer (*n_built * rec_cap bytes), the index the device-written out_idx, n_records is *n_built, and the generation carries the
+ * device's overlap, gaps and mismatches arrays as its aux (mpb_format_records_host's report lines).  In every other case the
+ * generation stays none: all or nothing.  The slot block belongs to the contig stage: mpb_contigs_text_host and
+ * mpb_contigs_filter_text_host may grow or overwrite it, so they set a generation THAT LIES IN THAT BLOCK to none, and only such a
+ * one -- a single-end generation stays in force behind them.  mpb_contigs_filter_text_host itself leaves no generation.
  * The generation is set to none by every call that may move, grow, overwrite or free the blocks the text and index lie in,
  * whether it succeeds, fails or hands its text back: mpb_fastq_index_host, mpb_filter_fastq_host, mpb_filter_bgzf_fastq_host,
  * mpb_contigs_filter_fastq_host, mpb_fasta_qual_index_host, mpb_filter_fasta_qual_host and mpb_destroy.  No other call touches them.  A `resident` that is not the generation in force
@@ -846,6 +854,32 @@ int mpb_format_text_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, con
                          int32_t n_labels, const int32_t *label_id, int32_t bgzf, uint8_t *out, int64_t out_cap, int64_t *out_bytes,
                          int64_t *text_needed, int64_t *bad_record, mpb_bgzf_stats *stats);
 int64_t mpb_resident_text(mpb_ctx *ctx);
+
+/*
+ * mpb_format_text_host with the two pieces of the host formatter's per-record interface it leaves out; the same kernels, the
+ * same two forms, windows, compressed form, *text_needed / ask-again convention and *bad_record.  mpb_format_text_host is this
+ * call with ee and aux NULL and kind 4 refused.
+ * ee (double[nsel], by POSITION k in sel; NULL: none): the USEARCH suffix ";ee=%.2f;size=1;" between the header token and the
+ * label, exactly where mio_format(..., ee) places it, for kinds 0, 1, 2 and 4.  The device renders "%.2f" in 64-bit integers
+ * from the bits of the double: the sign is the sign bit (-0.0 and -0.001 give "-0.00"); the magnitude m 2^-s becomes
+ * q = round-half-even(100 m / 2^s) on the exact binary value and is printed as q / 100, '.', the two digits of q % 100 --
+ * snprintf's result.  THE TAKEN DOMAIN is finite values with |ee| < 2^53.  Every ee[k] is checked on the host before anything is
+ * uploaded: one outside the domain is MPB_E_INVALID with *bad_record = k and a message naming ee; the caller formats on the host
+ * (the device defines no output for it).  The kernel makes the same check again.  ee always comes from the host, 8 bytes per
+ * selected record, in either form.
+ * kind 4 (MIO_FMT_REPORT; 3 is the collapse's names line and stays invalid): the contigs.report line of mio_format_report,
+ * hdr[;ee=..;size=1;] "\t1\t" overlap "\t" gaps "\t" mismatches "\n" -- no leading mark, no label (labels and label_id must be NULL),
+ * the header token ':' -> '_' or relabel + decimal.  The three numbers are aux[3 r .. 3 r + 2] of the RECORD r = sel[k], any
+ * int32.  The sequence and quality columns of the row are neither read nor checked.  Uploaded form: aux is
+ * int32[n_records][3] and required.  Resident form: aux must be NULL and the generation must be one that carries aux (the
+ * contig generation, above); otherwise MPB_E_INVALID, with a message of its own (a generation in force that has no aux is
+ * resident).  aux with any other kind is MPB_E_INVALID.
+ */
+int mpb_format_records_host(mpb_ctx *ctx, const char *text, int64_t text_bytes, const int64_t *idx, int64_t n_records, int64_t resident,
+                            const int64_t *sel, int64_t nsel, int32_t kind, int32_t fastq_offset, int32_t out_offset, int32_t clamp_q0,
+                            int32_t max_len, const char *relabel, const int64_t *relabel_index, const char *const *labels,
+                            int32_t n_labels, const int32_t *label_id, const double *ee, const int32_t *aux, int32_t bgzf, uint8_t *out,
+                            int64_t out_cap, int64_t *out_bytes, int64_t *text_needed, int64_t *bad_record, mpb_bgzf_stats *stats);
 
 /*
  * The data-parallel part of the collapse of identical sequences, on the device (k_col_hash, k_col_group, k_col_rep;

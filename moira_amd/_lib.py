@@ -180,6 +180,9 @@ PROTOTYPES = {
     "mpb_format_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_char_p, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int64,
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(BgzfStats)]),
+    "mpb_format_records_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_char_p, _VP, _VP, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, C.c_int64,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(BgzfStats)]),
     "mpb_resident_text": (C.c_int64, [_VP]),
     "mpb_collapse_text_host": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, C.POINTER(C.c_int64)]),
     "mpb_encode_ascii_device": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP]),

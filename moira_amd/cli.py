@@ -264,18 +264,22 @@ def build_parser():
                         "). Where it does not apply (no -oc gz, the line parser, several GPUs, no GPU) one line says so and host "
                         "zlib is used; a batch the device does not take is compressed on the host, with one message.")
     f.add_argument("--device_format", action="store_true",
-                   help="(not in moira.py) with --device_index and --device_pack, -c false and the mothur pipeline on one GPU: "
+                   help="(not in moira.py) with -c false on one GPU, single-end with --device_index and --device_pack or paired "
+                        "with --device_pair_index (either pipeline: the USEARCH ';ee=..;size=1;' suffix is written there as well): "
                         "format the kept and the discarded records of each chunk on the device too, from the text and the record "
-                        "index the filter call left there (plain input: the text goes up once and comes back as output; BGZF "
+                        "index the filter call left there -- for a paired chunk the contigs where they were built, and the lines "
+                        "of contigs.report from the arrays beside them (the slots still come down: the host keeps the headers for "
+                        "its errors and the fallback) -- (plain input: the text goes up once and comes back as output; BGZF "
                         "input: the inflated text still comes down too, for the host formatter's sake; the host formatter does "
                         "not run). With -oc gz and --device_compress the output text is compressed where it lies and only "
                         "BGZF members come down. A chunk that came the host way is formatted on the host as always, with one "
                         "message. Output files are identical (.gz: after decompression). Where it does not apply one line says "
                         "so. Measured once on the golden reads: as plain text the host formatter on 16 threads is faster (the "
                         "formatted text has to come back); compressed where it lies the device form is about four times faster "
-                        "than host formatting plus --device_compress. No rate is promised.")
+                        "than host formatting plus --device_compress. " + DEVICE_PAIR_TAIL_MEASURED + " No rate is promised.")
     f.add_argument("--device_collapse", action="store_true",
-                   help="(not in moira.py) with --device_index and --device_pack and -c true, single-end FASTQ on one GPU: compute "
+                   help="(not in moira.py) with -c true on one GPU, single-end FASTQ with --device_index and --device_pack or paired "
+                        "FASTQ with --device_pair_index (the contigs where they were built): compute "
                         "the part of --collapse that is the same for every read on the device too, from the text and the record "
                         "index the filter call left there: the Python-2 string hash of every (truncated) sequence and, for every "
                         "read, the first read of its chunk with the same sequence. The host collapse then hashes nothing and "
@@ -857,6 +861,13 @@ DEVICE_COLLAPSE_MEASURED = ("Measured once on one 64 MiB block of the golden rea
                             "most sequences are distinct (faster by more than the two ranges together); one pair of whole runs of "
                             "468,752 reads took 0.54 s with the switch and 0.60 s without.")
 
+# (tools/device_pair_tail_rate.py -> profiles/device_pair_tail_rate.json)
+DEVICE_PAIR_TAIL_MEASURED = ("Paired, measured once on one chunk of 65,536 golden 2 x 251 pairs, the contig call (60.7 ms alone) included: as "
+                             "plain text 105.5 ms on the device against 83.8 ms with the host formatter on 16 threads (no difference: within "
+                             "the two interquartile ranges together); as BGZF members 89.6 ms against 154.2 ms for host formatting plus "
+                             "--device_compress (faster by more than the two ranges together); --device_collapse 69.7 ms against 69.6 ms (no "
+                             "difference).")
+
 
 DEVICE_FASTA_QUAL_MEASURED = ("Measured once on the golden reads as fasta+qual tiled to 255 MiB of qual text (340,550 reads): one device call "
                               "takes 21.9 ms against 164.2 ms for the host parser plus the device text filter (faster by more than the two "
@@ -1177,24 +1188,36 @@ DEVICE_PAIR_INDEX_SENTENCE = ("--device_pair_index does not apply to this run (i
 
 def _device_format_eligible(args, backend, on):
     """--device_format applies where --device_index and --device_pack are in force (`on`: single-end FASTQ on the byte-level path
-    on one GPU), nothing is collapsed, the pipeline is mothur (no ee suffix) and the engine has the call."""
-    return bool((("device_index" in on and "device_pack" in on) or "device_fasta_qual" in on) and not args.collapse
-                and args.pipeline == "mothur" and hasattr(getattr(backend, "engine", None), "format_text"))
+    on one GPU) or --device_pair_index is (paired FASTQ: the contigs stay on the device), nothing is collapsed and the engine has
+    the call: format_text for the mothur pipeline of a single-end run; format_report -- the engine that has it also writes the
+    USEARCH ee suffix -- for the USEARCH pipeline and for every paired run, which writes contigs.report."""
+    eng = getattr(backend, "engine", None)
+    single = ("device_index" in on and "device_pack" in on) or "device_fasta_qual" in on
+    paired = "device_pair_index" in on and bool(args.paired)
+    if args.collapse or not (single or paired):
+        return False
+    if paired or args.pipeline != "mothur":
+        return hasattr(eng, "format_report") and hasattr(eng, "format_text")
+    return hasattr(eng, "format_text")
 
 
-DEVICE_FORMAT_SENTENCE = ("--device_format does not apply to this run (it takes single-end FASTQ input of the byte-level parser on one GPU, "
-                          "with --device_index and --device_pack, -c false and the mothur pipeline): the host formatter is used.")
+DEVICE_FORMAT_SENTENCE = ("--device_format does not apply to this run (it takes FASTQ input of the byte-level parser on one GPU with -c false: "
+                          "single-end with --device_index and --device_pack, paired with --device_pair_index): the host formatter is "
+                          "used.")
 
 
 def _device_collapse_eligible(args, backend, on):
     """--device_collapse applies where --device_index and --device_pack are in force (`on`: single-end FASTQ on the byte-level
-    path on one GPU), the run collapses and the engine has the call."""
-    return bool((("device_index" in on and "device_pack" in on) or "device_fasta_qual" in on) and args.collapse and not args.paired
-                and hasattr(getattr(backend, "engine", None), "collapse_text"))
+    path on one GPU) or, for a paired run, --device_pair_index is (the contigs stay on the device), the run collapses and the
+    engine has the call."""
+    single = (("device_index" in on and "device_pack" in on) or "device_fasta_qual" in on) and not args.paired
+    paired = "device_pair_index" in on and bool(args.paired)
+    return bool((single or paired) and args.collapse and hasattr(getattr(backend, "engine", None), "collapse_text"))
 
 
-DEVICE_COLLAPSE_SENTENCE = ("--device_collapse does not apply to this run (it takes single-end FASTQ input of the byte-level parser on one "
-                            "GPU, with --device_index and --device_pack and -c true): the host collapse hashes and groups every read.")
+DEVICE_COLLAPSE_SENTENCE = ("--device_collapse does not apply to this run (it takes FASTQ input of the byte-level parser on one GPU with "
+                            "-c true: single-end with --device_index and --device_pack, paired with --device_pair_index): the host "
+                            "collapse hashes and groups every read.")
 
 
 def _device_fasta_qual_eligible(args, backend):
@@ -1336,7 +1359,13 @@ def _filtered_where_built(built):
     if len(built) == 3:
         return built[0], built[1], built[2], None
     buf, idx, aux, ee, has_n, err = built
-    return buf, idx, aux, ((ee, has_n) if err is None else None)
+    resident = getattr(built, "resident", 0)                 # (--device_pair_index: the generation the call left, or 0)
+    return buf, idx, aux, ((_Filtered((ee, has_n), resident) if resident else (ee, has_n)) if err is None else None)
+
+
+class _BuiltResident(tuple):
+    """What a fused chunk yields, with .resident: the generation of the contigs the call left on the device."""
+    resident = 0
 
 
 class _DeferredContigs:
@@ -1501,7 +1530,8 @@ class _DevicePairIndexer:
     files' tails and the rules that pin the run to the reference's zip() parser -- with ONE device call as its pass in place of
     the two index calls: device(fbuf, rbuf, ffinal, rfinal, max_records) -> (res, cbuf, cidx, aux, ee, has_n, filter_error)
     (moira_amd.contig.contigs_from_fastq_text_filtered), which also builds and filters the contigs.  It yields what a fused chunk
-    yields, (cbuf, cidx, aux, ee, has_n, filter_error).  A header mismatch yields the pairs before it and then raises
+    yields, (cbuf, cidx, aux, ee, has_n, filter_error), as a _BuiltResident whose .resident is the generation of the contigs the
+    call left on the device (res.resident; 0, or a plain tuple from the host pass: none).  A header mismatch yields the pairs before it and then raises
     NameMismatchError, as _fast_chunks does, before the loop's own error.  A pair of blocks the device hands back (not_taken), or
     whose call ends in a ValueError, goes through fastio.paired_host_pass and host(fbuf, fidx, rbuf, ridx), today's fused call;
     the first such pair is reported.  A fastio.Unsupported of the host indexer is the run's to take."""
@@ -1511,13 +1541,19 @@ class _DevicePairIndexer:
             from .engine import NotTaken as not_taken
         self.device, self.host, self.max_records, self.refused, self.threads, self.not_taken = device, host, max_records, refused, threads, not_taken
 
+    @staticmethod
+    def _built(built, resident):
+        out = _BuiltResident(built)
+        out.resident = resident
+        return out
+
     def _one(self, tail, eof):
         """One pass over the two tails, as fastio.paired_lockstep asks for it; its payload is (mismatch, built or None)."""
         from . import fastio as F
         try:
             res, *built = self.device(tail[0], tail[1], eof[0], eof[1], self.max_records)
             return (res.fidx, res.ridx), (res.f_bad, res.r_bad), res.n_pairs, (res.f_consumed, res.r_consumed), \
-                (res.mismatch, tuple(built) if res.n_built else None)
+                (res.mismatch, self._built(built, getattr(res, "resident", 0)) if res.n_built else None)
         except (self.not_taken, ValueError) as e:
             self.refused(e)
         idx, bad, n, consumed, mismatch = F.paired_host_pass(tail, eof, self.max_records, self.threads)
@@ -1876,9 +1912,12 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
         from .engine import NotResident
         bgzf = members_out and hasattr(f, "write_members")
         try:
-            data = backend.engine.format_text(idx=idx, sel=sel, kind=kind, resident=resident, bgzf=bgzf,
-                                              **{k: v for k, v in kw.items() if k != "ee"})
-        except (NotResident, ValueError) as e:
+            more = {k: v for k, v in kw.items() if k != "ee" or v is not None}     # (ee: the USEARCH suffix; an engine without it is not eligible)
+            if kind == F.FMT_REPORT:
+                data = backend.engine.format_report(idx=idx, sel=sel, resident=resident, bgzf=bgzf, **more)
+            else:
+                data = backend.engine.format_text(idx=idx, sel=sel, kind=kind, resident=resident, bgzf=bgzf, **more)
+        except (NotResident, ValueError) as e:                 # (an ee outside what the device renders is one)
             paths.format_refused(e)
             return None
         return (lambda: f.write_members(data)) if bgzf else (lambda: f.write(data))
@@ -1967,11 +2006,18 @@ def _run_fast_fastq(args, backend, o, say, t0, paths):
 
                 hdr = dict(relabel=args.relabel or None)
                 if args.paired:
+                    # --device_format: the report lines too, on this thread, from the arrays the contig call left beside the slots
+                    done = None
+                    if paths.format and n:
+                        done = device_format(idx, None, F.FMT_REPORT, o.report,
+                                             dict(relabel_index=processed + np.arange(n), ee=ee if usearch else None, **hdr),
+                                             getattr(filtered, "resident", 0))
+
                     def write_report(buf=buf, idx=idx, aux=aux, ee=ee, first=processed, n=n, hdr=hdr):
                         everything = np.arange(n)
                         o.report.write(F.format_report(buf, idx, everything, aux, relabel_index=first + everything,
                                                        ee=ee if usearch else None, **hdr))
-                    lane(o.report).submit(write_report)
+                    lane(o.report).submit(done if done is not None else write_report)
                 good, bad = np.nonzero(label < 0)[0], np.nonzero(label >= 0)[0]
                 for sel, main_f, qual_f, lab in ((good, o.contig, o.qual, None), (bad, o.bad_contig, o.bad_qual, label)):
                     if not len(sel):

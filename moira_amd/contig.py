@@ -294,7 +294,9 @@ def contigs_from_fastq_text_filtered(fbuf, rbuf, ffinal=True, rfinal=True, max_r
                                      **kw):
     """contigs_from_fastq_filtered from the two mates' text ALONE (Engine.contigs_filter_fastq: the record indexes, the header
     comparison and the pairing are the device's) -> (res, cbuf, cidx, aux, ee, has_n, filter_error): res is the call's
-    PairedFastqResult (.fidx, .ridx, .f_bad, .r_bad, .f_consumed, .r_consumed, .mismatch, .n_built) and the six others are
+    PairedFastqResult (.fidx, .ridx, .f_bad, .r_bad, .f_consumed, .r_consumed, .mismatch, .n_built, and .resident: the generation of
+    the contigs the call left on the device, 0 when a pair was handed back or the filter refused -- nothing below makes another
+    call that would end it) and the six others are
     contigs_from_fastq_filtered's over the n_built pairs, merged the same way from the index rows the device returned.
     engine.NotTaken and ValueError are the call's: the caller indexes on the host and goes through contigs_from_fastq_filtered."""
     L = load()

@@ -217,6 +217,7 @@ int contigs_chunk(mpb_ctx *c, const char *ftext, int64_t ftext_bytes, const int6
                   const FilterAsk *fa)
 {
     CTXCHK(c);
+    resident_drop_contigs(c);                                // (the slot block may grow or be overwritten; a single-end text stays)
     if (bad_record) *bad_record = -1;
     if (n_done) *n_done = 0;
     if (n_handed_back) *n_handed_back = 0;
@@ -358,6 +359,10 @@ int mpb_contigs_filter_fastq_host(mpb_ctx *c, const char *ftext, int64_t ftext_b
                                   int64_t *filter_bad_record)
 {
     // 1. the arguments first: what is wrong with them is said with or without a device
+    int filter_rc_here = MPB_OK;                             // (whether the filter went through decides what stays resident)
+    int64_t back_here = 0;
+    if (!filter_rc) filter_rc = &filter_rc_here;
+    if (!n_handed_back) n_handed_back = &back_here;
     const FilterAsk fa{max_len, lower_n_is_base, filter_params, poisson, ee, ns, pass, len_out, flags_out, filtered, counts,
                        filter_rc, filter_bad_record};
     if (n_done) *n_done = 0;
@@ -518,5 +523,9 @@ int mpb_contigs_filter_fastq_host(mpb_ctx *c, const char *ftext, int64_t ftext_b
                      mismatches, done, nullptr, 0, nullptr, nullptr, n_done, n_handed_back, &fa, fres, index_out);
     if (rc) return rc;
     counts_out();
+    // 7. every pair built and filtered on the device: the slots, their index and the three arrays stay where they lie, the resident
+    // text of a new generation (all or nothing: a handed-back pair or a refused filter leaves none)
+    if (*why == MPB_FQ_WHY_TAKEN && nb > 0 && *n_handed_back == 0 && *filter_rc == MPB_OK)
+        resident_keep_contigs(c, st.out_buf, nb * rec_cap, st.out_idx, nb, st.overlap, st.gaps, st.mism);
     return MPB_OK;
 }

@@ -200,6 +200,9 @@ struct mpb_ctx {
     struct ResidentText {
         int64_t gen = 0, last = 0;       // the generation in force; the last one handed out
         const uint8_t *text = nullptr; int64_t text_bytes = 0; const int64_t *idx = nullptr; int64_t n = 0;
+        // the contig generation (mpb_contigs_filter_fastq_host: the slots, their index and the three arrays in contig_stage)
+        bool in_contig_stage = false;
+        const int32_t *aux[3] = {nullptr, nullptr, nullptr};     // overlap, gaps, mismatches by record; null: the generation carries none
     } resident;
     Buf pin_mem{BUF_PINNED};
     PinWords *pin = nullptr;             // (in pin_mem)
@@ -358,6 +361,12 @@ int filter_indexed(StreamQueue &q, const Indexed &in, int64_t text_bytes, uint8_
 // resident text (a new generation); resident_drop: none.  Every entry that carves either block drops it first.
 void resident_keep(mpb_ctx *c, const Indexed &in, int64_t text_bytes);
 void resident_drop(mpb_ctx *c);
+// ... the contig generation: the slot buffer, the device-written out_idx and the overlap / gaps / mismatches arrays a successful
+// mpb_contigs_filter_fastq_host left in contig_stage.  That block belongs to the contig stage: the two entries that carve it without
+// touching the index's blocks drop a generation that lies in it, and only such a one (resident_drop_contigs).
+void resident_keep_contigs(mpb_ctx *c, const uint8_t *slots, int64_t text_bytes, const int64_t *idx, int64_t n, const int32_t *overlap,
+                           const int32_t *gaps, const int32_t *mism);
+void resident_drop_contigs(mpb_ctx *c);
 // mpb_bgzf.cpp: one piece of text | tokens | slots | sizes | status rows | CRCs | offsets | the framed output, and what the host
 // keeps of a piece; shared with mpb_format.cpp, whose pieces of text are written where the kernels read them
 struct BgzfStage {

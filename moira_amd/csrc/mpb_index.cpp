@@ -111,9 +111,22 @@ void resident_keep(mpb_ctx *c, const Indexed &in, int64_t text_bytes)
 {
     c->resident.gen = ++c->resident.last;
     c->resident.text = in.st.text; c->resident.text_bytes = text_bytes; c->resident.idx = in.ix.idx; c->resident.n = in.n;
+    c->resident.in_contig_stage = false;
+    c->resident.aux[0] = c->resident.aux[1] = c->resident.aux[2] = nullptr;
+}
+
+void resident_keep_contigs(mpb_ctx *c, const uint8_t *slots, int64_t text_bytes, const int64_t *idx, int64_t n, const int32_t *overlap,
+                           const int32_t *gaps, const int32_t *mism)
+{
+    c->resident.gen = ++c->resident.last;
+    c->resident.text = slots; c->resident.text_bytes = text_bytes; c->resident.idx = idx; c->resident.n = n;
+    c->resident.in_contig_stage = true;
+    c->resident.aux[0] = overlap; c->resident.aux[1] = gaps; c->resident.aux[2] = mism;
 }
 
 void resident_drop(mpb_ctx *c) { c->resident.gen = 0; }
+
+void resident_drop_contigs(mpb_ctx *c) { if (c->resident.in_contig_stage) c->resident.gen = 0; }
 
 int64_t mpb_resident_text(mpb_ctx *c) { return c ? c->resident.gen : 0; }
 

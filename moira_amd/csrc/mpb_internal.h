@@ -318,12 +318,14 @@ void mpb_launch_pair_lists(const int8_t *cls, int64_t n, const uint32_t *prefix,
 // rows, sel, relabel_index and label_id are not trusted.  k_fmt_count + k_fmt_scan: size[nsel], prefix[nsel + 1], head[0] = the
 // bytes of the formatted text; status[0] (set to INT64_MAX by the caller) = the first k whose row fails a check.  k_fmt_write:
 // records k0..k1-1, clipped to bytes [win_lo, win_hi) of the formatted text, into out[win_hi - win_lo]; nothing when status[0] is set.
+// ee (p.has_ee): the bits of nsel doubles, by position; aux (the report kind): three arrays read at r * p.aux_stride, by record.
 struct FmParams;
 void mpb_launch_fmt_count(const uint8_t *text, const int64_t *idx, const int64_t *sel, const int64_t *relabel_index,
-                          const int32_t *label_id, int64_t nsel, const FmParams &p, int64_t *size, int64_t *prefix, int64_t *head,
-                          int64_t *status, hipStream_t s);
+                          const int32_t *label_id, const uint64_t *ee, const int32_t *const aux[3], int64_t nsel, const FmParams &p,
+                          int64_t *size, int64_t *prefix, int64_t *head, int64_t *status, hipStream_t s);
 void mpb_launch_fmt_write(const uint8_t *text, const uint8_t *blob, const int64_t *idx, const int64_t *sel,
-                          const int64_t *relabel_index, const int32_t *label_id, int64_t k0, int64_t k1, const FmParams &p,
+                          const int64_t *relabel_index, const int32_t *label_id, const uint64_t *ee, const int32_t *const aux[3],
+                          int64_t k0, int64_t k1, const FmParams &p,
                           const int64_t *prefix, const int64_t *status, int64_t win_lo, int64_t win_hi, uint8_t *out, hipStream_t s);
 // The data-parallel part of collapse (mpb_collapse_kernels.hip; what a lane does and ClParams: mpb_collapse_lane.inc).  Records
 // k < p.n_records of idx[.][6] over text[p.text_bytes] (an allocation rounded up to 16 bytes; the rows are not trusted): k_col_hash

@@ -295,8 +295,10 @@ class PairedFastqResult(ContigFilterResult):
     the two texts -- fidx / ridx, f_bad / r_bad as fastio.index(text, final, max_records) returns them for each file, n_pairs
     (min of the two record counts), mismatch (fastio.first_header_mismatch over n_pairs pairs, or -1), n_built (the pairs the
     contigs were built for: mismatch < 0 ? n_pairs : mismatch), f_consumed / r_consumed (what fastio.index(text, final, n_pairs)
-    consumes) and calls (how often the entry was asked: 1 + the capacities that had to be asked for again)."""
-    __slots__ = ("fidx", "ridx", "f_consumed", "r_consumed", "f_bad", "r_bad", "mismatch", "n_pairs", "n_built", "calls")
+    consumes), calls (how often the entry was asked: 1 + the capacities that had to be asked for again) and resident: the
+    generation of the contigs the call left on the device (cbuf, cidx and aux where they lie: Engine.format_text / format_report /
+    collapse_text take it), or 0 -- a handed-back pair or a refused filter leaves none."""
+    __slots__ = ("fidx", "ridx", "f_consumed", "r_consumed", "f_bad", "r_bad", "mismatch", "n_pairs", "n_built", "calls", "resident")
 
     def __init__(self, res, *a):
         for k in ContigResult.__slots__ + ContigFilterResult.__slots__:
@@ -693,39 +695,65 @@ class Engine:
         return int(self.lib.mpb_resident_text(self.ctx))
 
     def format_text(self, buf=None, idx=None, sel=None, kind=2, resident=None, bgzf=False, fastq_offset=33, max_len=0, relabel=None,
-                    relabel_index=None, labels=None, label_id=None, out_offset=None, clamp_q0=True):
+                    relabel_index=None, labels=None, label_id=None, out_offset=None, clamp_q0=True, ee=None, records_entry=False):
         """Records sel (None: all) of a text and its record index as fasta (kind 0), qual (1) or fastq (2) text, formatted on
-        the device (mpb_format_text_host): byte for byte fastio.format_records' on the same arguments (its `ee` is not offered).
+        the device (mpb_format_text_host; with ee, one float64 per selected record: mpb_format_records_host, which puts
+        ";ee=%.2f;size=1;" behind the header token): byte for byte fastio.format_records' on the same arguments.  An ee that is
+        not finite or not below 2^53 is a ValueError with .bad_record = k: the caller formats on the host.
+        records_entry=True: through mpb_format_records_host without ee as well (the same bytes; mpb_format_text_host is that call).
         buf + idx: the text and index go up once.  resident=g (a filter result's .resident; buf None): the text and index that
         call left on the device are read where they lie; idx is then the result's .idx, used for the record count and to size
         the output only.  -> bytes; with bgzf=True a uint8 array of the BGZF members of that text, compressed where it lies,
         without the end marker -- the bytes bgzf_compress returns for it (the counts: bgzf_stats()).
         NotResident for a generation that is no longer in force; ValueError with .bad_record = k for a selected record whose
         row, sel, relabel_index or label_id entry fails a check (nothing is written then)."""
+        return self._format_records("format_text", buf, idx, sel, kind, resident, bgzf, fastq_offset, max_len, relabel, relabel_index,
+                                    labels, label_id, out_offset, clamp_q0, ee, None, records_entry)
+
+    def format_report(self, buf=None, idx=None, aux=None, sel=None, resident=None, bgzf=False, relabel=None, relabel_index=None, ee=None):
+        """The contigs.report lines of records sel (None: all), formatted on the device (mpb_format_records_host, kind 4): byte
+        for byte fastio.format_report's on the same arguments.  buf + idx + aux (int32[n_records, 3], by record): all go up.
+        resident=g (a contigs_filter_fastq result's .resident; buf and aux None): the slots, their index and the device's own
+        overlap / gaps / mismatches arrays are read where they lie; idx is then the result's .cidx.  -> bytes, or BGZF members as
+        format_text.  NotResident for a generation that is no longer in force; ValueError for a generation that carries no aux
+        (a single-end text), and with .bad_record = k for a selected record that fails a check or an ee outside the domain."""
+        if not resident:
+            if aux is None:
+                raise ValueError("format_report: aux is needed with buf and idx")
+            aux = np.ascontiguousarray(aux, np.int32)
+            if idx is not None and aux.shape != (len(idx), 3):
+                raise ValueError("format_report: aux must be int32[n_records, 3]")
+        elif aux is not None:
+            raise ValueError("format_report: either buf, idx and aux or resident, not both")
+        return self._format_records("format_report", buf, idx, sel, 4, resident, bgzf, 33, 0, relabel, relabel_index, None, None, None,
+                                    True, ee, aux)
+
+    def _format_records(self, who, buf, idx, sel, kind, resident, bgzf, fastq_offset, max_len, relabel, relabel_index, labels, label_id,
+                        out_offset, clamp_q0, ee, aux, records_entry=False):
         if idx is None:
-            raise ValueError("format_text: idx is needed (resident form: the filter result's .idx)")
+            raise ValueError("%s: idx is needed (resident form: the result's index)" % who)
         idx, sel, nsel = _index_args(idx, sel)
         if resident is None or not resident:
             if buf is None:
-                raise ValueError("format_text: either buf and idx or resident")
+                raise ValueError("%s: either buf and idx or resident" % who)
             keep, addr, nbytes = _text_ptr(buf)
             gen = 0
         else:
             if buf is not None:
-                raise ValueError("format_text: either buf and idx or resident, not both")
+                raise ValueError("%s: either buf and idx or resident, not both" % who)
             keep, addr, nbytes, gen = None, None, 0, int(resident)
         if relabel is not None:
             relabel = relabel.encode() if isinstance(relabel, str) else bytes(relabel)
             if relabel_index is None:
-                raise ValueError("format_text: relabel without relabel_index")
+                raise ValueError("%s: relabel without relabel_index" % who)
             relabel_index = np.ascontiguousarray(relabel_index, np.int64).reshape(-1)
             if len(relabel_index) != nsel:
-                raise ValueError("format_text: relabel_index must hold one entry per selected record")
+                raise ValueError("%s: relabel_index must hold one entry per selected record" % who)
         enc, lab_arr = [], None
         if label_id is not None:
             label_id = np.ascontiguousarray(label_id, np.int32).reshape(-1)
             if len(label_id) != nsel:
-                raise ValueError("format_text: label_id must hold one entry per selected record")
+                raise ValueError("%s: label_id must hold one entry per selected record" % who)
             enc = [t.encode() if isinstance(t, str) else bytes(t) for t in (labels or [])]
             lab_arr = (C.c_char_p * max(len(enc), 1))(*enc)
         # an upper bound of the formatted text from the index: the call never has to be made twice
@@ -734,22 +762,31 @@ class Engine:
         lens = np.clip(rows[:, 3], 0, 1 << 31)
         if max_len > 0:
             lens = np.minimum(lens, int(max_len))
-        body = {0: lens + 1, 1: 4 * lens + 1, 2: 2 * lens + 4}.get(int(kind), lens)
+        body = {0: lens + 1, 1: 4 * lens + 1, 2: 2 * lens + 4, 4: 0 * lens + 40}.get(int(kind), lens)
         head = (len(relabel) + 20) if relabel is not None else np.clip(rows[:, 1], 0, 1 << 31)
         bound = int(np.sum(body + head)) + nsel * (3 + max([len(t) for t in enc] + [0]))
+        if ee is not None:
+            ee = np.ascontiguousarray(ee, np.float64).reshape(-1)
+            if len(ee) != nsel:
+                raise ValueError("%s: ee must hold one entry per selected record" % who)
+            bound += 32 * nsel
         cap = C.c_int64(bound)
         if bgzf:
             L.check(self.lib.mpb_bgzf_bound(bound, C.byref(cap)))
         out = np.empty(max(cap.value, 1), np.uint8)
         got, needed, bad, st = C.c_int64(0), C.c_int64(0), C.c_int64(-1), L.BgzfStats()
         off = int(fastq_offset)
-        rc = self.lib.mpb_format_text_host(
-            self.ctx, addr, nbytes, idx.ctypes.data if not gen else None, n, gen, sel.ctypes.data if sel is not None else None, nsel,
-            int(kind), off, off if out_offset is None else int(out_offset), 1 if clamp_q0 else 0, int(max_len),
-            relabel,
-            relabel_index.ctypes.data if relabel is not None else None, C.cast(lab_arr, C.c_void_p) if lab_arr is not None else None,
-            len(enc), label_id.ctypes.data if label_id is not None else None, 1 if bgzf else 0, out.ctypes.data, cap.value,
-            C.byref(got), C.byref(needed), C.byref(bad), C.byref(st))
+        head_args = (self.ctx, addr, nbytes, idx.ctypes.data if not gen else None, n, gen, sel.ctypes.data if sel is not None else None,
+                     nsel, int(kind), off, off if out_offset is None else int(out_offset), 1 if clamp_q0 else 0, int(max_len), relabel,
+                     relabel_index.ctypes.data if relabel is not None else None,
+                     C.cast(lab_arr, C.c_void_p) if lab_arr is not None else None, len(enc),
+                     label_id.ctypes.data if label_id is not None else None)
+        tail_args = (1 if bgzf else 0, out.ctypes.data, cap.value, C.byref(got), C.byref(needed), C.byref(bad), C.byref(st))
+        if ee is None and aux is None and int(kind) != 4 and not records_entry:
+            rc = self.lib.mpb_format_text_host(*(head_args + tail_args))
+        else:
+            rc = self.lib.mpb_format_records_host(*(head_args + (ee.ctypes.data if ee is not None else None,
+                                                                 aux.ctypes.data if aux is not None else None) + tail_args))
         del keep
         if rc == L.E_INVALID and b"is not resident" in self.lib.mpb_last_error():
             raise NotResident(self.lib.mpb_last_error().decode(errors="replace"))
@@ -907,7 +944,7 @@ class Engine:
         res = ContigFilterResult(res, *r.cut(n), filtered[:n].view(bool), counts.n_pass, counts.n_overflow, _filter_error(frc, fbad))
         return PairedFastqResult(res, fidx[:n_f.value], ridx[:n_r.value], f_cons.value, r_cons.value,
                                  _record_error(fbuf, fidx, n_f.value, f_kind.value), _record_error(rbuf, ridx, n_r.value, r_kind.value),
-                                 mis.value, n_pairs.value, n, calls)
+                                 mis.value, n_pairs.value, n, calls, self.resident_text())
 
     def decode_ascii_device(self, d_seq, d_qual, n, stride, d_out, d_len=None, fixed_len=0, fastq_offset=33,
                             d_err=None):
